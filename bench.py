@@ -13,13 +13,17 @@ rank owns) overlapped with the reduction of the own slab, one host read-back per
 a launcher starts its G ranks itself (torch.distributed.run children, started before this process touches a GPU).
 
 `value` = algorithmic bytes (E*D*s + E*8 + N*D*s per step, x ranks) / wall time, inputs
-already resident in HBM. The JSON line also carries `roofline` (dominant kernel = the segment-reduce
+already resident in HBM. A plain run does only that: set up, warm up, time --steps steps, print the line.
+With --full the JSON line also carries `roofline` (dominant kernel = the segment-reduce
 launch, timed with events on the launch stream), `cpu_baseline` (the C oracle port on a bounded sample,
 host cores of this box) — both at every N, measured on rank 0 — and per-op numbers for the other config-2 ops.
 
 Reading a 1 -> 8 curve: the N=1 headline is config 2 (E=50M per GPU), the N>1 headline config 5's share (E=100M per GPU).
-So that equal per-GPU work can be compared, the N=1 line carries `same_work.c5_share_1gpu` (E=100M, N=10M on one GPU, same
-cold step) and every N>1 line `same_work.c2_share` (E=50M per GPU through the same sharded step).
+So that equal per-GPU work can be compared, the N=1 line of a --full run carries `same_work.c5_share_1gpu` (E=100M, N=10M on
+one GPU, same cold step) and every N>1 line `same_work.c2_share` (E=50M per GPU through the same sharded step).
+
+--dump-outputs DIR writes what the last timed step returned (see dump_outputs) so that two builds can be compared output
+for output; the inputs depend only on the arguments.
 """
 import argparse
 import json
@@ -56,6 +60,36 @@ def algorithmic_bytes(op, N, E, D, s=4):
     raise KeyError(op)
 
 
+DUMP_ROW_BYTES = 32 << 20  # the row samples of all ranks together; with ids and column sums the dump stays under 64 MB
+
+
+def dump_outputs(torch, out, path, rank, world, lo=0):
+    """Write what the last timed step returned (out: [rows, D], the whole output or this rank's slab whose first row is
+    global row `lo`) under `path`:
+      scatter_add_rows.npy      a fixed sample of rows, ascending: all of them when they fit in DUMP_ROW_BYTES / world,
+                                otherwise drawn by a CPU generator seeded with the rank
+      scatter_add_row_ids.npy   their global row ids (float64, exact)
+      scatter_add_col_sums.npy  float64 sums over EVERY row of each column
+    With several ranks every rank writes its own set, prefixed rank<r>_."""
+    import numpy as np
+
+    n, d = out.shape
+    k = min(n, DUMP_ROW_BYTES // world // (d * out.element_size()))
+    if k == n:
+        rows = torch.arange(n)
+    else:
+        rows = torch.randperm(n, generator=torch.Generator().manual_seed(1234 + rank))[:k].sort().values
+    arrays = {
+        "rows": out[rows.to(out.device)].float().cpu().numpy(),
+        "row_ids": (rows + lo).double().numpy(),
+        "col_sums": out.sum(0, dtype=torch.float64).cpu().numpy(),
+    }
+    os.makedirs(path, exist_ok=True)
+    prefix = "scatter_add" if world == 1 else f"rank{rank}_scatter_add"
+    for name, a in arrays.items():
+        np.save(os.path.join(path, f"{prefix}_{name}.npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -68,9 +102,17 @@ def main():
                          "partition; the rest fall uniformly in the rank's own rows). Default: 1/70 per peer, i.e. "
                          "(G-1)/70 — every pair of partitions shares the same boundary, 10 %% in total at G=8. "
                          "(G-1)/G = an unpartitioned uniform random graph")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extra-ops", action="store_true", help="skip the per-op table (scatter_min/max/mean, index_select, index_add_)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, run the side legs too: roofline, warm, per-op table, layers, configs 3/4, "
+                         "same_work, cpu_baseline (N>1: same_work, roofline, cpu_baseline, other_cuts, spmm_src_partitioned)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip cpu_baseline")
+    ap.add_argument("--no-extra-ops", action="store_true",
+                    help="--full: skip the per-op table (scatter_min/max/mean, index_select, index_add_) and the config legs")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned as DIR/<name>.npy (float32 / float64, a fixed row sample)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     if args.workload is None:
         args.workload = "c2" if args.gpus == 1 else "c5"
 
@@ -167,6 +209,8 @@ def main():
     ms_per_step = elapsed / args.steps * 1e3
     job_bytes = world * algorithmic_bytes("scatter_add", Nloc, E, D)
     value = job_bytes / (elapsed / args.steps) / 1e9
+    if args.dump_outputs:
+        dump_outputs(torch, out, args.dump_outputs, rank, world, lo=rank * Nloc if dist is not None else 0)
 
     result = {
         "metric": "scatter_add effective HBM GB/s (algorithmic bytes / wall time, cold: index partition + bucketed segment reduce per call)",
@@ -200,7 +244,7 @@ def main():
     if rehearsal:
         result["rehearsal"] = "every rank on cuda:0 over gloo: code-path check only, NOT a measurement"
 
-    if dist is not None:
+    if dist is not None and args.full:
         def timed_variant(idx, exch, steps, warm=1, rows=None):
             nonlocal index, exchange, src
             keep = (index, exchange, src)
@@ -312,7 +356,7 @@ def main():
         except Exception as exc:  # noqa: BLE001
             result["spmm_src_partitioned"] = {"error": f"{type(exc).__name__}: {exc}"}
 
-    if rank == 0 and world == 1 and dist is None:
+    if args.full and rank == 0 and world == 1 and dist is None:
         result["roofline"] = roofline_leg(torch, gnnops, lib, src, index, Ntot, E, D, args.steps, args.workload == "c2")
         result["warm"] = warm_leg(torch, gnnops, src, index, Ntot, E, D, args.steps)
         if not args.no_extra_ops:

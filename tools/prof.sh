@@ -3,8 +3,9 @@
 tag=$1; shift
 out=$GRAFT_REPO_ROOT/gpurun_out/prof_$tag
 mkdir -p $out
+root=$(cd "$(dirname "$0")/.." && pwd)
 cd /tmp && export TMPDIR=/tmp
-timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d $out -o p -- python3 $GRAFT_REPO_ROOT/bench.py --no-cpu-baseline "$@" > $out/bench.json 2> $out/err.log
+timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d $out -o p -- python3 "$root/bench.py" --full --no-cpu-baseline "$@" > $out/bench.json 2> $out/err.log
 echo "rocprof exit $?"
 python3 - "$out" <<'PY'
 import csv, sys
