@@ -24,7 +24,6 @@
 // Algorithmic bytes per launch: E * (q row + 8 B column id (+ w row)) + N * (p row + out row) + 4 (N + 1); measured traffic
 // and the optimisation ladder: DESIGN.md §4 "Message-passing layers", profiles/round2_f_*.
 #include "common.h"
-#include <stdlib.h>
 
 namespace {
 
@@ -563,8 +562,6 @@ int launch(const Args& a0, int max_vec, hipStream_t stream) {
     while (vec > 1 && (vec > max_vec || a.K % vec != 0)) vec >>= 1;
     if (HEAVY)
         while (vec > 1 && vec * sizeof(T) > 4 && a.K / vec < 64) vec >>= 1;
-    const char* sw = getenv("GNNOPS_EDGE_VEC");   // A/B (tools/time_edge_reduce.py): force the piece width in elements
-    if (sw) { int f = atoi(sw); if (f >= 1 && f <= vec && (f & (f - 1)) == 0) vec = f; }
     if constexpr (NATIVE == 8) {
         if (vec == 8) return launch_vec<T, F, MULTI, HAS_W, 8>(a, stream);
     }
@@ -610,8 +607,6 @@ extern "C" size_t gnnops_edge_reduce_hub_workspace_bytes(int64_t E, int64_t K) {
     // below 32768 edges a hub costs one wave at most ~1.5 ms, while the three (empty) hub launches would cost every
     // launch-bound layer call on a batch of small graphs ~12 us
     if (E <= 4 * T_HUB || K <= 0) return 0;
-    const char* sw = getenv("GNNOPS_EDGE_HUBS");   // A/B (tools/time_edge_hubs.py): 0 = leave every destination to one lane group
-    if (sw && sw[0] == '0') return 0;
     return hub_layout(E, K).total;
 }
 

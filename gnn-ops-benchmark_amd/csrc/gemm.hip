@@ -449,14 +449,12 @@ __global__ __launch_bounds__(256, 2) void gemm_dma4_kernel(const uint16_t* __res
 // 256 B/clk plus 32 KiB of DMA stores against 2 x 256 MFMA cycles per SIMD); the larger wave tile reads 12 KiB per 32
 // MFMAs instead of 8 KiB per 16 and halves the L2 -> LDS bytes per flop. Same four-stage counted-vmcnt pipeline as
 // gemm_dma4_kernel; stage = A [256][32] (a4_off image) + B [32][256] as two [32][128] half images (b_off).
-// VAR 2 (default): the two wave groups ping-pong (see the main loop); VAR 1 (GNNOPS_GEMM_VAR=1, kept for A/B runs with
-// tools/time_gemm_var.py): all eight waves in lockstep with a half-step software pipeline.
 constexpr int BM2 = 256, BN2 = 256;
 constexpr int A2_BYTES = BM2 * BK4 * 2, B2_BYTES = BK4 * BN2 * 2, STAGE2_BYTES = A2_BYTES + B2_BYTES;  // 16 + 16 KiB
 constexpr int GEMM256_SMEM = NST * STAGE2_BYTES;                                                       // 128 KiB
 constexpr int EPI2_ROWS = 32;  // rows of a wave's 128 staged per epilogue round: 8 waves x 32 x CS x 4 B = 68 KiB
 
-template <typename T, bool IS_BF16, int VAR>
+template <typename T, bool IS_BF16>
 __global__ __launch_bounds__(512, 2) void gemm_dma256_kernel(const uint16_t* __restrict__ A, const uint16_t* __restrict__ Bm,
                                                              const T* __restrict__ addend, T* __restrict__ C, int64_t M,
                                                              int64_t N, int64_t K, int64_t lda, int64_t ldb, int64_t ldadd,
@@ -527,10 +525,21 @@ __global__ __launch_bounds__(512, 2) void gemm_dma256_kernel(const uint16_t* __r
     }
 
     const int64_t ksteps = K / BK4;  // even: K is a multiple of 64
-    // Fragment reads are inline asm: as builtins the transpose reads are ordered after EVERY outstanding LDS-DMA
-    // (s_waitcnt vmcnt(0)), which would undo the counted waits. Each s_waitcnt carries the registers it releases as
-    // operands, so no MFMA that uses them is scheduled above it.
-    auto read_first = [&](int64_t t, s16x4 (&blo)[4], s16x4 (&bhi)[4], s16x8 (&af)[8]) {  // B and rows 0..63 of A
+    // Ping-pong: waves 0-3 and 4-7 — wave w and w + 4 share a SIMD — run half a K-step apart, so one partner's memory
+    // phase (16 fragment reads, 4 DMA pieces at ~100 cycles of issue each, their latency) runs under the other's 32
+    // back-to-back MFMAs (all eight waves in lockstep measured 0.88 against 0.79 ms at 8192^3 bf16). Still ONE barrier
+    // per K-step kt:
+    //   waves 0-3 reach it after the MFMAs of tile kt, waves 4-7 after reading tile kt's fragments (reads retired);
+    //   every wave has waited for its own DMA pieces of tile kt+1 (vmcnt(8): tiles kt+2, kt+3 stay in flight);
+    //   behind it waves 0-3 read tile kt+1 and refill tile kt's stage with tile kt+4, waves 4-7 multiply tile kt,
+    //   then read tile kt+1 and refill tile kt's stage too (their pieces of tile kt+4 = (kt+1)+3).
+    // Both groups execute 1 + ksteps barriers. Fragments are single-buffered: a wave's MFMAs have all issued before
+    // its next reads are. Fragment reads are inline asm: as builtins the transpose reads are ordered after EVERY
+    // outstanding LDS-DMA (s_waitcnt vmcnt(0)), which would undo the counted waits. Each s_waitcnt carries the registers
+    // it releases as operands, so no MFMA that uses them is scheduled above it.
+    s16x8 af[8];
+    s16x4 blo[4], bhi[4];
+    auto read_all = [&](int64_t t) {
         const uint32_t st = (uint32_t)(t & (NST - 1)) * STAGE2_BYTES;
 #pragma unroll
         for (int ni = 0; ni < 4; ++ni) {
@@ -542,155 +551,66 @@ __global__ __launch_bounds__(512, 2) void gemm_dma256_kernel(const uint16_t* __r
         asm volatile("ds_read_b128 %0, %1 offset:1024" : "=v"(af[1]) : "v"(aa));
         asm volatile("ds_read_b128 %0, %1 offset:2048" : "=v"(af[2]) : "v"(aa));
         asm volatile("ds_read_b128 %0, %1 offset:3072" : "=v"(af[3]) : "v"(aa));
-    };
-    auto read_second = [&](int64_t t, s16x8 (&af)[8]) {  // rows 64..127 of A
-        const uint32_t aa = a_rd + (uint32_t)(t & (NST - 1)) * STAGE2_BYTES;
         asm volatile("ds_read_b128 %0, %1 offset:4096" : "=v"(af[4]) : "v"(aa));
         asm volatile("ds_read_b128 %0, %1 offset:5120" : "=v"(af[5]) : "v"(aa));
         asm volatile("ds_read_b128 %0, %1 offset:6144" : "=v"(af[6]) : "v"(aa));
         asm volatile("ds_read_b128 %0, %1 offset:7168" : "=v"(af[7]) : "v"(aa));
     };
-    s16x8 af[8];
-    // One K-step, software-pipelined in halves so the LDS reads run under this wave's own MFMAs:
-    //   rows 64..127 of tile kt are read under the MFMAs of rows 0..63; B and rows 0..63 of tile kt+1 under the MFMAs of
-    //   rows 64..127. B is double-buffered in registers (cur / nxt), A reuses af[0..3] once their MFMAs have issued.
-    auto step = [&](int64_t kt, s16x4 (&cblo)[4], s16x4 (&cbhi)[4], s16x4 (&nblo)[4], s16x4 (&nbhi)[4]) {
-        read_second(kt, af);
-        asm volatile("s_waitcnt lgkmcnt(4)"  // LDS returns in order: everything but the four reads just issued
-                     : "+v"(cblo[0]), "+v"(cblo[1]), "+v"(cblo[2]), "+v"(cblo[3]), "+v"(cbhi[0]), "+v"(cbhi[1]),
-                       "+v"(cbhi[2]), "+v"(cbhi[3]), "+v"(af[0]), "+v"(af[1]), "+v"(af[2]), "+v"(af[3]));
+    auto wait_reads = [&]() {
+        asm volatile("s_waitcnt lgkmcnt(0)"
+                     : "+v"(blo[0]), "+v"(blo[1]), "+v"(blo[2]), "+v"(blo[3]), "+v"(bhi[0]), "+v"(bhi[1]), "+v"(bhi[2]),
+                       "+v"(bhi[3]), "+v"(af[0]), "+v"(af[1]), "+v"(af[2]), "+v"(af[3]), "+v"(af[4]), "+v"(af[5]),
+                       "+v"(af[6]), "+v"(af[7]));
+    };
+    auto compute = [&]() {
         s16x8 bf[4];
 #pragma unroll
         for (int ni = 0; ni < 4; ++ni)
-            bf[ni] = s16x8{cblo[ni].x, cblo[ni].y, cblo[ni].z, cblo[ni].w, cbhi[ni].x, cbhi[ni].y, cbhi[ni].z, cbhi[ni].w};
+            bf[ni] = s16x8{blo[ni].x, blo[ni].y, blo[ni].z, blo[ni].w, bhi[ni].x, bhi[ni].y, bhi[ni].z, bhi[ni].w};
 #pragma unroll
-        for (int mi = 0; mi < 4; ++mi)
-#pragma unroll
-            for (int ni = 0; ni < 4; ++ni) acc[mi][ni] = mfma16<IS_BF16>(af[mi], bf[ni], acc[mi][ni]);
-        __builtin_amdgcn_sched_barrier(0);
-        asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(af[4]), "+v"(af[5]), "+v"(af[6]), "+v"(af[7]));
-        // tile kt+1 must have landed, tile kt+2 (4 DMA instructions) stays in flight; after the barrier every wave is
-        // done with tile kt-1's stage, which takes tile kt+3. Past the last tile the DMA re-fetches tile ksteps-1 into a
-        // stage nobody reads again: the count and the loop stay free of branches.
-        asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-        __builtin_amdgcn_s_barrier();
-        const int64_t tn = kt + NST - 1;
-        const int stn = (int)(tn & (NST - 1));
-        const int64_t k0n = (tn < ksteps ? tn : ksteps - 1) * BK4;
-        read_first(kt + 1, nblo, nbhi, af);  // past the end: a stale stage, never used
-        __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-        for (int mi = 4; mi < 8; ++mi) {
+        for (int mi = 0; mi < 8; ++mi)
 #pragma unroll
             for (int ni = 0; ni < 4; ++ni) acc[mi][ni] = mfma16<IS_BF16>(af[mi], bf[ni], acc[mi][ni]);
-            // one DMA piece behind every four MFMAs (issued right after the barrier they cost 3 % more)
-            if (mi & 1) dma_b(stn, k0n, (mi - 4) >> 1);
-            else dma_a(stn, k0n, (mi - 4) >> 1);
-            __builtin_amdgcn_sched_barrier(0);
-        }
         __builtin_amdgcn_sched_barrier(0);
     };
-
-    if constexpr (VAR == 2) {
-        // Ping-pong (the default): waves 0-3 and 4-7 — wave w and w + 4 share a SIMD — run half a K-step apart, so one
-        // partner's memory phase (16 fragment reads, 4 DMA pieces at ~100 cycles of issue each, their latency) runs under
-        // the other's 32 back-to-back MFMAs. Run in lockstep (VAR 1) both partners are in that phase together and the
-        // matrix pipe idles: 0.88 -> 0.79 ms at 8192^3 bf16. Still ONE barrier per K-step kt:
-        //   waves 0-3 reach it after the MFMAs of tile kt, waves 4-7 after reading tile kt's fragments (reads retired);
-        //   every wave has waited for its own DMA pieces of tile kt+1 (vmcnt(8): tiles kt+2, kt+3 stay in flight);
-        //   behind it waves 0-3 read tile kt+1 and refill tile kt's stage with tile kt+4, waves 4-7 multiply tile kt,
-        //   then read tile kt+1 and refill tile kt's stage too (their pieces of tile kt+4 = (kt+1)+3).
-        // Both groups execute 1 + ksteps barriers. Fragments are single-buffered: a wave's MFMAs have all issued before
-        // its next reads are.
-        s16x4 blo[4], bhi[4];
-        auto read_all = [&](int64_t t) {
-            const uint32_t st = (uint32_t)(t & (NST - 1)) * STAGE2_BYTES;
-#pragma unroll
-            for (int ni = 0; ni < 4; ++ni) {
-                asm volatile("ds_read_b64_tr_b16 %0, %1" : "=v"(blo[ni]) : "v"(b_lo_off[ni] + st));
-                asm volatile("ds_read_b64_tr_b16 %0, %1" : "=v"(bhi[ni]) : "v"(b_hi_off[ni] + st));
-            }
-            const uint32_t aa = a_rd + st;
-            asm volatile("ds_read_b128 %0, %1" : "=v"(af[0]) : "v"(aa));
-            asm volatile("ds_read_b128 %0, %1 offset:1024" : "=v"(af[1]) : "v"(aa));
-            asm volatile("ds_read_b128 %0, %1 offset:2048" : "=v"(af[2]) : "v"(aa));
-            asm volatile("ds_read_b128 %0, %1 offset:3072" : "=v"(af[3]) : "v"(aa));
-            asm volatile("ds_read_b128 %0, %1 offset:4096" : "=v"(af[4]) : "v"(aa));
-            asm volatile("ds_read_b128 %0, %1 offset:5120" : "=v"(af[5]) : "v"(aa));
-            asm volatile("ds_read_b128 %0, %1 offset:6144" : "=v"(af[6]) : "v"(aa));
-            asm volatile("ds_read_b128 %0, %1 offset:7168" : "=v"(af[7]) : "v"(aa));
-        };
-        auto wait_reads = [&]() {
-            asm volatile("s_waitcnt lgkmcnt(0)"
-                         : "+v"(blo[0]), "+v"(blo[1]), "+v"(blo[2]), "+v"(blo[3]), "+v"(bhi[0]), "+v"(bhi[1]), "+v"(bhi[2]),
-                           "+v"(bhi[3]), "+v"(af[0]), "+v"(af[1]), "+v"(af[2]), "+v"(af[3]), "+v"(af[4]), "+v"(af[5]),
-                           "+v"(af[6]), "+v"(af[7]));
-        };
-        auto compute = [&]() {
-            s16x8 bf[4];
-#pragma unroll
-            for (int ni = 0; ni < 4; ++ni)
-                bf[ni] = s16x8{blo[ni].x, blo[ni].y, blo[ni].z, blo[ni].w, bhi[ni].x, bhi[ni].y, bhi[ni].z, bhi[ni].w};
-#pragma unroll
-            for (int mi = 0; mi < 8; ++mi)
-#pragma unroll
-                for (int ni = 0; ni < 4; ++ni) acc[mi][ni] = mfma16<IS_BF16>(af[mi], bf[ni], acc[mi][ni]);
-            __builtin_amdgcn_sched_barrier(0);
-        };
-        auto dma_tile = [&](int64_t tn) { dma((int)(tn & (NST - 1)), (tn < ksteps ? tn : ksteps - 1) * BK4); };
-        dma_tile(0);
-        dma_tile(1);
-        dma_tile(2);
-        if (__builtin_amdgcn_readfirstlane(wave) < 4) {
-            dma_tile(3);
-            asm volatile("s_waitcnt vmcnt(12)" ::: "memory");  // own pieces of tile 0
+    // past the last tile the DMA re-fetches tile ksteps-1 into a stage nobody reads again: the counts stay free of branches
+    auto dma_tile = [&](int64_t tn) { dma((int)(tn & (NST - 1)), (tn < ksteps ? tn : ksteps - 1) * BK4); };
+    dma_tile(0);
+    dma_tile(1);
+    dma_tile(2);
+    if (__builtin_amdgcn_readfirstlane(wave) < 4) {
+        dma_tile(3);
+        asm volatile("s_waitcnt vmcnt(12)" ::: "memory");  // own pieces of tile 0
+        __builtin_amdgcn_s_barrier();
+        read_all(0);
+        for (int64_t kt = 0; kt < ksteps; ++kt) {
+            wait_reads();
+            compute();
+            asm volatile("s_waitcnt vmcnt(8)" ::: "memory");  // own pieces of tile kt+1; kt+2 and kt+3 stay in flight
             __builtin_amdgcn_s_barrier();
-            read_all(0);
-            for (int64_t kt = 0; kt < ksteps; ++kt) {
-                wait_reads();
-                compute();
-                asm volatile("s_waitcnt vmcnt(8)" ::: "memory");  // own pieces of tile kt+1; kt+2 and kt+3 stay in flight
-                __builtin_amdgcn_s_barrier();
-                read_all(kt + 1);   // past the end: a stale stage, never used
-                dma_tile(kt + 4);   // tile kt's stage: waves 4-7 retired their reads of it before the barrier
-                __builtin_amdgcn_sched_barrier(0);
-            }
-        } else {
+            read_all(kt + 1);   // past the end: a stale stage, never used
+            dma_tile(kt + 4);   // tile kt's stage: waves 4-7 retired their reads of it before the barrier
+            __builtin_amdgcn_sched_barrier(0);
+        }
+    } else {
+        asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
+        __builtin_amdgcn_s_barrier();
+        for (int64_t kt = 0; kt < ksteps; ++kt) {
+            read_all(kt);
+            dma_tile(kt + 3);   // tile kt-1's stage: everyone read it before the previous barrier
+            wait_reads();
             asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
             __builtin_amdgcn_s_barrier();
-            for (int64_t kt = 0; kt < ksteps; ++kt) {
-                read_all(kt);
-                dma_tile(kt + 3);   // tile kt-1's stage: everyone read it before the previous barrier
-                wait_reads();
-                asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-                __builtin_amdgcn_s_barrier();
-                compute();
-            }
+            compute();
         }
-        asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)"
-                     : "+v"(blo[0]), "+v"(blo[1]), "+v"(blo[2]), "+v"(blo[3]), "+v"(bhi[0]), "+v"(bhi[1]), "+v"(bhi[2]),
-                       "+v"(bhi[3]), "+v"(af[0]), "+v"(af[1]), "+v"(af[2]), "+v"(af[3]), "+v"(af[4]), "+v"(af[5]),
-                       "+v"(af[6]), "+v"(af[7])
-                     :
-                     : "memory");
-    } else {
-#pragma unroll
-    for (int t = 0; t < NST - 1; ++t) dma(t, (int64_t)(t < ksteps ? t : ksteps - 1) * BK4);
-    asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    s16x4 bl0[4], bh0[4], bl1[4], bh1[4];
-    read_first(0, bl0, bh0, af);
-    for (int64_t kt = 0; kt < ksteps; kt += 2) {
-        step(kt, bl0, bh0, bl1, bh1);
-        step(kt + 1, bl1, bh1, bl0, bh0);
     }
     // the reads issued for the tile past the end still target live registers: retire them before anything is reused
     asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)"
-                 : "+v"(bl0[0]), "+v"(bl0[1]), "+v"(bl0[2]), "+v"(bl0[3]), "+v"(bh0[0]), "+v"(bh0[1]), "+v"(bh0[2]),
-                   "+v"(bh0[3]), "+v"(af[0]), "+v"(af[1]), "+v"(af[2]), "+v"(af[3])
+                 : "+v"(blo[0]), "+v"(blo[1]), "+v"(blo[2]), "+v"(blo[3]), "+v"(bhi[0]), "+v"(bhi[1]), "+v"(bhi[2]),
+                   "+v"(bhi[3]), "+v"(af[0]), "+v"(af[1]), "+v"(af[2]), "+v"(af[3]), "+v"(af[4]), "+v"(af[5]),
+                   "+v"(af[6]), "+v"(af[7])
                  :
                  : "memory");
-    }
     __syncthreads();  // all DMA (including the redundant tail fetches) landed, all reads done: the stages become the epilogue's
 
     float* ctile = reinterpret_cast<float*>(smem) + wave * (EPI2_ROWS * CS);
@@ -738,28 +658,20 @@ __global__ __launch_bounds__(512, 2) void gemm_dma256_kernel(const uint16_t* __r
     }
 }
 
-template <typename T, bool IS_BF16, int VAR>
-int launch_dma256_var(const void* input, const void* mat1, const void* mat2, void* out, int64_t M, int64_t N, int64_t K,
+template <typename T, bool IS_BF16>
+int launch_dma256(const void* input, const void* mat1, const void* mat2, void* out, int64_t M, int64_t N, int64_t K,
                   int64_t lda, int64_t ldb, int64_t ldadd, const uint16_t* at, const uint16_t* bt, int64_t Kmain, hipStream_t stream) {
     static bool configured = false;
     if (!configured) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_dma256_kernel<T, IS_BF16, VAR>),
+        if (hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_dma256_kernel<T, IS_BF16>),
                                 hipFuncAttributeMaxDynamicSharedMemorySize, GEMM256_SMEM) != hipSuccess)
             return gnnops_check_launch("addmm attribute");
         configured = true;
     }
-    hipLaunchKernelGGL((gemm_dma256_kernel<T, IS_BF16, VAR>), dim3((unsigned)gnnops_cdiv(N, BN2), (unsigned)gnnops_cdiv(M, BM2)), dim3(512),
+    hipLaunchKernelGGL((gemm_dma256_kernel<T, IS_BF16>), dim3((unsigned)gnnops_cdiv(N, BN2), (unsigned)gnnops_cdiv(M, BM2)), dim3(512),
                        GEMM256_SMEM, stream, (const uint16_t*)mat1, (const uint16_t*)mat2, (const T*)input, (T*)out, M, N, K,
                        lda, ldb, ldadd, at, bt, Kmain);
     return gnnops_check_launch("addmm");
-}
-
-template <typename T, bool IS_BF16>
-int launch_dma256(const void* input, const void* mat1, const void* mat2, void* out, int64_t M, int64_t N, int64_t K,
-                  int64_t lda, int64_t ldb, int64_t ldadd, const uint16_t* at, const uint16_t* bt, int64_t Kmain, hipStream_t stream) {
-    const char* var = getenv("GNNOPS_GEMM_VAR");
-    if (var && var[0] == '1') return launch_dma256_var<T, IS_BF16, 1>(input, mat1, mat2, out, M, N, K, lda, ldb, ldadd, at, bt, Kmain, stream);
-    return launch_dma256_var<T, IS_BF16, 2>(input, mat1, mat2, out, M, N, K, lda, ldb, ldadd, at, bt, Kmain, stream);
 }
 
 // ---- split-K tail over the same 256 x 256 tiles: ONE persistent workgroup per CU --------------------------------------
@@ -801,19 +713,19 @@ __global__ __launch_bounds__(512, 2) void gemm_sk256_kernel(const uint16_t* __re
                                                             const uint16_t* __restrict__ At, const uint16_t* __restrict__ Bt,
                                                             int64_t Kmain, float* __restrict__ slots,
                                                             unsigned* __restrict__ flags, int tiles_m, int tiles_n, int dp_tiles,
-                                                            int tail_tiles, int split, int order) {
+                                                            int tail_tiles, int split) {
     extern __shared__ __attribute__((aligned(1024))) unsigned char smem256[];
     unsigned char* smem = smem256;
     __shared__ int poisoned;
 
     const int G = (int)gridDim.x;
-    const int v = ((order & 1) && (G & 7) == 0) ? ((int)blockIdx.x & 7) * (G >> 3) + ((int)blockIdx.x >> 3) : (int)blockIdx.x;
+    const int v = (G & 7) == 0 ? ((int)blockIdx.x & 7) * (G >> 3) + ((int)blockIdx.x >> 3) : (int)blockIdx.x;
     const int64_t S = K / BK4;
     int dp_next = v;
     // tail: block b = 8 i + x (XCD x): piece x mod split of tail tile i (8 / split) + x / split
     const int tail_j = (int)blockIdx.x & (split - 1);
     const int tail_t = ((int)blockIdx.x >> 3) * (8 / split) + (((int)blockIdx.x & 7) / split);
-    bool tail_left = split > 1 && tail_t < tail_tiles && !(order & 8);   // order bits 4, 8: timing-only builds of the A/B tool
+    bool tail_left = split > 1 && tail_t < tail_tiles;
     if (threadIdx.x == 0) poisoned = 0;
     const bool vec_c = (N % 8 == 0) && ((uintptr_t)C % 16 == 0) && (addend == nullptr || (uintptr_t)addend % 16 == 0);
     const bool half_c = (N % 4 == 0) && ((uintptr_t)C % 8 == 0) && (addend == nullptr || (uintptr_t)addend % 8 == 0);
@@ -837,8 +749,7 @@ __global__ __launch_bounds__(512, 2) void gemm_sk256_kernel(const uint16_t* __re
             break;
         }
         int tm, tn;
-        if (order & 2) sk_tile_rc(t, tiles_m, tiles_n, tm, tn);
-        else { tm = t / tiles_n; tn = t - tm * tiles_n; }
+        sk_tile_rc(t, tiles_m, tiles_n, tm, tn);
         const int64_t m0 = (int64_t)tm * BM2, n0 = (int64_t)tn * BN2;
         const int64_t ksteps = ke - kb;
         // per-lane constants are rebuilt for every piece from a value the compiler cannot see through: hoisted out of the
@@ -935,7 +846,7 @@ __global__ __launch_bounds__(512, 2) void gemm_sk256_kernel(const uint16_t* __re
                 for (int ni = 0; ni < 4; ++ni) acc[mi][ni] = mfma16<IS_BF16>(af[mi], bf[ni], acc[mi][ni]);
             __builtin_amdgcn_sched_barrier(0);
         };
-        // the ping-pong main loop of gemm_dma256_kernel (VAR 2), over K-steps kb .. ke-1 of this tile
+        // the ping-pong main loop of gemm_dma256_kernel, over K-steps kb .. ke-1 of this tile
         dma_tile(0);
         dma_tile(1);
         dma_tile(2);
@@ -974,7 +885,7 @@ __global__ __launch_bounds__(512, 2) void gemm_sk256_kernel(const uint16_t* __re
         __syncthreads();  // every DMA landed, every fragment read: the stages are free (epilogue staging, next piece)
 
         int mi_lo = 0, mi_hi = 8;   // the 16-row blocks of every wave's 128 rows this workgroup stores
-        if (is_tail && !(order & 4)) {
+        if (is_tail) {
             const int b0 = (int)blockIdx.x - tail_j;   // the tile's workgroups: blocks b0 .. b0 + split - 1
             mi_lo = tail_j * (8 / split);
             mi_hi = mi_lo + 8 / split;
@@ -1085,14 +996,14 @@ inline int cu_count() {
 
 // The K split of the last round's tiles (1: plain grid launch — whole rounds already, more than half a round left, or off).
 inline int sk_split_of(int64_t T, int G) {
-    const char* sw = getenv("GNNOPS_GEMM_SK");  // A/B (tools/time_gemm_sk.py): 0 = off, 3 = persistent loop for whole rounds too
+    const char* sw = getenv("GNNOPS_GEMM_SK");  // 0 = off: the plain grid launch, the tests' reference for the split
     if (sw && sw[0] == '0') return 1;
     // T < G (every tile a "last round" tile, cut so that most CUs get a piece) was tried and lost: 49 tiles of L = 1581 as
     // 196 pieces 54 vs 41 us, 64 tiles of L = 2000 58 vs 37, 100 tiles as 200 pieces 75 vs 75 — three to seven 192-KiB partial
     // tiles per workgroup cost more than the short K loops save (profiles/round3_f_gemm_streamk.txt)
     if ((G & 7) != 0 || T < G) return 1;
     const int64_t r = T % G;
-    if (r == 0) return (sw && sw[0] == '3') ? 8 : 1;
+    if (r == 0) return 1;
     const int per_xcd = G / 8;   // tail tiles one XCD can take per piece
     if (r <= per_xcd) return 8;
     if (r <= 2 * per_xcd) return 4;
@@ -1118,15 +1029,10 @@ int launch_sk256(const void* input, const void* mat1, const void* mat2, void* ou
     // cleared by a kernel, not a memset node (common.h gnnops_memset_async)
     if (gnnops_memset_async(flags, 0, sk_flag_bytes(G), stream) != hipSuccess) return gnnops_check_launch("addmm flags");
     const int tiles_m = (int)gnnops_cdiv(M, BM2), tiles_n = (int)gnnops_cdiv(N, BN2);
-    const char* od = getenv("GNNOPS_GEMM_SK_ORDER");  // A/B: bit 0 = workgroup id by XCD share, bit 1 = tile ids down bands of 8 rows
-    int order = od ? atoi(od) : 3;
-    // bits 4 and 8 (no hand-off / no tail) leave the last round's tiles WRONG: they exist for tools/time_gemm_sk_parts.py, which also
-    // sets GNNOPS_GEMM_SK_TIMING_ONLY — without that they are ignored
-    if (!getenv("GNNOPS_GEMM_SK_TIMING_ONLY")) order &= 3;
     const int tail_tiles = (int)((int64_t)tiles_m * tiles_n % G), dp_tiles = tiles_m * tiles_n - tail_tiles;
     hipLaunchKernelGGL((gemm_sk256_kernel<T, IS_BF16>), dim3((unsigned)G), dim3(512), GEMM256_SMEM, stream, (const uint16_t*)mat1,
                        (const uint16_t*)mat2, (const T*)input, (T*)out, M, N, K, lda, ldb, ldadd, at, bt, Kmain, (float*)sk_ws, flags, tiles_m,
-                       tiles_n, dp_tiles, tail_tiles, split, order);
+                       tiles_n, dp_tiles, tail_tiles, split);
     return gnnops_check_launch("addmm stream-K");
 }
 
@@ -1265,7 +1171,8 @@ __global__ __launch_bounds__(256, 4) void gemm_f32_kernel(const float* __restric
 // costs nothing and no hand-counted wait is needed. Tiles are handed out XCD-contiguously in 8-wide column strips:
 // the 32 workgroups of an XCD work on 4 x 8 neighbouring tiles (4 A panels + 8 B panels through one L2).
 // Needs K % 16 == 0, N % 4 == 0 and 16-B aligned operands (the host falls back to the 128 x 128 kernel otherwise);
-// any M and N (filler rows / columns, guarded epilogue).
+// any M and N (filler rows / columns, guarded epilogue). One wave per SIMD (four waves of 128 x 128) and register-staged
+// operands were both measured slower (profiles/round2_d_gemm_f32_variants.txt).
 constexpr int F2_BK = 16, F2_NST = 3;
 constexpr int F2_A_BYTES = 256 * F2_BK * 4;   // 16 KiB
 constexpr int F2_BROW = 1040;                  // B row pitch in bytes: 256 floats + 16 B
@@ -1273,9 +1180,6 @@ constexpr int F2_B_BYTES = F2_BK * F2_BROW;    // 16640
 constexpr int F2_STAGE = F2_A_BYTES + F2_B_BYTES;
 constexpr int F2_SMEM = F2_NST * F2_STAGE;     // 99072 B (the epilogue's 8 x 32 x 68 floats = 69632 B fit inside)
 
-// DBG (timing-only builds behind GNNOPS_GEMM_F32_DBG, wrong results): 1 no DMA inside the loop, 2 no fragment reads inside
-// the loop, 3 no barrier / wait at the top of a K-step — which part of a K-step the matrix pipe waits for.
-template <bool STAGGER, int DBG = 0>
 __global__ __launch_bounds__(512, 2) void gemm_f32_dma256_kernel(const float* __restrict__ A, const float* __restrict__ Bm,
                                                                  const float* __restrict__ addend, float* __restrict__ C,
                                                                  int64_t M, int64_t N, int64_t K, int tiles_m, int tiles_n, int64_t ldadd) {
@@ -1336,127 +1240,56 @@ __global__ __launch_bounds__(512, 2) void gemm_f32_dma256_kernel(const float* __
     const int64_t ksteps = K / F2_BK;
     dma(0, 0);
     if (ksteps > 1) dma(1, F2_BK);
-    f32x4 af[8], af2[8];
-    float bf[4][4], bf2[4][4];
-    auto read_into = [&](int64_t kt, f32x4 (&fa)[8], float (&fb)[4][4]) {
+    f32x4 af[8];
+    float bf[4][4];
+    auto read_frags = [&](int64_t kt) {
         const unsigned char* sA = smemf + (int)(kt % F2_NST) * F2_STAGE;
         const unsigned char* sB = sA + F2_A_BYTES;
 #pragma unroll
-        for (int mi = 0; mi < 8; ++mi) fa[mi] = *reinterpret_cast<const f32x4*>(sA + a4_off(a_row + mi * 16, q));
+        for (int mi = 0; mi < 8; ++mi) af[mi] = *reinterpret_cast<const f32x4*>(sA + a4_off(a_row + mi * 16, q));
 #pragma unroll
         for (int j = 0; j < 4; ++j)
 #pragma unroll
             for (int ni = 0; ni < 4; ++ni)
-                fb[ni][j] = *reinterpret_cast<const float*>(sB + (4 * q + j) * F2_BROW + (wc * 64 + ni * 16 + (lane & 15)) * 4);
+                bf[ni][j] = *reinterpret_cast<const float*>(sB + (4 * q + j) * F2_BROW + (wc * 64 + ni * 16 + (lane & 15)) * 4);
     };
-    auto mfma_from = [&](int j0, const f32x4 (&fa)[8], const float (&fb)[4][4]) {
+    auto mfma_half = [&](int j0) {
 #pragma unroll
         for (int j = j0; j < j0 + 2; ++j)
 #pragma unroll
             for (int mi = 0; mi < 8; ++mi)
 #pragma unroll
                 for (int ni = 0; ni < 4; ++ni)
-                    acc[mi][ni] = __builtin_amdgcn_mfma_f32_16x16x4f32(fa[mi][j], fb[ni][j], acc[mi][ni], 0, 0, 0);
+                    acc[mi][ni] = __builtin_amdgcn_mfma_f32_16x16x4f32(af[mi][j], bf[ni][j], acc[mi][ni], 0, 0, 0);
     };
-    auto read_frags = [&](int64_t kt) { read_into(kt, af, bf); };
-    auto mfma_half = [&](int j0) { mfma_from(j0, af, bf); };
-    if constexpr (DBG == 5) {
-        // REGISTER-STAGED operands: global_load_dwordx4 into registers right after the fragment reads, ds_write_b128 after the
-        // MFMAs. Same LDS image (the swizzle is on the source address, the write goes to piece * 1 KiB + lane * 16 B). A
-        // global_load_lds instruction costs the issuing wave ~100 cycles of issue during which it feeds no MFMA
-        // (MI355X_MICROARCH.md "LDS-DMA piece issue cost"); a dwordx4 load ~4 and a ds_write_b128 ~13.
-        typedef float f4 __attribute__((ext_vector_type(4)));
-        f4 ra[2], rb[2];
-        auto gload = [&](int64_t k0) {
-#pragma unroll
-            for (int p = 0; p < 2; ++p) {
-                ra[p] = *reinterpret_cast<const f4*>(a_src[p] + k0);
-                rb[p] = *reinterpret_cast<const f4*>(b_src[p] + k0 * N);
-            }
-        };
-        auto swrite = [&](int stage) {
-            unsigned char* base = smemf + stage * F2_STAGE;
-#pragma unroll
-            for (int p = 0; p < 2; ++p) {
-                *reinterpret_cast<f4*>(base + (wave * 2 + p) * 1024 + lane * 16) = ra[p];
-                *reinterpret_cast<f4*>(base + F2_A_BYTES + (wave * 2 + p) * F2_BROW + lane * 16) = rb[p];
-            }
-        };
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the two tiles the DMA prologue fetched
-        for (int64_t kt = 0; kt < ksteps; ++kt) {
-            __syncthreads();
-            read_frags(kt);
-            const bool more = kt + 2 < ksteps;
-            if (more) gload((kt + 2) * F2_BK);
-            mfma_half(0);
-            mfma_half(2);
-            if (more) swrite((int)((kt + 2) % F2_NST));
-        }
-    } else if constexpr (DBG == 4) {
-        // SOFTWARE-PIPELINED fragments: the barrier for tile kt+1 and its fragment reads (into the second register set) sit
-        // in the MIDDLE of tile kt's MFMA block, so the burst of LDS reads all eight waves issue behind a barrier
-        // (~600 LDS cycles for 8 x 16 reads) runs under the second half's 64 MFMAs instead of in front of an idle pipe.
+    // PING-PONG: wave w and wave w+4 share a SIMD. Waves 4-7 run half a K-step behind waves 0-3: in every phase one
+    // of the two does its memory work (wait, barrier, fragment reads, four DMA instructions — each ~100 cycles of
+    // issue during which the wave feeds no MFMA) and the first 64 MFMAs of its tile, while its partner issues the last
+    // 64 MFMAs of ITS tile back to back; in lockstep both partners stalled at the same time and the matrix pipe idled
+    // ~12 % of a K-step (profiles/round2_d_gemm_f32_variants.txt). One barrier per phase. A wave waits for its own DMA
+    // pieces (vmcnt(0)) before the barrier that opens its memory phase: pieces of tile t are issued two of the wave's
+    // memory phases earlier and are visible to everyone from the barrier after the wave's NEXT memory phase on — before
+    // any wave reads tile t. The two groups run the same loop body, shifted by one barrier: b0 | G0: mem(0) + first
+    // half | b1 | G0: second half, G1: mem(0) + first half | b2 | G0: mem(1) + first half, G1: second half | ... Every
+    // wave passes the same number of barriers (2 * ksteps + 1).
+    const int grp = __builtin_amdgcn_readfirstlane(wave >> 2);
+    if (grp == 1) {                                             // b0: waves 4-7 start one phase late
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");        // (their pieces of tiles 0 and 1 are waited for here)
+        __syncthreads();
+    }
+    for (int64_t kt = 0; kt < ksteps; ++kt) {
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();
-        read_into(0, af, bf);
-        auto step = [&](int64_t kt, f32x4 (&ca)[8], float (&cb)[4][4], f32x4 (&na)[8], float (&nb)[4][4]) {
-            mfma_from(0, ca, cb);
-            if (kt + 1 < ksteps) {
-                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // tile kt+1: issued one K-step ago
-                __syncthreads();
-                read_into(kt + 1, na, nb);
-                if (kt + 2 < ksteps) dma((int)((kt + 2) % F2_NST), (kt + 2) * F2_BK);   // stage of tile kt-1: read a K-step ago
-            }
-            mfma_from(2, ca, cb);
-        };
-        int64_t kt = 0;
-        for (; kt + 1 < ksteps; kt += 2) {
-            step(kt, af, bf, af2, bf2);
-            step(kt + 1, af2, bf2, af, bf);
-        }
-        if (kt < ksteps) step(kt, af, bf, af2, bf2);
-    } else
-    if constexpr (!STAGGER) {
-        for (int64_t kt = 0; kt < ksteps; ++kt) {
-            if (DBG != 3) {
-                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // this wave's pieces of tiles kt (and kt+1: a whole K-step old)
-                __syncthreads();                                    // everyone's pieces landed; everyone is done reading tile kt-1
-            }
-            if (DBG != 2 || kt == 0) read_frags(kt);
-            if (DBG != 1 && kt + 2 < ksteps) dma((int)((kt + 2) % F2_NST), (kt + 2) * F2_BK);   // its stage was read in step kt-1
-            mfma_half(0);
-            mfma_half(2);
-        }
-    } else {
-        // PING-PONG: wave w and wave w+4 share a SIMD. Waves 4-7 run half a K-step behind waves 0-3: in every phase one
-        // of the two does its memory work (wait, barrier, fragment reads, four DMA instructions — each ~100 cycles of
-        // issue during which the wave feeds no MFMA) and the first 64 MFMAs of its tile, while its partner issues the last
-        // 64 MFMAs of ITS tile back to back; in lockstep both partners stalled at the same time and the matrix pipe idled
-        // ~12 % of a K-step. One barrier per phase. A wave waits for its own DMA pieces (vmcnt(0)) before the barrier
-        // that opens its memory phase: pieces of tile t are issued two of the wave's memory phases earlier and are
-        // visible to everyone from the barrier after the wave's NEXT memory phase on — before any wave reads tile t.
-        // The two groups run the same loop body, shifted by one barrier: b0 | G0: mem(0) + first half | b1 | G0: second
-        // half, G1: mem(0) + first half | b2 | G0: mem(1) + first half, G1: second half | ... Every wave passes the same
-        // number of barriers (2 * ksteps + 1).
-        const int grp = __builtin_amdgcn_readfirstlane(wave >> 2);
-        if (grp == 1) {                                             // b0: waves 4-7 start one phase late
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");        // (their pieces of tiles 0 and 1 are waited for here)
-            __syncthreads();
-        }
-        for (int64_t kt = 0; kt < ksteps; ++kt) {
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            __syncthreads();
-            read_frags(kt);
-            if (kt + 2 < ksteps) dma((int)((kt + 2) % F2_NST), (kt + 2) * F2_BK);
-            mfma_half(0);
-            // phase boundary only: no wait here (a `__syncthreads()` would wait vmcnt(0) for the DMA issued half a K-step
-            // ago). What the protocol needs from this barrier — this wave's fragment reads of tile kt are complete — holds:
-            // the MFMAs above consumed them.
-            asm volatile("s_barrier" ::: "memory");
-            mfma_half(2);
-        }
-        if (grp == 0) asm volatile("s_barrier" ::: "memory");      // the barrier waves 4-7 opened their last half with
+        read_frags(kt);
+        if (kt + 2 < ksteps) dma((int)((kt + 2) % F2_NST), (kt + 2) * F2_BK);   // its stage held tile kt-1
+        mfma_half(0);
+        // phase boundary only: no wait here (a `__syncthreads()` would wait vmcnt(0) for the DMA issued half a K-step
+        // ago). What the protocol needs from this barrier — this wave's fragment reads of tile kt are complete — holds:
+        // the MFMAs above consumed them.
+        asm volatile("s_barrier" ::: "memory");
+        mfma_half(2);
     }
+    if (grp == 0) asm volatile("s_barrier" ::: "memory");      // the barrier waves 4-7 opened their last half with
     __syncthreads();   // the stages are free: the epilogue reuses them
 
     // epilogue: each wave stages its 128 x 64 tile through LDS in four rounds of 32 rows and writes 16-B row pieces
@@ -1479,174 +1312,6 @@ __global__ __launch_bounds__(512, 2) void gemm_f32_dma256_kernel(const float* __
             const int64_t row = m0 + wr * 128 + c * 32 + rr;
             const int64_t col = n0 + wc * 64 + pc;
             f32x4 v = *reinterpret_cast<const f32x4*>(&ctile[rr * CS + pc]);
-            if (row >= M || col >= N) continue;
-            if (vec_c && col + 4 <= N) {
-                if (addend) {
-                    const f32x4 g = *reinterpret_cast<const f32x4*>(addend + row * ldadd + col);
-                    v[0] += g[0]; v[1] += g[1]; v[2] += g[2]; v[3] += g[3];
-                }
-                *reinterpret_cast<f32x4*>(C + row * N + col) = v;
-            } else {
-#pragma unroll
-                for (int i = 0; i < 4; ++i)
-                    if (col + i < N) C[row * N + col + i] = v[i] + (addend ? addend[row * ldadd + col + i] : 0.f);
-            }
-        }
-        __builtin_amdgcn_wave_barrier();
-    }
-}
-
-// ---- fp32, one wave per SIMD: 256 x 256 block tile, FOUR waves of 128 x 128 --------------------------------------
-// The eight-wave kernel above keeps the matrix pipe busy 87.7 % of the cycles (PMC, profiles/round2_d_gemm_f32_pmc.txt): all
-// eight waves read their fragments in one burst behind each barrier (~600 LDS cycles per 8192 MFMA cycles) and two waves
-// of 256 registers have no room to double-buffer them. Here a wave owns a whole SIMD and its 512-register file: 256
-// accumulator registers (8 x 8 MFMA tiles), two sets of fragments (A 8 x b128, B 8 x 4 scalars: 64 registers each). The
-// barrier for tile t+1, its fragment reads and the DMA of tile t+2 sit in the MIDDLE of tile t's 256 MFMAs, the DMA
-// instructions spread between MFMA groups, so nothing the wave waits for is on the critical path of the matrix pipe.
-// Same stages, LDS images, k-permutation and tile order as gemm_f32_dma256_kernel; LDS traffic per K-step is 64 KiB
-// instead of 96 (128 x 128 wave tiles).
-constexpr int W4_CS = 132;   // epilogue row stride in floats (128 + 4)
-
-__global__ __launch_bounds__(256, 1) void gemm_f32_w4_kernel(const float* __restrict__ A, const float* __restrict__ Bm,
-                                                             const float* __restrict__ addend, float* __restrict__ C,
-                                                             int64_t M, int64_t N, int64_t K, int tiles_m, int tiles_n, int64_t ldadd) {
-    extern __shared__ __attribute__((aligned(1024))) unsigned char smemw[];
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int wr = wave >> 1, wc = wave & 1;   // 2 x 2 waves: rows wr*128, columns wc*128
-
-    constexpr int W = 8;
-    const int64_t t = xcd_contiguous(blockIdx.x, gridDim.x);
-    const int full_strips = tiles_n / W;
-    const int64_t in_full = (int64_t)full_strips * W * tiles_m;
-    int by, bx;
-    if (t < in_full) {
-        const int64_t strip = t / ((int64_t)W * tiles_m), r = t % ((int64_t)W * tiles_m);
-        by = (int)(r / W);
-        bx = (int)(strip * W + r % W);
-    } else {
-        const int wl = tiles_n - full_strips * W;
-        const int64_t r = t - in_full;
-        by = (int)(r / wl);
-        bx = full_strips * W + (int)(r % wl);
-    }
-    const int64_t m0 = (int64_t)by * 256, n0 = (int64_t)bx * 256;
-
-    f32x4 acc[8][8];
-#pragma unroll
-    for (int i = 0; i < 8; ++i)
-#pragma unroll
-        for (int j = 0; j < 8; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-
-    // this wave's DMA pieces per stage: A pieces 4w .. 4w+3 (16 rows x 64 B each), B rows 4w .. 4w+3 (1 KiB each)
-    const float* a_src[4];
-    const float* b_src[4];
-#pragma unroll
-    for (int p = 0; p < 4; ++p) {
-        const int ar = (wave * 4 + p) * 16 + (lane >> 2);
-        const int64_t arow = (m0 + ar < M) ? m0 + ar : M - 1;
-        a_src[p] = A + arow * K + (((lane & 3) ^ a4_swz(ar)) << 2);
-        int64_t bcol = n0 + lane * 4;
-        if (bcol > N - 4) bcol = N - 4;
-        b_src[p] = Bm + (int64_t)(wave * 4 + p) * N + bcol;
-    }
-    // LDS-DMA as ONE asm statement (M0 = the wave-uniform LDS destination, written in the statement that reads it —
-    // cdna_hip_programming.md §5.7): as a builtin the compiler drains every outstanding LDS read before it (lgkmcnt(0)) and
-    // every outstanding DMA before the next LDS read (vmcnt(0)); here the protocol below owns both orders.
-    const uint32_t lds0 = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) unsigned char*)smemw;
-    auto glds = [&](const float* gsrc, uint32_t lds_dst) {
-        unsigned keep;
-        asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-                     : "=&s"(keep) : "v"(gsrc), "s"(lds_dst) : "memory");
-    };
-    auto dma_a = [&](int stage, int64_t k0, int p) { glds(a_src[p] + k0, lds0 + stage * F2_STAGE + (wave * 4 + p) * 1024); };
-    auto dma_b = [&](int stage, int64_t k0, int p) {
-        glds(b_src[p] + k0 * N, lds0 + stage * F2_STAGE + F2_A_BYTES + (wave * 4 + p) * F2_BROW);
-    };
-    auto dma_all = [&](int stage, int64_t k0) {
-#pragma unroll
-        for (int p = 0; p < 4; ++p) { dma_a(stage, k0, p); dma_b(stage, k0, p); }
-    };
-
-    const int a_row = wr * 128 + (lane & 15);
-    const int q = lane >> 4;
-    const int64_t ksteps = K / F2_BK;
-    // ONE set of fragment registers in two halves that roll: (a_lo, b_lo) = k-steps j = 0, 1 of a tile, (a_hi, b_hi) =
-    // j = 2, 3. While the MFMAs of one half run, the other half's registers are free and receive what comes next.
-    typedef float f32x2 __attribute__((ext_vector_type(2)));
-    f32x2 a_lo[8], a_hi[8];
-    float b_lo[8][2], b_hi[8][2];
-    auto read_half = [&](int64_t kt, int h, f32x2 (&fa)[8], float (&fb)[8][2]) {
-        const unsigned char* sA = smemw + (int)(kt % F2_NST) * F2_STAGE;
-        const unsigned char* sB = sA + F2_A_BYTES;
-#pragma unroll
-        for (int mi = 0; mi < 8; ++mi) fa[mi] = *reinterpret_cast<const f32x2*>(sA + a4_off(a_row + mi * 16, q) + h * 8);
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-            for (int ni = 0; ni < 8; ++ni)
-                fb[ni][j] = *reinterpret_cast<const float*>(sB + (4 * q + 2 * h + j) * F2_BROW + (wc * 128 + ni * 16 + (lane & 15)) * 4);
-    };
-    // The 64 accumulator tiles fill the accumulator half of the register file exactly (256 AGPRs). As a builtin the
-    // compiler rotates them through spare registers (D != C plus hundreds of v_accvgpr moves per K-step); as an asm
-    // statement with a read-write "a" operand each tile stays where it is (accumulate chain: no wait states needed
-    // between an MFMA and the next one that takes its D whole as C — cdna_hip_programming.md §5.7 item 2).
-    auto mfma_j = [&](int j, const f32x2 (&fa)[8], const float (&fb)[8][2]) {
-#pragma unroll
-        for (int mi = 0; mi < 8; ++mi)
-#pragma unroll
-            for (int ni = 0; ni < 8; ++ni)
-                asm("v_mfma_f32_16x16x4_f32 %0, %1, %2, %0" : "+a"(acc[mi][ni]) : "v"(fa[mi][j]), "v"(fb[ni][j]));
-    };
-
-    dma_all(0, 0);
-    if (ksteps > 1) dma_all(1, F2_BK);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    read_half(0, 0, a_lo, b_lo);
-    for (int64_t kt = 0; kt < ksteps; ++kt) {
-        read_half(kt, 1, a_hi, b_hi);           // second half of THIS tile: lands under the 128 MFMAs below
-        mfma_j(0, a_lo, b_lo);
-        mfma_j(1, a_lo, b_lo);
-        const bool next = kt + 1 < ksteps, more = kt + 2 < ksteps;
-        const int st2 = (int)((kt + 2) % F2_NST);
-        const int64_t k2 = (kt + 2) * F2_BK;
-        if (next) {
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // tile kt+1: its DMA was issued one K-step ago
-            __syncthreads();                                    // everyone's pieces landed; everyone has read all of tile kt
-            read_half(kt + 1, 0, a_lo, b_lo);                   // first half of the NEXT tile, under the MFMAs below
-        }
-        // the DMA of tile kt+2 (its stage held tile kt-1) between the MFMA groups of the second half. (Staging these
-        // operands through registers instead — dwordx4 loads here, ds_write_b128 after the last MFMA — measured SLOWER:
-        // 117.6 vs 122.5 TFLOP/s at 8192^3, profiles/round2_d_gemm_f32_variants.txt.)
-        if (more) { dma_a(st2, k2, 0); dma_b(st2, k2, 0); dma_a(st2, k2, 1); dma_b(st2, k2, 1); }
-        mfma_j(0, a_hi, b_hi);
-        if (more) { dma_a(st2, k2, 2); dma_b(st2, k2, 2); dma_a(st2, k2, 3); dma_b(st2, k2, 3); }
-        mfma_j(1, a_hi, b_hi);
-    }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();   // the stages are free: the epilogue reuses them
-
-    // epilogue: each wave stages its 128 x 128 tile through LDS in four rounds of 32 rows and writes 16-B row pieces
-    float* ctile = reinterpret_cast<float*>(smemw) + wave * (32 * W4_CS);
-    const bool vec_c = (N % 4 == 0) && ((uintptr_t)C % 16 == 0) && (addend == nullptr || (uintptr_t)addend % 16 == 0);
-    const int pr = lane >> 5, pc = (lane & 31) * 4;   // 32 lanes x 4 columns per row, 2 rows per pass
-#pragma unroll
-    for (int c = 0; c < 4; ++c) {
-#pragma unroll
-        for (int h = 0; h < 2; ++h)
-#pragma unroll
-            for (int ni = 0; ni < 8; ++ni)
-#pragma unroll
-                for (int r = 0; r < 4; ++r)
-                    ctile[(h * 16 + (lane >> 4) * 4 + r) * W4_CS + ni * 16 + (lane & 15)] = acc[c * 2 + h][ni][r];
-        __builtin_amdgcn_wave_barrier();
-#pragma unroll
-        for (int pass = 0; pass < 16; ++pass) {
-            const int rr = pass * 2 + pr;
-            const int64_t row = m0 + wr * 128 + c * 32 + rr;
-            const int64_t col = n0 + wc * 128 + pc;
-            f32x4 v = *reinterpret_cast<const f32x4*>(&ctile[rr * W4_CS + pc]);
             if (row >= M || col >= N) continue;
             if (vec_c && col + 4 <= N) {
                 if (addend) {
@@ -1770,11 +1435,11 @@ struct GemmPlan {
     size_t sk_bytes;      // slots + flags of gemm_sk256_kernel
 };
 
-// Whole padded copies or in-place reads? Measured over the reference's sweep (tools/time_gemm_pad.py,
-// profiles/round3_f_gemm_pad_modes.txt): B read in place costs nothing at any size (256-B row pieces); A in place (64-B
-// row pieces at a pitch that is no multiple of a cache line) costs 2 % of the product at L = 4684 and 15-20 % at L = 8045,
-// so from ~30 M elements on A is copied into padded rows (a copy is L^2, the penalty L^3). The 128 x 128 kernel moves twice
-// the bytes per flop: once there is more than one workgroup per CU both operands are copied.
+// Whole padded copies or in-place reads? Measured over the reference's sweep (profiles/round3_f_gemm_pad_modes.txt):
+// B read in place costs nothing at any size (256-B row pieces); A in place (64-B row pieces at a pitch that is no
+// multiple of a cache line) costs 2 % of the product at L = 4684 and 15-20 % at L = 8045, so from ~30 M elements on A
+// is copied into padded rows (a copy is L^2, the penalty L^3). The 128 x 128 kernel moves twice the bytes per flop:
+// once there is more than one workgroup per CU both operands are copied.
 inline void gemm_copy_whole(int64_t M, int64_t N, int64_t K, int path, bool& a, bool& b) {
     if (path == 1) {
         a = b = gnnops_cdiv(M, BM) * gnnops_cdiv(N, BN) > cu_count();
@@ -1786,23 +1451,18 @@ inline void gemm_copy_whole(int64_t M, int64_t N, int64_t K, int path, bool& a, 
 
 inline GemmPlan gemm_plan(int64_t M, int64_t N, int64_t K) {
     GemmPlan g{};
-    const char* sw = getenv("GNNOPS_GEMM_NO_DMA");  // A/B switch for tools/time_gemm.py: 1 = register staging, 3 = 128 x 128 DMA only
     const bool aligned = M % BM == 0 && N % BN == 0 && K % BK == 0;
-    const bool dma = K > 0 && !(sw && sw[0] == '1') && (aligned || (M >= 512 && N >= 512 && K >= 256));
+    const bool dma = K > 0 && (aligned || (M >= 512 && N >= 512 && K >= 256));
     if (dma) {
-        const char* mn = getenv("GNNOPS_GEMM_MIN256");  // A/B: least number of 256 x 256 tiles that takes the big-tile kernel
-        const int64_t min256 = mn ? atoll(mn) : 128;  // measured: 144 tiles 0.062 vs 0.086 ms, 100 tiles 0.056 vs 0.046 (tools/time_gemm_tiles.py)
-        g.path = (gnnops_cdiv(M, BM2) * gnnops_cdiv(N, BN2) >= min256 && !(sw && sw[0] == '3')) ? 2 : 1;
+        // 256 x 256 tiles from 128 of them on (measured: 144 tiles 0.062 vs 0.086 ms, 100 tiles 0.056 vs 0.046)
+        g.path = gnnops_cdiv(M, BM2) * gnnops_cdiv(N, BN2) >= 128 ? 2 : 1;
         // Operands are read in place where that is cheaper, with only the last K-tile copied (zeros past K; a B row's last
         // 16-B piece may run into the next row, and behind B's very last row there is no next row), or copied whole into
-        // aligned zero-padded rows. GNNOPS_GEMM_PAD = full | a | b | none forces a choice (tools/time_gemm_pad.py).
+        // aligned zero-padded rows. GNNOPS_GEMM_PAD=full copies both whole (the tests' reference for the in-place reads).
         const bool need = K % 64 != 0 || N % 8 != 0;
         const char* pd = getenv("GNNOPS_GEMM_PAD");
         bool whole_a = false, whole_b = false;
         if (pd && pd[0] == 'f') whole_a = whole_b = true;
-        else if (pd && pd[0] == 'a') whole_a = true;
-        else if (pd && pd[0] == 'b') whole_b = true;
-        else if (pd && pd[0] == 'n') whole_a = whole_b = false;
         else gemm_copy_whole(M, N, K, g.path, whole_a, whole_b);
         g.Kp = round_up(K, 64);
         g.copy_a = whole_a && (K % 64 != 0 || K % 8 != 0);
@@ -1887,47 +1547,18 @@ extern "C" int gnnops_addmm_ld(const void* input, int64_t ldadd, const void* mat
     if (dtype == GNNOPS_F32) {
         const bool a_vec = (K % 4 == 0) && ((uintptr_t)mat1 % 16 == 0);
         const bool b_vec = (N % 4 == 0) && ((uintptr_t)mat2 % 16 == 0);
-        // big problems with whole K-steps and 16-B aligned rows: 256 x 256 tiles staged by LDS-DMA (GNNOPS_GEMM_F32_BIG=0: off)
+        // big problems with whole K-steps and 16-B aligned rows: 256 x 256 tiles staged by LDS-DMA
         const int64_t tm = gnnops_cdiv(M, 256), tn = gnnops_cdiv(N, 256);
-        const char* big = getenv("GNNOPS_GEMM_F32_BIG");
-        if (a_vec && b_vec && K % F2_BK == 0 && K >= 2 * F2_BK && N >= 4 && tm * tn >= 128 && tm * tn < ((int64_t)1 << 31) &&
-            !(big && big[0] == '0')) {
+        if (a_vec && b_vec && K % F2_BK == 0 && K >= 2 * F2_BK && N >= 4 && tm * tn >= 128 && tm * tn < ((int64_t)1 << 31)) {
             static bool configured = false;
             if (!configured) {
-                if (hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_f32_dma256_kernel<true>),
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, F2_SMEM) != hipSuccess ||
-                    hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_f32_dma256_kernel<false>),
+                if (hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_f32_dma256_kernel),
                                         hipFuncAttributeMaxDynamicSharedMemorySize, F2_SMEM) != hipSuccess)
                     return gnnops_check_launch("addmm f32 attribute");
                 configured = true;
             }
-            if (big && big[0] == '4') {   // one wave per SIMD: four waves of 128 x 128 (A/B: tools/time_gemm_f32_dbg.py)
-                static bool cfg4 = false;
-                if (!cfg4) {
-                    if (hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_f32_w4_kernel),
-                                            hipFuncAttributeMaxDynamicSharedMemorySize, F2_SMEM) != hipSuccess)
-                        return gnnops_check_launch("addmm f32 w4 attribute");
-                    cfg4 = true;
-                }
-                hipLaunchKernelGGL(gemm_f32_w4_kernel, dim3((unsigned)(tm * tn)), dim3(256), F2_SMEM, stream, (const float*)mat1,
-                                   (const float*)mat2, (const float*)input, (float*)out, M, N, K, (int)tm, (int)tn, ldadd);
-                return gnnops_check_launch("addmm f32 w4");
-            }
-            const char* dbg = getenv("GNNOPS_GEMM_F32_DBG");
-            if (dbg && dbg[0] >= '1' && dbg[0] <= '5') {
-                auto kfn = dbg[0] == '1' ? &gemm_f32_dma256_kernel<false, 1> : dbg[0] == '2' ? &gemm_f32_dma256_kernel<false, 2>
-                           : dbg[0] == '3' ? &gemm_f32_dma256_kernel<false, 3> : dbg[0] == '4' ? &gemm_f32_dma256_kernel<false, 4>
-                           : &gemm_f32_dma256_kernel<false, 5>;
-                if (hipFuncSetAttribute(reinterpret_cast<const void*>(kfn), hipFuncAttributeMaxDynamicSharedMemorySize, F2_SMEM) != hipSuccess)
-                    return gnnops_check_launch("addmm f32 attribute");
-                hipLaunchKernelGGL(kfn, dim3((unsigned)(tm * tn)), dim3(512), F2_SMEM, stream,
-                                   (const float*)mat1, (const float*)mat2, (const float*)input, (float*)out, M, N, K, (int)tm, (int)tn, ldadd);
-            } else if (big && big[0] == '1')   // A/B: all eight waves in lockstep (tools/time_gemm_f32.py)
-                hipLaunchKernelGGL(gemm_f32_dma256_kernel<false>, dim3((unsigned)(tm * tn)), dim3(512), F2_SMEM, stream,
-                                   (const float*)mat1, (const float*)mat2, (const float*)input, (float*)out, M, N, K, (int)tm, (int)tn, ldadd);
-            else
-                hipLaunchKernelGGL(gemm_f32_dma256_kernel<true>, dim3((unsigned)(tm * tn)), dim3(512), F2_SMEM, stream,
-                                   (const float*)mat1, (const float*)mat2, (const float*)input, (float*)out, M, N, K, (int)tm, (int)tn, ldadd);
+            hipLaunchKernelGGL(gemm_f32_dma256_kernel, dim3((unsigned)(tm * tn)), dim3(512), F2_SMEM, stream,
+                               (const float*)mat1, (const float*)mat2, (const float*)input, (float*)out, M, N, K, (int)tm, (int)tn, ldadd);
             return gnnops_check_launch("addmm f32 256");
         }
         dim3 fgrid((unsigned)gnnops_cdiv(N, BN), (unsigned)gnnops_cdiv(M, BM));

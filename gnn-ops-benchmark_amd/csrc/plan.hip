@@ -205,8 +205,7 @@ extern "C" int gnnops_index_max(const int64_t* index, int64_t E, int64_t* d_max,
     if (gnnops_memset_async(d_max, 0xff, sizeof(int64_t), stream) != hipSuccess)
         return gnnops_check_launch("index_max memset");
     if (E > 0) {
-        int grid = gnnops_grid_cap(gnnops_cdiv(E, 256 * 8), 256);  // one workgroup per CU: 55 us against 75 us with 1024 or more (tools/time_index_max.py)
-        if (const char* g = getenv("GNNOPS_IMAX_GRID")) grid = gnnops_grid_cap(gnnops_cdiv(E, 256 * 8), atoi(g));
+        const int grid = gnnops_grid_cap(gnnops_cdiv(E, 256 * 8), 256);  // one workgroup per CU: 55 us against 75 us with 1024 or more (tools/time_index_max.py)
         hipLaunchKernelGGL(index_max_kernel, dim3(grid), dim3(256), 0, stream, index, E, d_max);
     }
     return gnnops_check_launch("index_max");

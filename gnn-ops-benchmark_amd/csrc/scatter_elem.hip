@@ -527,9 +527,8 @@ inline LdsGeom lds_geometry(int64_t N, int64_t K, int reduce, bool small_cell = 
         if (tc > 64) tc = 64;
         if (tc >= 4) tc &= ~(int64_t)3;      // whole 8-B / 32-B pieces of a row
         // few destinations: the strips would be wide and few ((1000)^2: 28 workgroups on 256 CUs) — narrow them until there
-        // is about a workgroup per CU (GNNOPS_LDS_NARROW=0 keeps the wide strips, for A/B runs)
-        static const bool narrow = !(getenv("GNNOPS_LDS_NARROW") && getenv("GNNOPS_LDS_NARROW")[0] == '0');
-        while (narrow && tc >= 8 && B * gnnops_cdiv(K, tc) < 192) tc = (tc >> 1) & ~(int64_t)3;
+        // is about a workgroup per CU
+        while (tc >= 8 && B * gnnops_cdiv(K, tc) < 192) tc = (tc >> 1) & ~(int64_t)3;
         if (tc >= 2 || K < 2) return LdsGeom{(int)tc, N, 1};
     }
     const int64_t tc = K < 4 ? K : 4;

@@ -1,5 +1,5 @@
-"""gnnops_edge_reduce on one graph of BASELINE config 2's size (N = 10M, E = 50M, uniform endpoints): lane width sweep
-(GNNOPS_EDGE_VEC = elements per lane; fewer = more lanes per row, down to one row per wave)."""
+"""gnnops_edge_reduce on one graph of BASELINE config 2's size (N = 10M, E = 50M, uniform endpoints): ms per call and
+algorithmic bandwidth of each message functor."""
 import os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [os.path.join(ROOT, "gnn-ops-benchmark_amd")]
@@ -42,11 +42,7 @@ for dt, name in ((torch.float16, "fp16"), (torch.float32, "fp32")):
                       lambda pq=pq, d2=d2: conv.edge_reduce("add", pq[:, d2:2 * d2], ei, n, p=pq[:, :d2], aggr=aggr, scalers=scal, avg_deg={"log": 1.7, "lin": 5.0}),
                       (e * (d2 * es + 8) + n * (d2 * es + 12 * d2 * es) + 4 * (n + 1)) / 1e9))
     for label, fn, gb in cases:
-        for v in ("", "8", "4", "2", "1"):
-            os.environ.pop("GNNOPS_EDGE_VEC", None)
-            if v:
-                os.environ["GNNOPS_EDGE_VEC"] = v
-            ms = timed(fn)
-            print(f"{label:52s} lane width {v or 'policy':>6s}: {ms:8.3f} ms  {gb / ms * 1e3:7.1f} GB/s alg  ({gb / ms * 1e3 / 80:4.1f} % of 8 TB/s)", flush=True)
+        ms = timed(fn)
+        print(f"{label:52s} {ms:8.3f} ms  {gb / ms * 1e3:7.1f} GB/s alg  ({gb / ms * 1e3 / 80:4.1f} % of 8 TB/s)", flush=True)
     cases = []
     del pq, x

@@ -1,5 +1,5 @@
-"""Time gnnops.addmm at a few square sizes: 16-bit operands with the LDS-DMA fast path on and off (A/B in one process,
-interleaved), then fp32. Prints ms, TFLOP/s and the largest difference from torch.addmm."""
+"""Time gnnops.addmm at a few square sizes: 16-bit operands, then fp32. Prints ms, TFLOP/s and the largest difference
+from torch.addmm."""
 import os
 import sys
 
@@ -32,11 +32,8 @@ sizes = [int(a) for a in sys.argv[1:]] or [1581, 4096, 8164, 8192]
 for dt in (torch.bfloat16, torch.float16):
     for L in sizes:
         a, b, c = operands(L, dt)
-        for no_dma in ("0", "3", "1", "0"):
-            os.environ["GNNOPS_GEMM_NO_DMA"] = no_dma
-            ms, err = timed(a, b, c, 10)
-            print(f"{str(dt):16s} no_dma={no_dma} L={L:6d} {ms:8.3f} ms  {2 * L ** 3 / ms / 1e9:8.1f} TFLOP/s  maxdiff_vs_torch={err:.4f}", flush=True)
-os.environ["GNNOPS_GEMM_NO_DMA"] = "0"
+        ms, err = timed(a, b, c, 10)
+        print(f"{str(dt):16s} L={L:6d} {ms:8.3f} ms  {2 * L ** 3 / ms / 1e9:8.1f} TFLOP/s  maxdiff_vs_torch={err:.4f}", flush=True)
 for L in (4096, 8192):
     a, b, c = operands(L, torch.float32)
     ms, err = timed(a, b, c, 5)

@@ -1,5 +1,4 @@
-"""Layout-F scatter (the reference's (L, L) full-shape index) at mid sizes: wide vs narrowed LDS strips (separate processes:
-GNNOPS_LDS_NARROW is read once)."""
+"""Layout-F scatter (the reference's (L, L) full-shape index) at mid sizes: us per call of sum and min along dims 0 and 1."""
 import os
 import sys
 

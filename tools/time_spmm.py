@@ -1,5 +1,4 @@
-"""Config 3 SpMM (CSR 2M x 2M, nnz 40M, D=256 bf16): time spmm_rows_kernel with the dense operand swept in column slices
-(GNNOPS_SPMM_GSHIFT: lanes per row = 2^g, slice = 2^g * 16 B of every 512-B row), nontemporal vs cached gathers.
+"""Config 3 SpMM (CSR 2M x 2M, nnz 40M, D = 256 and 128 bf16): time spmm_rows_kernel and the bandwidth of its gathers.
 usage (GPU box): python tools/time_spmm.py"""
 import os
 import sys
@@ -35,19 +34,8 @@ def main():
     val = torch.rand(nnz, generator=g, device=dev).to(torch.bfloat16)
     for D in (256, 128):
         Bm = torch.rand(M, D, generator=g, device=dev).to(torch.bfloat16)
-        ref = None
-        for gs in ("", "4", "3", "2", "1"):
-            if gs:
-                os.environ["GNNOPS_SPMM_GSHIFT"] = gs
-            else:
-                os.environ.pop("GNNOPS_SPMM_GSHIFT", None)
-            out = gnnops.spmm_csr(rowptr, col, val, Bm)
-            if ref is None:
-                ref = out
-            same = bool(torch.equal(out, ref))
-            ms = ev_ms(lambda: gnnops.spmm_csr(rowptr, col, val, Bm))
-            print(f"D={D} gshift={gs or 'auto'}: {ms:.3f} ms  gathered {nnz * D * 2 / ms / 1e6:.0f} GB/s  identical={same}", flush=True)
-        os.environ.pop("GNNOPS_SPMM_GSHIFT", None)
+        ms = ev_ms(lambda: gnnops.spmm_csr(rowptr, col, val, Bm))
+        print(f"D={D}: {ms:.3f} ms  gathered {nnz * D * 2 / ms / 1e6:.0f} GB/s", flush=True)
         del Bm
 
 
