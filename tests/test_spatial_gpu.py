@@ -3,9 +3,12 @@ spline_basis / spline_weighting / spline_conv and torch_cluster's grid_cluster /
 / random_walk, through the import seams (`from torch_spline_conv import ...`, `from torch_cluster import ...`).
 
 PARITY UNPINNED (oracle/spatial_oracle.py header): neither package nor any output of it is in the reference tree; the oracle
-restates the published definitions. Bars: integer outputs (weight_index, cluster ids, neighbour lists, sampled indices) exact
-— inputs are drawn so that no two candidate distances tie within fp32 rounding, except where a test builds exact ties on
-purpose to pin the smaller-index rule; floating outputs within 1e-5 (fp32) / 4e-3 (fp16) of the value scale.
+restates the published definitions. Bars: integer outputs (weight_index, cluster ids, neighbour lists, sampled indices) exact;
+floating outputs within 1e-5 (fp32) / 4e-3 (fp16) of the value scale. knn / radius / nearest / fps are checked against the
+oracle's float32 forms, which round exactly as the kernels do, so the neighbour lists must be EQUAL even on clouds built to
+tie (lattices, duplicated points, far from the origin) — except cosine knn, whose sqrt / division rounding is not pinned:
+there the answer must be a valid one (_assert_cosine_valid). Every fast path (grid, one-pass best-64, register fps) is
+compared both with its sibling kernel and with the oracle.
 """
 import numpy as np
 import pytest
@@ -23,6 +26,45 @@ def ora():
 
 def _f64(t):
     return t.detach().float().cpu().numpy().astype(np.float64)
+
+
+def _np(t):
+    return t.cpu().numpy()
+
+
+def _assert_oracle(got, want, what=""):
+    got = _np(got)
+    assert got.shape == want.shape and np.array_equal(got, want), (what, got.shape, want.shape,
+                                                                    None if got.shape != want.shape else np.argwhere(got != want)[:5])
+
+
+def _dyadic(g, n, D, sites=4096, step=8):
+    """n points on a lattice of multiples of 1 / step with about `sites` sites: every distance exact, ties everywhere."""
+    m = max(2, int(round(sites ** (1.0 / D))))
+    return torch.randint(0, m, (n, D), generator=g).float() / step
+
+
+def _assert_cosine_valid(got, ora, x, y, k, bx, by):
+    """cosine knn: a valid answer rather than the bit-exact one (sqrt / division rounding is not pinned). Per query: the oracle's
+    number of pairs, no duplicates, every chosen fp64 distance <= the oracle's k-th + 1e-6, and every oracle pair more than 1e-5
+    inside the k-th distance chosen too."""
+    want = ora.knn(x, y, k, bx, by, cosine=True)
+    got = _np(got)
+    xs, ys = ora._points32(x).astype(np.float64), ora._points32(y).astype(np.float64)
+
+    def d64(pairs):
+        a, b = xs[pairs[1]], ys[pairs[0]]
+        return 1 - (a * b).sum(1) / (np.linalg.norm(a, axis=1) * np.linalg.norm(b, axis=1))
+
+    assert np.array_equal(np.bincount(got[0], minlength=len(ys)), np.bincount(want[0], minlength=len(ys)))
+    assert len({(int(a), int(b)) for a, b in got.T}) == got.shape[1], "a neighbour listed twice"
+    dg, dw = d64(got), d64(want)
+    kth = np.full(len(ys), -np.inf)
+    np.maximum.at(kth, want[0], dw)
+    assert bool((dg <= kth[got[0]] + 1e-6).all()), "a chosen neighbour beyond the k-th distance"
+    inside = want[:, dw < kth[want[0]] - 1e-5]
+    chosen = {(int(a), int(b)) for a, b in got.T}
+    assert all((int(a), int(b)) in chosen for a, b in inside.T), "a clearly nearer neighbour missed"
 
 
 def _close(got, want, tol, what):
@@ -125,22 +167,34 @@ def test_fps(ora, batches):
 
 @pytest.mark.parametrize("dt", [torch.float32, torch.float16])
 @pytest.mark.parametrize("D", [1, 2, 3, 5])
-def test_fps_clouds_kept_in_registers(dt, D, monkeypatch):
+def test_fps_clouds_kept_in_registers(ora, dt, D, monkeypatch):
     """Clouds of at most 8192 points in <= 3 dimensions keep their points and running distances in registers (csrc/cluster.hip
-    fps_kernel); GNNOPS_FPS_REGISTERS=0 forces the general loop. The same samples in the same order: ragged clouds (1, 2, 63,
-    1025, 8192 and 8193 points — the last takes the general loop either way), duplicated points (ties to the smaller
-    index), D = 5 (general loop)."""
+    fps_kernel); GNNOPS_FPS_REGISTERS=0 forces the general loop. The same samples in the same order, and the oracle's: ragged
+    clouds (1, 2, 63, 1025, 8192 and 8193 points — the last takes the general loop either way), duplicated points (ties to the
+    smaller index; at ratio 1.0 every point is sampled and then the zero distances tie), D = 5 (general loop), ratio 0.3 (ceil
+    rounds the one-point cloud up to one sample) and 1.0; random_start pinned through its first samples."""
     from torch_cluster import fps
 
     g = torch.Generator().manual_seed(17 + D)
     sizes = [1, 2, 63, 1025, 8192, 8193, 700]
     x = torch.cat([torch.rand(n, D, generator=g) for n in sizes]).to(dt)
     x[70:100] = x[66:67]                         # a run of equal points inside the 1025-point cloud
+    x[9400:9500] = x[9300:9400]                  # and inside the 8192-point one
     batch = torch.cat([torch.full((n,), b) for b, n in enumerate(sizes)])
-    got = fps(x.cuda(), batch.cuda(), ratio=0.3, random_start=False)
-    monkeypatch.setenv("GNNOPS_FPS_REGISTERS", "0")
-    ref = fps(x.cuda(), batch.cuda(), ratio=0.3, random_start=False)
-    assert torch.equal(got, ref)
+    ptr = np.concatenate([[0], np.cumsum(sizes)])
+    for ratio in (0.3, 1.0):
+        monkeypatch.delenv("GNNOPS_FPS_REGISTERS", raising=False)
+        got = fps(x.cuda(), batch.cuda(), ratio=ratio, random_start=False)
+        rnd = fps(x.cuda(), batch.cuda(), ratio=ratio, random_start=True) if ratio < 1 else None
+        monkeypatch.setenv("GNNOPS_FPS_REGISTERS", "0")
+        ref = fps(x.cuda(), batch.cuda(), ratio=ratio, random_start=False)
+        assert torch.equal(got, ref)
+        _assert_oracle(got, ora.fps(x, batch.numpy(), ratio, ptr[:-1]), f"fps ratio {ratio}")
+        if rnd is not None:                      # the first sample of every batch is the random start; the rest follows from it
+            per = np.ceil(np.array(sizes) * ratio).astype(np.int64)
+            start = _np(rnd)[np.concatenate([[0], np.cumsum(per)[:-1]])]
+            assert bool(((start >= ptr[:-1]) & (start < ptr[1:])).all())
+            _assert_oracle(rnd, ora.fps(x, batch.numpy(), ratio, start), "fps random_start")
 
 
 @pytest.mark.parametrize("batches,cosine", [(1, False), (4, False), (3, True)])
@@ -173,13 +227,13 @@ def test_knn_fewer_candidates_than_k_and_exact_ties():
     assert got.cpu().tolist() == [[0, 0, 1], [0, 1, 3]]
 
 
-@pytest.mark.parametrize("k", [1, 16, 64, 70])
+@pytest.mark.parametrize("k", [1, 16, 33, 63, 64, 65, 70])
 @pytest.mark.parametrize("cosine", [False, True])
-def test_knn_one_pass_equals_k_rounds(k, cosine, monkeypatch):
+def test_knn_one_pass_equals_k_rounds(ora, k, cosine, monkeypatch):
     """k <= 64 takes the one-pass kernel (the wave keeps its best 64 keys sorted across lanes; csrc/cluster.hip knn_topk_kernel),
     larger k the k-round kernel; GNNOPS_KNN_ROUNDS=1 forces the latter. Same pairs in the same order on a cloud with many
     exact ties (points on a coarse lattice, duplicated points), ragged batches, a batch with fewer than k points, and a point
-    whose coordinates are NaN (never a neighbour)."""
+    whose coordinates are NaN (never a neighbour). Both equal the oracle (cosine: a valid answer)."""
     from torch_cluster import knn
 
     g = torch.Generator().manual_seed(40 + k)
@@ -197,16 +251,54 @@ def test_knn_one_pass_equals_k_rounds(k, cosine, monkeypatch):
     assert not bool((got[1] == 777).any())
     per_query = torch.bincount(got[0].cpu(), minlength=700)
     assert int(per_query[by == 3].max()) == min(k, 9)
+    if cosine:
+        _assert_cosine_valid(got, ora, x, y, k, bx.numpy(), by.numpy())
+    else:
+        _assert_oracle(got, ora.knn(x, y, k, bx.numpy(), by.numpy()), "knn")
+
+
+@pytest.mark.parametrize("dt", [torch.float32, torch.float16, torch.bfloat16])
+@pytest.mark.parametrize("D", [1, 5])
+@pytest.mark.parametrize("k", [1, 33, 64, 65])
+def test_knn_exhaustive_dtypes_and_widths_against_the_oracle(ora, dt, D, k, monkeypatch):
+    """The exhaustive kernels (one-pass for k <= 64, k-round above) in fp32 / fp16 / bf16 and D = 1 and 5 (D = 3 fp32 is the test
+    above), on a dyadic lattice (multiples of 1/8, queries half a step off in some rows: every distance exact in every dtype,
+    ties everywhere): ragged batches, a batch of nine points (fewer than k), a NaN point. The oracle's pairs exactly; cosine
+    a valid answer; both kernels the same pairs."""
+    from torch_cluster import knn
+
+    g = torch.Generator().manual_seed(300 + 10 * D + k)
+    x = _dyadic(g, 3000, D, sites=128)                      # coordinates <= 127 / 8: exact in bf16's 8 significant bits
+    x[100:130] = x[40:70]
+    x[555] = float("nan")
+    bx = torch.sort(torch.randint(0, 3, (3000,), generator=g)).values
+    bx[-9:] = 3
+    y = _dyadic(g, 400, D, sites=128) + (torch.rand(400, 1, generator=g) < 0.5).float() / 16
+    by = torch.sort(torch.randint(0, 4, (400,), generator=g)).values
+    for t in (x, y):                                          # the lattice is exact in the dtype
+        assert torch.equal(t.to(dt).float().nan_to_num(-1), t.nan_to_num(-1))
+    x, y = x.to(dt), y.to(dt)
+    for cosine in (False, True):
+        got = knn(x.cuda(), y.cuda(), k, bx.cuda(), by.cuda(), cosine=cosine)
+        monkeypatch.setenv("GNNOPS_KNN_ROUNDS", "1")
+        assert torch.equal(got, knn(x.cuda(), y.cuda(), k, bx.cuda(), by.cuda(), cosine=cosine))
+        monkeypatch.delenv("GNNOPS_KNN_ROUNDS")
+        if cosine:
+            _assert_cosine_valid(got, ora, x, y, k, bx.numpy(), by.numpy())
+        else:
+            _assert_oracle(got, ora.knn(x, y, k, bx.numpy(), by.numpy()), f"knn {dt} D={D}")
+            assert not bool((got[1] == 555).any())
 
 
 @pytest.mark.parametrize("D", [1, 2, 3])
-@pytest.mark.parametrize("k", [1, 9, 64])
-def test_knn_through_the_grid_equals_the_exhaustive_kernel(D, k, monkeypatch):
+@pytest.mark.parametrize("k", [1, 9, 33, 64])
+def test_knn_through_the_grid_equals_the_exhaustive_kernel(ora, D, k, monkeypatch):
     """One cloud of >= 8192 fp32 points in <= 3 dimensions is searched through a uniform grid (gnnops_knn_grid_cells -> plan ->
     gnnops_knn_grid_query): the same pairs in the same order as the exhaustive kernel, on clouds made to hurt — a dense clump
     beside empty space (many empty cells, long walks), a coarse lattice (exact ties across cell faces), duplicated points,
-    a flat axis, NaN and infinite coordinates among x, queries outside the box / NaN, fewer finite candidates than k never
-    (that needs a tiny cloud: covered by the exhaustive tests)."""
+    a dyadic lattice (multiples of 1/8: ties exact in any arithmetic, on cell faces), a flat axis, NaN and infinite coordinates
+    among x, queries outside the box / NaN (no pairs), fewer finite candidates than k never (that needs a tiny cloud: covered by
+    the exhaustive tests). Both equal the oracle, here and on the copy far from the origin and the flat cloud."""
     from torch_cluster import knn
     from gnnops import spatial
 
@@ -218,10 +310,13 @@ def test_knn_through_the_grid_equals_the_exhaustive_kernel(D, k, monkeypatch):
     x[9000:9100] = x[8900:9000]                             # duplicates
     if D == 3:
         x[9100:12000, 2] = 0.5                              # a slab
+    x[12000:14000] = torch.randint(0, 9, (2000, D), generator=g).float() / 8     # dyadic lattice
     x[123] = float("nan")
     x[456, 0] = float("inf")
     y = torch.rand(900, D, generator=g) * 1.6 - 0.3         # a third of the queries outside the box
     y[:200] = x[6000:6200]                                  # queries ON lattice points
+    y[200:260] = x[12000:12060]                             # ... on dyadic ones
+    y[260:300] = x[12000:12040] + 1 / 16                    # ... half a step off them
     y[5] = float("nan")
     calls = []
     real = spatial._knn_grid
@@ -232,24 +327,28 @@ def test_knn_through_the_grid_equals_the_exhaustive_kernel(D, k, monkeypatch):
     ref = knn(x.cuda(), y.cuda(), k)
     assert calls == [1]
     assert torch.equal(got, ref)
-    assert not bool((got[1] == 123).any())
+    assert not bool((got[1] == 123).any()) and not bool((got[0] == 5).any())
+    _assert_oracle(got, ora.knn(x, y, k), "grid knn")
     # the same cloud far from the origin (coordinates around 3000: an ulp is a sizeable part of a cell) and queries far outside
     xo, yo = x + 3000.0, torch.cat([y[:300] + 3000.0, y[300:600] * 500.0 - 7000.0])
     monkeypatch.setattr(spatial, "_KNN_GRID_MIN_POINTS", 8192)
     got_o = knn(xo.cuda(), yo.cuda(), k)
     monkeypatch.setattr(spatial, "_KNN_GRID_MIN_POINTS", 1 << 40)
     assert torch.equal(got_o, knn(xo.cuda(), yo.cuda(), k))
+    _assert_oracle(got_o, ora.knn(xo, yo, k), "grid knn far from the origin")
     # a flat cloud (every point the same): one cell, every query walks it
     flat = torch.full((9000, D), 0.25)
     assert torch.equal(knn(flat.cuda(), y[:50].cuda(), k), knn(flat[:9000].cuda(), y[:50].cuda(), k))
     monkeypatch.setattr(spatial, "_KNN_GRID_MIN_POINTS", 8192)
     got_flat = knn(flat.cuda(), y[10:50].cuda(), k)
     assert got_flat[1].view(40, k).cpu().tolist() == [list(range(k))] * 40
+    _assert_oracle(got_flat, ora.knn(flat, y[10:50], k), "grid knn flat")
 
 
-def test_knn_and_radius_grid_per_cloud_under_a_batch_vector(monkeypatch):
+def test_knn_and_radius_grid_per_cloud_under_a_batch_vector(ora, monkeypatch):
     """A batch vector over a few clouds of which some are large: the large ones walk a grid of their own, the small ones (and an
-    empty one) the exhaustive kernel, cloud by cloud; the pairs are those of the single exhaustive call over all of them."""
+    empty one) the exhaustive kernel, cloud by cloud; the pairs are those of the single exhaustive call over all of them, and
+    the oracle's."""
     from torch_cluster import knn, radius
     from gnnops import spatial
 
@@ -266,6 +365,8 @@ def test_knn_and_radius_grid_per_cloud_under_a_batch_vector(monkeypatch):
     got_k = knn(x.cuda(), y.cuda(), 12, bx.cuda(), by.cuda())
     got_r = radius(x.cuda(), y.cuda(), 0.15, bx.cuda(), by.cuda(), max_num_neighbors=20)
     assert calls == [9000, 12000, 9000, 12000]
+    _assert_oracle(got_k, ora.knn(x, y, 12, bx.numpy(), by.numpy()), "per-cloud knn")
+    _assert_oracle(got_r, ora.radius(x, y, 0.15, bx.numpy(), by.numpy(), 20), "per-cloud radius")
     monkeypatch.setattr(spatial, "_KNN_GRID_MIN_POINTS", 1 << 40)
     assert torch.equal(got_k, knn(x.cuda(), y.cuda(), 12, bx.cuda(), by.cuda()))
     assert torch.equal(got_r, radius(x.cuda(), y.cuda(), 0.15, bx.cuda(), by.cuda(), max_num_neighbors=20))
@@ -273,11 +374,11 @@ def test_knn_and_radius_grid_per_cloud_under_a_batch_vector(monkeypatch):
 
 
 @pytest.mark.parametrize("D", [1, 2, 3])
-@pytest.mark.parametrize("r,cap", [(0.03, 32), (0.11, 64), (0.5, 7), (0.0, 4)])
-def test_radius_through_the_grid_equals_the_exhaustive_kernel(D, r, cap, monkeypatch):
+@pytest.mark.parametrize("r,cap", [(0.03, 32), (0.11, 64), (0.5, 7), (0.0, 4), (0.07, 1)])
+def test_radius_through_the_grid_equals_the_exhaustive_kernel(ora, D, r, cap, monkeypatch):
     """torch_cluster.radius on one cloud of >= 8192 fp32 points walks the same grid: the `cap` smallest indices inside the ball,
-    ascending — the exhaustive kernel's answer — for balls smaller than a cell, spanning many cells, covering half the cloud,
-    and empty (r = 0: the comparison is strict)."""
+    ascending — the exhaustive kernel's answer and the oracle's — for balls smaller than a cell, spanning many cells, covering
+    half the cloud, and empty (r = 0: the comparison is strict); and on the copy far from the origin."""
     from torch_cluster import radius
     from gnnops import spatial
 
@@ -299,6 +400,70 @@ def test_radius_through_the_grid_equals_the_exhaustive_kernel(D, r, cap, monkeyp
     assert calls == [1] and torch.equal(got, ref)
     if r == 0.0:
         assert got.numel() == 0
+    _assert_oracle(got, ora.radius(x, y, r, None, None, cap), "grid radius")
+    xo, yo = x + 3000.0, y + 3000.0                             # an ulp is ~2e-4 here: distances round coarsely
+    monkeypatch.setattr(spatial, "_KNN_GRID_MIN_POINTS", 8192)
+    got_o = radius(xo.cuda(), yo.cuda(), r, max_num_neighbors=cap)
+    assert calls == [1, 1]
+    monkeypatch.setattr(spatial, "_KNN_GRID_MIN_POINTS", 1 << 40)
+    assert torch.equal(got_o, radius(xo.cuda(), yo.cuda(), r, max_num_neighbors=cap))
+    _assert_oracle(got_o, ora.radius(xo, yo, r, None, None, cap), "grid radius far from the origin")
+
+
+@pytest.mark.parametrize("D", [1, 2, 3])
+@pytest.mark.parametrize("cap", [1, 7, 32, 64])
+def test_radius_grid_at_exactly_r_on_a_dyadic_lattice(ora, D, cap, monkeypatch):
+    """Points exactly r = 1/8 away on a lattice of spacing 1/8 are outside the ball (d < r^2 is strict, and every distance is
+    exact); one fp32 ulp more and they are inside. The grid walk, the exhaustive kernel and the oracle agree, cap by cap."""
+    from torch_cluster import radius
+    from gnnops import spatial
+
+    g = torch.Generator().manual_seed(80 + D + cap)
+    x = _dyadic(g, 9000, D)
+    y = torch.cat([x[:300], x[300:400] + 1 / 16])
+    up = float(np.nextafter(np.float32(0.125), np.float32(1)))
+    for r in (0.125, up):
+        got = radius(x.cuda(), y.cuda(), r, max_num_neighbors=cap)
+        monkeypatch.setattr(spatial, "_KNN_GRID_MIN_POINTS", 1 << 40)
+        assert torch.equal(got, radius(x.cuda(), y.cuda(), r, max_num_neighbors=cap))
+        monkeypatch.setattr(spatial, "_KNN_GRID_MIN_POINTS", 8192)
+        want = ora.radius(x, y, r, None, None, cap)
+        _assert_oracle(got, want, f"radius {r}")
+        on = got[:, got[0] < 300].cpu()                         # the queries ON lattice sites
+        d = ((x[on[1]] - y[on[0]]) ** 2).sum(1)
+        if r == 0.125:                                          # only the query's own site (and the points on it) is inside
+            assert bool((d == 0).all())
+        else:                                                   # the sites 1/8 away are in too
+            assert bool((d == 1 / 64).any())
+
+
+@pytest.mark.parametrize("D", [2, 3])
+def test_knn_graph_and_radius_graph_through_the_grid(ora, D, monkeypatch):
+    """knn_graph / radius_graph on one cloud of >= 8192 points take the grid (k + 1 / cap + 1 neighbours, self loops dropped):
+    the oracle's edges, on a cloud with a run of 100 identical points — there a point's own index need not be among its k + 1
+    nearest (its twins of smaller index come first), and then it keeps k + 1 edges."""
+    from torch_cluster import knn_graph, radius_graph
+    from gnnops import spatial
+
+    g = torch.Generator().manual_seed(95 + D)
+    x = torch.rand(8300, D, generator=g)
+    x[1000:1100] = x[999]
+    x[2000:3000] = _dyadic(g, 1000, D) / 8
+    calls = []
+    real = spatial._knn_grid
+    monkeypatch.setattr(spatial, "_knn_grid", lambda *a, **kw: (calls.append(1), real(*a, **kw))[1])
+    k, r, cap = 8, 0.04, 24
+    got_k = knn_graph(x.cuda(), k)
+    got_r = radius_graph(x.cuda(), r, max_num_neighbors=cap)
+    assert calls == [1, 1]
+    w = ora.knn(x, x, k + 1)
+    w = np.stack([w[1], w[0]])[:, w[0] != w[1]]         # flow source_to_target: (neighbour, point), self loops dropped
+    _assert_oracle(got_k, w, "knn_graph")
+    counts = np.bincount(w[1], minlength=len(x))
+    assert (counts == k + 1).any() and (counts >= k).all()   # the twins: some points keep k + 1 edges
+    w = ora.radius(x, x, r, None, None, cap + 1)
+    w = np.stack([w[1], w[0]])[:, w[0] != w[1]]
+    _assert_oracle(got_r, w, "radius_graph")
 
 
 @pytest.mark.parametrize("batches", [1, 4])
