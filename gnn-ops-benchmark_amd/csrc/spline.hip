@@ -21,52 +21,9 @@
 // of weight matrices, there is no shared operand tile to put on the matrix cores without first sorting E * S products by
 // kernel index.
 #include "common.h"
+#include "spline_common.h"
 
 namespace {
-
-constexpr int MAX_DIM = 8;
-constexpr int MAX_S = 64;
-
-struct SplineMeta {
-    int D, degree, S;
-    int64_t kernel_size[MAX_DIM];
-    int is_open[MAX_DIM];
-};
-
-template <int M>
-__device__ inline float bspline(float v, int k) {
-    if constexpr (M == 1) {
-        return k == 0 ? 1.f - v : v;
-    } else if constexpr (M == 2) {
-        if (k == 0) return 0.5f * v * v - v + 0.5f;
-        if (k == 1) return -v * v + v + 0.5f;
-        return 0.5f * v * v;
-    } else {
-        if (k == 0) return (1.f - v) * (1.f - v) * (1.f - v) / 6.f;
-        if (k == 1) return (3.f * v * v * v - 6.f * v * v + 4.f) / 6.f;
-        if (k == 2) return (-3.f * v * v * v + 3.f * v * v + 3.f * v + 1.f) / 6.f;
-        return v * v * v / 6.f;
-    }
-}
-
-// basis value and weight index of combination s for one edge's pseudo-coordinates (fp32 arithmetic for every storage type)
-template <typename T, int M>
-__device__ inline void basis_of(const T* __restrict__ pseudo_e, const SplineMeta& sm, int s, float& b, int64_t& wi) {
-    int k = s;
-    int64_t off = 1;
-    wi = 0;
-    b = 1.f;
-    for (int d = 0; d < sm.D; ++d) {
-        const int k_mod = k % (M + 1);
-        k /= (M + 1);
-        float v = Elem<T>::load(pseudo_e + d) * (float)(sm.kernel_size[d] - M * sm.is_open[d]);
-        const float fl = floorf(v);
-        wi += (((int64_t)fl + k_mod) % sm.kernel_size[d]) * off;
-        off *= sm.kernel_size[d];
-        v -= fl;
-        b *= bspline<M>(v, k_mod);
-    }
-}
 
 template <typename T, int M>
 __global__ __launch_bounds__(256) void spline_basis_kernel(const T* __restrict__ pseudo, SplineMeta sm, int64_t E,
@@ -146,25 +103,6 @@ __global__ __launch_bounds__(256) void spline_conv_kernel(const T* __restrict__ 
         if (bias && o < Mout) acc += Elem<T>::load(bias + o);
         if (o < Mout) Elem<T>::store(out + n * Mout + o, acc);
     }
-}
-
-int fill_meta(SplineMeta& sm, const int64_t* kernel_size, const uint8_t* is_open_spline, int D, int degree, const char* what) {
-    GNNOPS_REQUIRE(D >= 1 && D <= MAX_DIM, GNNOPS_EUNSUPPORTED, "%s: 1..%d pseudo-coordinate dimensions", what, MAX_DIM);
-    GNNOPS_REQUIRE(degree >= 1 && degree <= 3, GNNOPS_EUNSUPPORTED, "%s: B-spline degree must be 1, 2 or 3", what);
-    GNNOPS_REQUIRE(kernel_size && is_open_spline, GNNOPS_EINVAL, "%s: null kernel_size / is_open_spline", what);
-    sm.D = D;
-    sm.degree = degree;
-    int64_t S = 1;
-    for (int d = 0; d < D; ++d) {
-        S *= degree + 1;
-        GNNOPS_REQUIRE(kernel_size[d] >= 1, GNNOPS_EINVAL, "%s: kernel_size must be positive", what);
-        sm.kernel_size[d] = kernel_size[d];
-        sm.is_open[d] = is_open_spline[d] ? 1 : 0;
-    }
-    GNNOPS_REQUIRE(S <= MAX_S, GNNOPS_EUNSUPPORTED, "%s: (degree + 1)^D = %lld basis products per edge, at most %d", what, (long long)S,
-                   MAX_S);
-    sm.S = (int)S;
-    return GNNOPS_OK;
 }
 
 template <typename T>

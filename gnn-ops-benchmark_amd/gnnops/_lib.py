@@ -87,6 +87,10 @@ SIGNATURES = {
     "gnnops_spline_basis": (_ci, [_vp, _vp, _vp, _i64, _ci, _ci, _vp, _vp, _ci, _vp]),
     "gnnops_spline_weighting": (_ci, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _ci, _vp]),
     "gnnops_spline_conv": (_ci, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _ci, _ci, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _ci, _ci, _vp]),
+    "gnnops_spline_basis_bw": (_ci, [_vp, _vp, _vp, _vp, _i64, _ci, _ci, _vp, _ci, _vp]),
+    "gnnops_spline_weighting_bw_basis": (_ci, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _ci, _vp]),
+    "gnnops_spline_weighting_bw_weight_workspace_bytes": (_sz, [_i64, _i64, _i64, _i64]),
+    "gnnops_spline_weighting_bw_weight": (_ci, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _ci, _vp, _sz, _vp]),
     "gnnops_grid_cluster": (_ci, [_vp, _i64, _ci, _vp, _vp, _vp, _vp, _ci, _vp]),
     "gnnops_knn": (_ci, [_vp, _vp, _vp, _vp, _i64, _i64, _ci, _ci, _ci, _vp, _ci, _vp]),
     "gnnops_knn_grid_cells": (_ci, [_vp, _i64, _ci, _ci, _vp, _vp, _vp]),

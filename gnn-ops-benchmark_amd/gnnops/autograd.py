@@ -392,3 +392,130 @@ def addmm(input, mat1, mat2, *, beta=1, alpha=1):
 
 def matmul(input, other):
     return addmm(None, input, other)
+
+
+# ---- torch_spline_conv (gnnops/spatial.py; kernels csrc/spline.hip forward, csrc/spline_bw.hip backward) ----------------
+class _SplineBasis(torch.autograd.Function):
+    """spline_basis, differentiable in pseudo [E, D]: d pseudo[e, d] = sum_s d basis[e, s] * d b[e, s] / d pseudo[e, d]
+    (floor() carries no gradient; weight_index has none)."""
+
+    @staticmethod
+    def forward(ctx, pseudo, kernel_size, is_open_spline, degree):
+        from . import spatial
+
+        basis, wi = spatial._spline_basis_raw(pseudo, kernel_size, is_open_spline, degree)
+        ctx.save_for_backward(pseudo)
+        ctx.meta = (kernel_size, is_open_spline, degree)
+        ctx.mark_non_differentiable(wi)
+        return basis, wi
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_basis, _grad_wi):
+        from . import spatial
+
+        (pseudo,) = ctx.saved_tensors
+        return spatial._spline_basis_bw(grad_basis, pseudo, *ctx.meta), None, None, None
+
+
+class _SplineWeighting(torch.autograd.Function):
+    """spline_weighting, differentiable in x, weight and basis. d x is the forward kernel on the transposed table
+    [K, Mout, Min]; d weight groups the (edge, combination) pairs by kernel index (a plan of weight_index, cached under that
+    tensor) and contracts on the matrix cores; d basis is the bilinear form per pair."""
+
+    @staticmethod
+    def forward(ctx, x, weight, basis, weight_index):
+        from . import spatial
+
+        out = spatial._spline_weighting_raw(x, weight, basis, weight_index)
+        ctx.save_for_backward(x.contiguous(), weight.contiguous(), basis.contiguous(), weight_index.contiguous())
+        ctx.wi_owner = weight_index
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        from . import spatial
+        from .sparse import _transpose_batched
+
+        x, weight, basis, wi = ctx.saved_tensors
+        g = g.contiguous()
+        d_x = d_w = d_b = None
+        if ctx.needs_input_grad[0]:
+            d_x = spatial._spline_weighting_raw(g, _transpose_batched(weight), basis, wi)
+        if ctx.needs_input_grad[1]:
+            K = weight.size(0)
+            plan = ops.get_plan(wi.view(-1), K, owner=ctx.wi_owner) if wi.numel() else None
+            d_w = spatial._spline_bw_weight(g, x, basis, wi, K, plan=plan)
+        if ctx.needs_input_grad[2]:
+            d_b = spatial._spline_bw_basis(g, x, weight, wi)
+        return d_x, d_w, d_b, None
+
+
+class _SplineConv(torch.autograd.Function):
+    """spline_conv: the forward is the fused per-destination kernel, which keeps neither the basis nor the messages. The
+    backward recomputes basis / weight_index (one spline_basis launch), scales G by 1 / degree when ``norm``, and then
+      d weight       pairs grouped by kernel index, MFMA contraction, rows of x / G read through edge_index[1] / edge_index[0]
+      d x            the fused forward kernel over the plan of edge_index[1] with the transposed table, + G @ root_weight^T
+      d pseudo       the bilinear form per (edge, combination), then the backward of spline_basis
+      d root_weight  x^T @ G  (MFMA GEMM)          d bias  column sums of G
+    Not fused: d weight, d x and d pseudo are separate passes over the edges; only the forward is one kernel."""
+
+    @staticmethod
+    def forward(ctx, x, edge_index, pseudo, weight, kernel_size, is_open_spline, degree, norm, root_weight, bias):
+        from . import spatial
+
+        out = spatial._spline_conv_raw(x, edge_index, pseudo, weight, kernel_size, is_open_spline, degree, norm, root_weight, bias)
+        ctx.save_for_backward(x.contiguous(), pseudo.contiguous(), weight.contiguous(), root_weight)
+        ctx.edge_index = edge_index.contiguous() if not edge_index.is_contiguous() else edge_index
+        ctx.meta = (kernel_size, is_open_spline, degree)
+        ctx.norm = norm
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, G):
+        from . import spatial
+        from .sparse import _transpose_batched, transpose_contiguous
+
+        x, pseudo, weight, root = ctx.saved_tensors
+        edge_index = ctx.edge_index
+        need = ctx.needs_input_grad
+        G = G.contiguous()
+        N = x.size(0)
+        row, col = edge_index[0], edge_index[1]
+        d_x = d_p = d_w = d_root = d_bias = None
+        if need[0] or need[2] or need[3]:
+            ghat = G
+            if ctx.norm:
+                rowptr = ops.get_plan(row, N, owner=edge_index, tag=0, companion=col).rowptr
+                ghat = G / (rowptr[1:] - rowptr[:-1]).clamp_(min=1).to(G.dtype).unsqueeze(1)
+            if need[2] or need[3]:
+                basis, wi = spatial._spline_basis_raw(pseudo, *ctx.meta)
+            if need[3]:
+                d_w = spatial._spline_bw_weight(ghat, x, basis, wi, weight.size(0), col, row)
+            if need[2]:
+                d_p = spatial._spline_basis_bw(spatial._spline_bw_basis(ghat, x, weight, wi, col, row), pseudo, *ctx.meta)
+            if need[0]:
+                d_x = spatial._spline_conv_raw(ghat, edge_index, pseudo, _transpose_batched(weight), *ctx.meta, norm=False,
+                                               transposed=True)
+        if root is not None:
+            if need[0]:
+                d_x = d_x + ops.matmul(G, transpose_contiguous(root))
+            if need[8]:
+                d_root = ops.matmul(transpose_contiguous(x), G)
+        if need[9]:
+            d_bias = G.sum(0)
+        return d_x, None, d_p, d_w, None, None, None, None, d_root, d_bias
+
+
+def spline_basis(pseudo, kernel_size, is_open_spline, degree):
+    return _SplineBasis.apply(pseudo, kernel_size, is_open_spline, degree)
+
+
+def spline_weighting(x, weight, basis, weight_index):
+    return _SplineWeighting.apply(x, weight, basis, weight_index)
+
+
+def spline_conv(x, edge_index, pseudo, weight, kernel_size, is_open_spline, degree=1, norm=True, root_weight=None, bias=None):
+    return _SplineConv.apply(x, edge_index, pseudo, weight, kernel_size, is_open_spline, degree, norm, root_weight, bias)

@@ -544,3 +544,54 @@ class PNAConv(_Layer):
             outs.append(o)
         out = outs[0] if T == 1 else torch.cat(outs, dim=1)
         return _linear(out, self.lin, self._cache("lin"))
+
+
+class SplineConv(_Layer):
+    """x'_i = 1/|N(i)| sum_j x_j . h(e_ij) + x_i . root + bias, h = the B-spline kernel over the K = kernel_size^dim table
+    ``weight`` [K, in, out] (SplineCNN, Fey et al. 2018; torch_geometric SplineConv). Not one of the reference's five layers: it is
+    the trainable front end of torch_spline_conv.spline_conv (gnnops/spatial.py) — one fused forward kernel, backward in
+    gnnops.autograd._SplineConv. ``aggr`` "mean" divides by the in-degree (norm=True), "add" does not.
+
+    ``edge_index`` follows PyG's source_to_target flow: row 0 holds the sources, messages are summed at ``edge_index[1]``.
+    spline_conv sums at row 0 of ITS index, so the layer hands it the flipped index; the flipped copy is kept per edge_index
+    object, which keeps the edge plans cached across steps. torch_geometric is not available to compare against: the parameter
+    names ``weight``, ``root``, ``bias`` and the uniform initialisation are this package's choice (name parity unpinned)."""
+
+    def __init__(self, in_channels, out_channels, dim, kernel_size, is_open_spline=True, degree=1, aggr="mean", root_weight=True,
+                 bias=True):
+        super().__init__()
+        if aggr not in ("mean", "add", "sum"):
+            raise ValueError("SplineConv: aggr must be 'mean' or 'add'")
+        as_list = lambda v: [v] * dim if isinstance(v, (int, bool)) else list(v)   # noqa: E731
+        ks, op = as_list(kernel_size), as_list(is_open_spline)
+        if len(ks) != dim or len(op) != dim:
+            raise ValueError("SplineConv: kernel_size and is_open_spline need one entry per dimension")
+        self.in_channels, self.out_channels, self.dim, self.degree, self.aggr = in_channels, out_channels, dim, degree, aggr
+        self.register_buffer("kernel_size", torch.tensor(ks, dtype=torch.int64), persistent=False)
+        self.register_buffer("is_open_spline", torch.tensor([1 if o else 0 for o in op], dtype=torch.uint8), persistent=False)
+        K = 1
+        for k in ks:
+            K *= k
+        bound = 1.0 / float(in_channels * (degree + 1) ** dim) ** 0.5
+        self.weight = torch.nn.Parameter(torch.empty(K, in_channels, out_channels).uniform_(-bound, bound))
+        rb = 1.0 / float(in_channels) ** 0.5
+        self.root = torch.nn.Parameter(torch.empty(in_channels, out_channels).uniform_(-rb, rb)) if root_weight else None
+        self.bias = torch.nn.Parameter(torch.zeros(out_channels)) if bias else None
+        self._flipped = None   # (weakref to edge_index, its version, flipped copy)
+
+    def _flip(self, edge_index):
+        import weakref
+
+        hit = self._flipped
+        if hit is not None and hit[0]() is edge_index and hit[1] == edge_index._version:
+            return hit[2]
+        flipped = edge_index.flip(0).contiguous()
+        if not edge_index.is_inference():
+            self._flipped = (weakref.ref(edge_index), edge_index._version, flipped)
+        return flipped
+
+    def forward(self, x, edge_index, edge_attr):
+        from .spatial import spline_conv
+
+        return spline_conv(x, self._flip(edge_index), edge_attr, self.weight, self.kernel_size, self.is_open_spline, self.degree,
+                           self.aggr == "mean", self.root, self.bias)

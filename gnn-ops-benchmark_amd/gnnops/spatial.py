@@ -1,10 +1,11 @@
 """The remaining ops of the reference's list (ops.txt:17-19, 29-41) behind the packages' own
 signatures: torch_spline_conv.{spline_basis, spline_weighting, spline_conv} and torch_cluster.{grid_cluster, fps, knn,
 knn_graph, radius, radius_graph, nearest, random_walk}. The import seams are the sibling packages ``torch_spline_conv`` and
-``torch_cluster`` in this directory. Kernels: csrc/spline.hip, csrc/cluster.hip. Parity unpinned (neither package nor any
+``torch_cluster`` in this directory. Kernels: csrc/spline.hip, csrc/spline_bw.hip, csrc/cluster.hip. Parity unpinned (neither package nor any
 output of it is in the reference tree): oracle/spatial_oracle.py restates the published definitions.
 
-Forward only. Device tensors only — CPU tensors are refused, not emulated."""
+The spline ops are differentiable (autograd.Functions in gnnops/autograd.py over the kernels of csrc/spline_bw.hip; first
+derivatives only); the torch_cluster ops are forward only. Device tensors only — CPU tensors are refused, not emulated."""
 import weakref
 
 import torch
@@ -37,8 +38,21 @@ def _host(t, dtype):
     return host
 
 
+def _needs_grad(*tensors):
+    return torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in tensors)
+
+
 def spline_basis(pseudo, kernel_size, is_open_spline, degree):
-    """torch_spline_conv.spline_basis (torch.ops.torch_spline_conv.spline_basis, ops.txt:19): (basis [E, S], weight_index [E, S])."""
+    """torch_spline_conv.spline_basis (torch.ops.torch_spline_conv.spline_basis, ops.txt:19): (basis [E, S], weight_index [E, S]).
+    Differentiable in pseudo (gnnops/autograd.py; floor() carries no gradient, weight_index has none)."""
+    if _needs_grad(pseudo):
+        from . import autograd
+
+        return autograd.spline_basis(pseudo.unsqueeze(-1) if pseudo.dim() == 1 else pseudo, kernel_size, is_open_spline, degree)
+    return _spline_basis_raw(pseudo, kernel_size, is_open_spline, degree)
+
+
+def _spline_basis_raw(pseudo, kernel_size, is_open_spline, degree):
     _require_gpu(pseudo)
     ops._refuse_grad("spline_basis", pseudo)
     if pseudo.dim() == 1:
@@ -59,7 +73,16 @@ def spline_basis(pseudo, kernel_size, is_open_spline, degree):
 
 
 def spline_weighting(x, weight, basis, weight_index):
-    """torch_spline_conv.spline_weighting (ops.txt:18): x [E, Min], weight [K, Min, Mout] -> [E, Mout]."""
+    """torch_spline_conv.spline_weighting (ops.txt:18): x [E, Min], weight [K, Min, Mout] -> [E, Mout].
+    Differentiable in x, weight and basis."""
+    if _needs_grad(x, weight, basis):
+        from . import autograd
+
+        return autograd.spline_weighting(x, weight, basis, weight_index)
+    return _spline_weighting_raw(x, weight, basis, weight_index)
+
+
+def _spline_weighting_raw(x, weight, basis, weight_index):
     _require_gpu(x, weight, basis, weight_index)
     ops._refuse_grad("spline_weighting", x, weight, basis)
     if x.dim() != 2 or weight.dim() != 3 or weight.size(1) != x.size(1) or basis.shape != weight_index.shape or basis.size(0) != x.size(0):
@@ -80,7 +103,21 @@ def spline_weighting(x, weight, basis, weight_index):
 def spline_conv(x, edge_index, pseudo, weight, kernel_size, is_open_spline, degree=1, norm=True, root_weight=None, bias=None):
     """torch_spline_conv.spline_conv (ops.txt:31): messages x[edge_index[1]] blended through the B-spline kernel, summed at
     edge_index[0] (divided by that row's degree when ``norm``), + x @ root_weight + bias. One pass over the plan of
-    edge_index[0]; neither the basis tensors nor the [E, Mout] messages are materialised."""
+    edge_index[0]; neither the basis tensors nor the [E, Mout] messages are materialised.
+    Differentiable in x, pseudo, weight, root_weight and bias (gnnops/autograd.py _SplineConv)."""
+    if _needs_grad(x, pseudo, weight, root_weight, bias):
+        from . import autograd
+
+        return autograd.spline_conv(x.unsqueeze(-1) if x.dim() == 1 else x, edge_index,
+                                    pseudo.unsqueeze(-1) if pseudo.dim() == 1 else pseudo, weight, kernel_size, is_open_spline,
+                                    degree, norm, root_weight, bias)
+    return _spline_conv_raw(x, edge_index, pseudo, weight, kernel_size, is_open_spline, degree, norm, root_weight, bias)
+
+
+def _spline_conv_raw(x, edge_index, pseudo, weight, kernel_size, is_open_spline, degree=1, norm=True, root_weight=None, bias=None,
+                     transposed=False):
+    """``transposed``: sum at edge_index[1] what travels from edge_index[0] (the plan of the OTHER row of the same tensor):
+    with x := d out and weight := the [K, Mout, Min] transposed table this is d x of the layer."""
     _require_gpu(x, edge_index, pseudo, weight, root_weight, bias)
     ops._refuse_grad("spline_conv", x, pseudo, weight, root_weight, bias)
     if x.dim() == 1:
@@ -103,12 +140,13 @@ def spline_conv(x, edge_index, pseudo, weight, kernel_size, is_open_spline, degr
     ks, op = _host(kernel_size, torch.int64), _host(is_open_spline, torch.uint8)
     if ks.numel() != D or op.numel() != D:
         raise RuntimeError("spline_conv: kernel_size and is_open_spline need one entry per pseudo-coordinate")
-    row, col = edge_index[0], edge_index[1]
-    plan = get_plan(row, N, owner=edge_index, tag=0, companion=col)
+    r, c = (1, 0) if transposed else (0, 1)
+    row, col = edge_index[r], edge_index[c]
+    plan = get_plan(row, N, owner=edge_index, tag=r, companion=col)
     if plan.col is not None or E == 0:
         src = plan.col if E else col
     else:
-        src, _ = _csr_arrays(plan, col, None, owner=edge_index, tag=1)
+        src, _ = _csr_arrays(plan, col, None, owner=edge_index, tag=c)
     out = torch.empty((N, Mout), dtype=x.dtype, device=x.device)
     ptr = lambda t: t.contiguous().data_ptr() if t is not None else None   # noqa: E731
     root_c = root_weight.contiguous() if root_weight is not None else None
@@ -117,6 +155,53 @@ def spline_conv(x, edge_index, pseudo, weight, kernel_size, is_open_spline, degr
         check(_lib.load().gnnops_spline_conv(x.data_ptr(), plan.rowptr.data_ptr(), plan.perm.data_ptr(), src.data_ptr(), pseudo.data_ptr(),
                                              weight.data_ptr(), ks.data_ptr(), op.data_ptr(), D, int(degree), ptr(root_c), ptr(bias_c),
                                              out.data_ptr(), N, E, Min, Mout, 1 if norm else 0, dt, _stream()), "spline_conv")
+    return out
+
+
+# ---- backward pieces (csrc/spline_bw.hip); the autograd.Functions of gnnops/autograd.py are made of these ----
+def _spline_basis_bw(grad_basis, pseudo, kernel_size, is_open_spline, degree):
+    """d pseudo [E, D] from d basis [E, S]."""
+    pseudo, grad_basis = pseudo.contiguous(), grad_basis.contiguous()
+    E, D = pseudo.shape
+    ks, op = _host(kernel_size, torch.int64), _host(is_open_spline, torch.uint8)
+    out = torch.empty_like(pseudo)
+    with _on(pseudo.device):
+        check(_lib.load().gnnops_spline_basis_bw(grad_basis.data_ptr(), pseudo.data_ptr(), ks.data_ptr(), op.data_ptr(), E, D, int(degree),
+                                                 out.data_ptr(), _dtype_code(pseudo, "spline_basis_bw"), _stream()), "spline_basis_bw")
+    return out
+
+
+def _spline_bw_basis(grad_out, x, weight, weight_index, x_rows=None, g_rows=None):
+    """d basis[e, s] = x[x_rows[e]]^T weight[weight_index[e, s]] grad_out[g_rows[e]] (row index None = row e)."""
+    E, S = weight_index.shape
+    out = torch.empty((E, S), dtype=x.dtype, device=x.device)
+    ptr = lambda t: t.data_ptr() if t is not None else None   # noqa: E731
+    with _on(x.device):
+        check(_lib.load().gnnops_spline_weighting_bw_basis(grad_out.data_ptr(), x.data_ptr(), weight.data_ptr(), weight_index.data_ptr(),
+                                                           ptr(x_rows), ptr(g_rows), out.data_ptr(), E, weight.size(1), weight.size(2), S,
+                                                           _dtype_code(x, "spline_weighting_bw_basis"), _stream()),
+              "spline_weighting_bw_basis")
+    return out
+
+
+def _spline_bw_weight(grad_out, x, basis, weight_index, K, x_rows=None, g_rows=None, plan=None):
+    """d weight [K, Min, Mout]: the E * S (edge, combination) pairs grouped by kernel index (``plan`` = Plan of
+    weight_index.view(-1) over K, built here when not given), one MFMA contraction per kernel. Every entry is written."""
+    E, S = weight_index.shape
+    Min, Mout = x.size(1), grad_out.size(1)
+    out = torch.empty((K, Min, Mout), dtype=x.dtype, device=x.device)
+    L = _lib.load()
+    if E * S and plan is None:
+        plan = ops.Plan(weight_index.view(-1), K)
+    ws_bytes = L.gnnops_spline_weighting_bw_weight_workspace_bytes(E, S, Min, Mout)
+    ws = torch.empty(max(ws_bytes, 4), dtype=torch.uint8, device=x.device)
+    ptr = lambda t: t.data_ptr() if t is not None else None   # noqa: E731
+    with _on(x.device):
+        check(L.gnnops_spline_weighting_bw_weight(grad_out.data_ptr(), x.data_ptr(), basis.data_ptr(),
+                                                  plan.rowptr.data_ptr() if plan is not None else None,
+                                                  plan.perm.data_ptr() if plan is not None else None, ptr(x_rows), ptr(g_rows),
+                                                  out.data_ptr(), E, K, Min, Mout, S, _dtype_code(x, "spline_weighting_bw_weight"),
+                                                  ws.data_ptr(), ws_bytes, _stream()), "spline_weighting_bw_weight")
     return out
 
 

@@ -465,6 +465,17 @@ int gnnops_edge_grad(int functor, const void* p, int64_t ldp, const void* q, int
  *   gnnops_spline_conv       the whole layer per destination row in one pass: (rowptr, perm) = plan of edge_index[0],
  *                            src int64 [E] = edge_index[1] in plan order, pseudo [E, D] in edge order; norm != 0 divides by
  *                            the row's degree; root_weight [Min, Mout] and bias [Mout] optional
+ *   Backward (csrc/spline_bw.hip; named after the package's own backward ops). x_rows / g_rows: optional int64 [E] row
+ *   indices into x / grad_out (NULL = row e) - spline_conv's backward passes edge_index[1] / edge_index[0], so no gathered
+ *   [E, Min] / [E, Mout] copy exists. No floating-point atomics: repeated calls give identical bits.
+ *   gnnops_spline_basis_bw            grad_basis [E, S] -> grad_pseudo [E, D] (floor() carries no gradient)
+ *   gnnops_spline_weighting_bw_basis  grad_basis[e, s] = x[xr(e)]^T weight[weight_index[e, s]] grad_out[gr(e)]
+ *   gnnops_spline_weighting_bw_weight grad_weight [K, Min, Mout], every entry written (exact zeros for kernels no pair uses):
+ *                                     (rowptr [K + 1], perm [E * S]) = gnnops_plan_build of weight_index viewed as [E * S]
+ *                                     over K; per kernel an MFMA contraction of the gathered rows basis * x and grad_out.
+ *                                     E * S < 2^31. Workspace: gnnops_spline_weighting_bw_weight_workspace_bytes.
+ *   grad_x has no entry point of its own: it is gnnops_spline_weighting / gnnops_spline_conv on grad_out with the table
+ *   transposed to [K, Mout, Min] (gnnops_transpose_batched), for the layer over the plan of edge_index[1].
  * torch_cluster  (batches as CSR pointers ptr [batches + 1] int64 over points sorted by batch; all arrays on the device)
  *   gnnops_grid_cluster  voxel id per point; size / start / end: device double [D]
  *   gnnops_knn           col [Ny, k] = the k nearest x of every y within its batch, ascending (distance, index); -1 = none
@@ -485,6 +496,16 @@ int gnnops_spline_conv(const void* x, const int32_t* rowptr, const int32_t* perm
                        const void* weight, const int64_t* kernel_size, const uint8_t* is_open_spline, int D, int degree,
                        const void* root_weight, const void* bias, void* out, int64_t N, int64_t E, int64_t Min, int64_t Mout,
                        int norm, int dtype, gnnops_stream_t stream);
+int gnnops_spline_basis_bw(const void* grad_basis, const void* pseudo, const int64_t* kernel_size, const uint8_t* is_open_spline,
+                           int64_t E, int D, int degree, void* grad_pseudo, int dtype, gnnops_stream_t stream);
+int gnnops_spline_weighting_bw_basis(const void* grad_out, const void* x, const void* weight, const int64_t* weight_index,
+                                     const int64_t* x_rows, const int64_t* g_rows, void* grad_basis, int64_t E, int64_t Min,
+                                     int64_t Mout, int64_t S, int dtype, gnnops_stream_t stream);
+size_t gnnops_spline_weighting_bw_weight_workspace_bytes(int64_t E, int64_t S, int64_t Min, int64_t Mout);
+int gnnops_spline_weighting_bw_weight(const void* grad_out, const void* x, const void* basis, const int32_t* rowptr,
+                                      const int32_t* perm, const int64_t* x_rows, const int64_t* g_rows, void* grad_weight,
+                                      int64_t E, int64_t K, int64_t Min, int64_t Mout, int64_t S, int dtype, void* workspace,
+                                      size_t workspace_bytes, gnnops_stream_t stream);
 int gnnops_grid_cluster(const void* pos, int64_t N, int D, const double* d_size, const double* d_start, const double* d_end,
                         int64_t* cluster, int dtype, gnnops_stream_t stream);
 int gnnops_knn(const void* x, const void* y, const int64_t* ptr_x, const int64_t* ptr_y, int64_t batches, int64_t Ny, int D,
