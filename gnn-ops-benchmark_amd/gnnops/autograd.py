@@ -41,7 +41,8 @@ class _ScatterMean(torch.autograd.Function):
     def forward(ctx, src, index, dim, dim_size):
         dim = dim % src.dim()
         out = ops.scatter(src, index, dim, None, dim_size, "mean")
-        ones = torch.ones((src.size(dim),) if index.dim() == 1 else src.shape, dtype=src.dtype, device=src.device)
+        # counted in float32 whatever src is: a bf16 count is rounded above 256, an fp16 one is inf above 65504 (gradient 0)
+        ones = torch.ones((src.size(dim),) if index.dim() == 1 else src.shape, dtype=torch.float32, device=src.device)
         count = ops.scatter(ones, index, 0 if index.dim() == 1 else dim, None, out.size(dim), "sum").clamp_(min=1)
         if index.dim() == 1:
             shape = [1] * src.dim()
@@ -54,7 +55,7 @@ class _ScatterMean(torch.autograd.Function):
     @staticmethod
     def backward(ctx, grad_out):
         index, count = ctx.saved_tensors
-        return _gather_back((grad_out / count).contiguous(), index, ctx.dim, ctx.src_shape), None, None, None
+        return _gather_back((grad_out / count).to(grad_out.dtype).contiguous(), index, ctx.dim, ctx.src_shape), None, None, None
 
 
 class _ScatterMinMax(torch.autograd.Function):
@@ -179,9 +180,9 @@ class _SegmentCSR(torch.autograd.Function):
         seg = index if index is not None else segment.expand_rowptr(indptr, src.size(0))
         if reduce == "mean":
             if index is not None:
-                cnt = ops.scatter(torch.ones(src.size(0), dtype=src.dtype, device=src.device), index, 0, None, N, "sum")
+                cnt = ops.scatter(torch.ones(src.size(0), dtype=torch.float32, device=src.device), index, 0, None, N, "sum")
             else:
-                cnt = (indptr[1:] - indptr[:-1]).to(src.dtype)
+                cnt = (indptr[1:] - indptr[:-1]).to(torch.float32)   # float32 counts: see _ScatterMean
             ctx.save_for_backward(seg, cnt.clamp_(min=1))
         else:
             ctx.save_for_backward(seg)
@@ -199,7 +200,7 @@ class _SegmentCSR(torch.autograd.Function):
             return dx[: ctx.E], None, None, None, None
         if ctx.reduce == "mean":
             seg, cnt = ctx.saved_tensors
-            g = g / cnt.view([-1] + [1] * (g.dim() - 1))
+            g = (g / cnt.view([-1] + [1] * (g.dim() - 1))).to(g.dtype)
         else:
             (seg,) = ctx.saved_tensors
         g_ext = torch.cat([g, g.new_zeros((1,) + tuple(g.shape[1:]))])     # row N: positions outside every segment

@@ -360,13 +360,16 @@ def composite(src, index, N, mode, eps=1e-12, unbiased=True):
             out[n] = np.sqrt(var / (f32(c) + f32(1e-6)))
             continue
         m = x.max(axis=0) if len(rows) else np.zeros(K, f32)
-        s = np.zeros(K, f32)
-        for r in x:
-            s = s + np.exp(r - m, dtype=f32)
-        if mode == "logsumexp":
-            out[n] = m + np.log(s + f32(eps), dtype=f32)
-        elif mode == "softmax":
-            out[rows] = np.exp(x - m, dtype=f32) / s
-        else:
-            out[rows] = (x - m) - np.log(s + f32(eps), dtype=f32)
+        with np.errstate(invalid="ignore", divide="ignore"):
+            d = x - m
+            d[np.isnan(d)] = -np.inf          # (-inf) - (-inf), a wholly masked group: counted as -inf (composite.hip)
+            s = np.zeros(K, f32)
+            for r in d:
+                s = s + np.exp(r, dtype=f32)
+            if mode == "logsumexp":
+                out[n] = m + np.log(s + f32(eps), dtype=f32)
+            elif mode == "softmax":
+                out[rows] = np.exp(d, dtype=f32) / s
+            else:
+                out[rows] = d - np.log(s + f32(eps), dtype=f32)
     return out
