@@ -490,7 +490,8 @@ class _SplineConv(torch.autograd.Function):
             ghat = G
             if ctx.norm:
                 rowptr = ops.get_plan(row, N, owner=edge_index, tag=0, companion=col).rowptr
-                ghat = G / (rowptr[1:] - rowptr[:-1]).clamp_(min=1).to(G.dtype).unsqueeze(1)
+                # degree and division in float32, rounded once (an fp16 degree above 65504 is inf, a bf16 one above 256 inexact)
+                ghat = (G / (rowptr[1:] - rowptr[:-1]).clamp(min=1).to(torch.float32).unsqueeze(1)).to(G.dtype)
             if need[2] or need[3]:
                 basis, wi = spatial._spline_basis_raw(pseudo, *ctx.meta)
             if need[3]:

@@ -145,8 +145,9 @@ class _EdgeReduce(torch.autograd.Function):
         E = index.size(1)
         plan_dst = get_plan(dst_rows, ctx.num_dst, owner=edge_index, tag=1, companion=src_rows)
         if ctx.aggr == "mean":
-            deg = (plan_dst.rowptr[1:] - plan_dst.rowptr[:-1]).clamp(min=1).to(g.dtype)
-            g = g / deg.unsqueeze(1)
+            # counted and divided in float32, rounded once: an fp16 degree above 65504 is inf (gradient 0), a bf16 one above 256 inexact
+            deg = (plan_dst.rowptr[1:] - plan_dst.rowptr[:-1]).clamp(min=1).to(torch.float32)
+            g = (g / deg.unsqueeze(1)).to(g.dtype)
         d_q = d_p = d_w = None
         K = g.size(1)
         if ctx.functor == "copy":
@@ -161,11 +162,12 @@ class _EdgeReduce(torch.autograd.Function):
         q_, ldq = _rows(q, "q", _PARTS[ctx.functor][0], K)
         p_, ldp = _rows(p, "p", 2, K)
         w_, ldw = _rows(w, "w", 2, K) if has_w else (None, 0)
+        g, ldg = _rows(g, "the output gradient", 1, K)     # one expanded row (out.sum().backward()) has stride 0
         gp = torch.empty((E, 2 * K), dtype=g.dtype, device=g.device)
         gq = torch.empty((E, K), dtype=g.dtype, device=g.device) if ctx.functor == "film" else None
         ptr = lambda t: t.data_ptr() if t is not None else None   # noqa: E731
         with _on(g.device):
-            check(_lib.load().gnnops_edge_grad(FUNCTORS[ctx.functor], ptr(p_), ldp, ptr(q_), ldq, ptr(w_), ldw, g.data_ptr(), g.stride(0),
+            check(_lib.load().gnnops_edge_grad(FUNCTORS[ctx.functor], ptr(p_), ldp, ptr(q_), ldq, ptr(w_), ldw, g.data_ptr(), ldg,
                                                src_rows.data_ptr(), dst_rows.data_ptr(), gp.data_ptr(), ptr(gq), E, K,
                                                _dtype_code(g, "edge_grad"), _stream()), "edge_grad")
         if need_p:

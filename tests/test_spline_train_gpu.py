@@ -281,3 +281,75 @@ def test_a_spline_cnn_trains():
         losses.append(float(loss.detach()))
     assert all(l == l for l in losses) and losses[-1] < 0.7 * losses[0], losses
     assert all(not torch.equal(a, b.detach()) for a, b in zip(start, params))
+
+
+# ---- norm=True with a row whose degree the storage type cannot hold --------------------------------------------------------
+def _hub_row_inputs(dtype, hub, n=64, e=2000, m=8):
+    """make_inputs on (1, 1, [5], [1]) with row 5 brought to exactly ``hub`` edges: the extra ones come from columns 0 .. 9,
+    which feed no other row."""
+    cfg = (1, 1, [5], [1])
+    inputs, R, ei = sc.make_inputs(900, n, e, cfg, m, m, True, dtype)
+    g = torch.Generator().manual_seed(901)
+    ei[1] = 10 + ei[1] % (n - 10)
+    more = hub - int((ei[0] == 5).sum())
+    ei = torch.cat([ei, torch.stack([torch.full((more,), 5), torch.randint(0, 10, (more,), generator=g)])], 1)
+    inputs["pseudo"] = torch.cat([inputs["pseudo"], sc.pseudo_coords(g, more, 1, [5], [1]).to(dtype).double()])
+    return cfg, inputs, R, ei
+
+
+def _degree_scaled(grads, ei, n):
+    """d pseudo[e] times the degree of the row e belongs to, d x[j] times the smallest degree among the rows j feeds: a member
+    of the 70 000-edge row has 1 / 70 000 of the gradient of the rest and would vanish under a max-relative measure."""
+    import conv_chain as cc
+
+    s = cc.mean_scales(torch.stack([ei[1], ei[0]]), n, n)
+    return {k: (v * s["w"] if k == "pseudo" else v * s["q"] if k == "x" else v) for k, v in grads.items()}
+
+
+@pytest.mark.parametrize("via", ["op", "layer"])
+@pytest.mark.parametrize("dtype,hub", [(torch.float16, 70000), (torch.bfloat16, 257)], ids=["float16-70000", "bfloat16-257"])
+def test_norm_with_a_degree_the_storage_type_cannot_hold(tsc, dtype, hub, via):
+    """spline_conv(norm=True) / SplineConv(aggr="mean"): the backward divides G by the degree, counted and divided in float32.
+    fp16: 70 000 is inf, so a degree in the storage type zeroes the row's gradient and that of every column feeding it (an error
+    of 1.0 of scale on the degree-scaled d x): this is what the case pins. bf16: 257 is 256, the largest relative error a bf16
+    degree can have (0.39 %); that is BELOW what bf16 storage of the gradients costs by itself (self error of d pseudo 2e-3, bar
+    8e-3), so no bf16 bar derived from the chain can tell a rounded degree from an exact one — the case covers the branch and
+    says so, it does not pin the bf16 degree.
+    Bars: the three tensors the degree reaches (d x, d pseudo, d weight, degree-scaled) take 4 x the distance of the chain run in
+    the storage type (spline_chain with ``rnd``, each gradient stored once in that type) from the float64 chain, TOL where that is tighter, measured here on the CPU from the chain alone; out, d
+    root_weight and d bias, whose storage roundings that chain does not model, keep this file's TOL."""
+    cfg, inputs, R, ei = _hub_row_inputs(dtype, hub)
+    n = inputs["x"].size(0)
+    deg = torch.bincount(ei[0], minlength=n)
+    assert int(deg[5]) == hub and not bool((ei[1][ei[0] != 5] < 10).any())
+    assert float(deg[5].to(dtype)) != hub            # the storage type cannot hold this degree
+    want_out, want = sc.conv_grads(inputs, ei, R, cfg[2], cfg[3], cfg[0], True)
+    _, self_grads = sc.conv_grads(inputs, ei, R, cfg[2], cfg[3], cfg[0], True, rnd=dtype)
+    self_grads = {k: v.to(dtype).double() for k, v in self_grads.items()}       # each gradient is stored in the storage type
+    want_s, self_s = _degree_scaled(want, ei, n), _degree_scaled(self_grads, ei, n)
+    bars = {k: TOL[dtype] for k in list(want) + ["out"]}
+    for k in ("x", "pseudo", "weight"):
+        bars[k] = min(4 * sc.rel_err(self_s[k], want_s[k]), TOL[dtype])         # never looser than this file's own bar
+        assert bars[k] > 0, k
+    if dtype == torch.float16:                       # the bug, in the chain's terms: the hub's feeders get 0, an error of 1.0
+        lost = {k: v.clone() for k, v in want.items()}
+        lost["x"][:10] = 0
+        assert sc.rel_err(_degree_scaled(lost, ei, n)["x"], want_s["x"]) > 100 * bars["x"]
+    dev = _device(inputs, dtype)
+    if via == "op":
+        out = _conv_dev(tsc, dev, ei, R, cfg, True, dtype)
+        got = {k: dev[k].grad for k in want}
+    else:
+        from gnnops.conv import SplineConv
+
+        layer = SplineConv(8, 8, dim=1, kernel_size=5, is_open_spline=True, degree=1, aggr="mean").to(dtype).cuda()
+        with torch.no_grad():
+            layer.weight.copy_(dev["weight"]), layer.root.copy_(dev["root_weight"]), layer.bias.copy_(dev["bias"])
+        out = layer(dev["x"], ei.flip(0).cuda(), dev["pseudo"])
+        (out.float() * R.to(dtype).cuda().float()).sum().backward()
+        got = {"x": dev["x"].grad, "pseudo": dev["pseudo"].grad, "weight": layer.weight.grad, "root_weight": layer.root.grad,
+               "bias": layer.bias.grad}
+    _check(out, want_out, bars["out"], "out")
+    got_s = _degree_scaled({k: v.detach().double().cpu() for k, v in got.items()}, ei, n)
+    for k in want:
+        _check(got_s[k], want_s[k], bars[k], f"d {k} (degree-scaled)")
