@@ -14,7 +14,8 @@
 //     tile in LDS and writes 16-B row pieces.
 // Three kernels (gemm_plan() picks): the register-staged, fully bounds-checked gemm_kernel for small problems; and for
 // anything of size the LDS-DMA pipelines gemm_dma4_kernel (128 x 128 tiles) and gemm_dma256_kernel (256 x 256, eight
-// waves; gemm_sk256_kernel = the same as persistent workgroups with the last round of tiles cut along K) —
+// waves; gemm_sk256_kernel = persistent workgroups with the last round of tiles cut along K; both are gemm256_main_loop
+// over a range of K-steps followed by gemm256_epilogue over a range of rows, the split-K hand-off in between) —
 // global_load_lds_dwordx4 into four LDS stages of K = 32 with counted vmcnt waits. The reference sweeps L = 1581 ... 8164:
 // rows of any alignment are read where they lie and only the last K-tile comes from zero-filled side copies
 // (pad_tail_kernel); large A operands are still copied whole into aligned padded rows (pad_rows_kernel) — gemm_plan().
@@ -89,6 +90,28 @@ __device__ inline void epi_store8(T* __restrict__ C, const T* __restrict__ adden
                 Elem<T>::store(C + row * N + col + i, v);
             }
         }
+    }
+}
+
+// One pass of the LDS-DMA kernels' epilogues: eight staged fp32 outputs at `st` (row `row`, columns col..col+7), + addend,
+// one rounding, stored. `pre_ok` (uniform: an interior tile with an addend, 16-B rows): the addend piece was loaded ahead
+// into `pre` and nothing needs a bounds check; otherwise epi_store8 loads it and checks.
+template <typename T>
+__device__ __forceinline__ void epi_staged_row8(const float* st, T* __restrict__ C, const T* __restrict__ addend, int64_t row,
+                                                int64_t col, int64_t M, int64_t N, bool pre_ok, const u32x4& pre, bool vec_c,
+                                                bool half_c, int64_t ldadd) {
+    float f[8];
+    const f32x4 lo = *reinterpret_cast<const f32x4*>(st);
+    const f32x4 hi = *reinterpret_cast<const f32x4*>(st + 4);
+    f[0] = lo[0]; f[1] = lo[1]; f[2] = lo[2]; f[3] = lo[3]; f[4] = hi[0]; f[5] = hi[1]; f[6] = hi[2]; f[7] = hi[3];
+    if (pre_ok) {
+        float g[8];
+        Elem<T>::unpack(pre, g);
+#pragma unroll
+        for (int i = 0; i < 8; ++i) f[i] += g[i];
+        *reinterpret_cast<u32x4*>(C + row * N + col) = Elem<T>::pack(f);
+    } else {
+        epi_store8<T>(C, addend, row, col, M, N, f, vec_c, half_c, ldadd);
     }
 }
 
@@ -426,20 +449,8 @@ __global__ __launch_bounds__(256, 2) void gemm_dma4_kernel(const uint16_t* __res
 #pragma unroll
     for (int pass = 0; pass < 8; ++pass) {
         const int rr = pass * 8 + pr;
-        float f[8];
-        const f32x4 lo = *reinterpret_cast<const f32x4*>(&ctile[rr * CS + pc]);
-        const f32x4 hi = *reinterpret_cast<const f32x4*>(&ctile[rr * CS + pc + 4]);
-        f[0] = lo[0]; f[1] = lo[1]; f[2] = lo[2]; f[3] = lo[3]; f[4] = hi[0]; f[5] = hi[1]; f[6] = hi[2]; f[7] = hi[3];
-        const int64_t row = m0 + wr * 64 + rr, col = n0 + wc * 64 + pc;
-        if (pre_ok) {
-            float g[8];
-            Elem<T>::unpack(pre[pass], g);
-#pragma unroll
-            for (int i = 0; i < 8; ++i) f[i] += g[i];
-            *reinterpret_cast<u32x4*>(C + row * N + col) = Elem<T>::pack(f);
-        } else {
-            epi_store8<T>(C, addend, row, col, M, N, f, vec_c, half_c, ldadd);
-        }
+        epi_staged_row8<T>(&ctile[rr * CS + pc], C, addend, m0 + wr * 64 + rr, n0 + wc * 64 + pc, M, N, pre_ok, pre[pass], vec_c,
+                           half_c, ldadd);
     }
 }
 
@@ -454,20 +465,31 @@ constexpr int A2_BYTES = BM2 * BK4 * 2, B2_BYTES = BK4 * BN2 * 2, STAGE2_BYTES =
 constexpr int GEMM256_SMEM = NST * STAGE2_BYTES;                                                       // 128 KiB
 constexpr int EPI2_ROWS = 32;  // rows of a wave's 128 staged per epilogue round: 8 waves x 32 x CS x 4 B = 68 KiB
 
-template <typename T, bool IS_BF16>
-__global__ __launch_bounds__(512, 2) void gemm_dma256_kernel(const uint16_t* __restrict__ A, const uint16_t* __restrict__ Bm,
-                                                             const T* __restrict__ addend, T* __restrict__ C, int64_t M,
-                                                             int64_t N, int64_t K, int64_t lda, int64_t ldb, int64_t ldadd,
-                                                             const uint16_t* __restrict__ At, const uint16_t* __restrict__ Bt,
-                                                             int64_t Kmain) {
-    extern __shared__ __attribute__((aligned(1024))) unsigned char smem256[];
-    unsigned char* smem = smem256;
-
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+// The main loop of both 256 x 256 kernels: acc = A[m0.., K-steps kb .. kb+ksteps-1] @ B[.., n0..] for the workgroup's tile,
+// every wave its 128 x 64 part. Zeroes acc, builds the per-lane DMA sources and LDS read offsets from `tid` (a caller
+// that loops over tiles decides through `tid` what may be hoisted), and returns behind the barrier that frees the stages.
+//
+// Ping-pong: waves 0-3 and 4-7 — wave w and w + 4 share a SIMD — run half a K-step apart, so one partner's memory
+// phase (16 fragment reads, 4 DMA pieces at ~100 cycles of issue each, their latency) runs under the other's 32
+// back-to-back MFMAs (all eight waves in lockstep measured 0.88 against 0.79 ms at 8192^3 bf16). Still ONE barrier
+// per K-step kt:
+//   waves 0-3 reach it after the MFMAs of tile kt, waves 4-7 after reading tile kt's fragments (reads retired);
+//   every wave has waited for its own DMA pieces of tile kt+1 (vmcnt(8): tiles kt+2, kt+3 stay in flight);
+//   behind it waves 0-3 read tile kt+1 and refill tile kt's stage with tile kt+4, waves 4-7 multiply tile kt,
+//   then read tile kt+1 and refill tile kt's stage too (their pieces of tile kt+4 = (kt+1)+3).
+// Both groups execute 1 + ksteps barriers. Fragments are single-buffered: a wave's MFMAs have all issued before
+// its next reads are. Fragment reads are inline asm: as builtins the transpose reads are ordered after EVERY
+// outstanding LDS-DMA (s_waitcnt vmcnt(0)), which would undo the counted waits. Each s_waitcnt carries the registers
+// it releases as operands, so no MFMA that uses them is scheduled above it.
+template <bool IS_BF16>
+__device__ __forceinline__ void gemm256_main_loop(f32x4 (&acc)[8][4], unsigned char* smem, const uint16_t* __restrict__ A,
+                                                  const uint16_t* __restrict__ Bm, const uint16_t* __restrict__ At,
+                                                  const uint16_t* __restrict__ Bt, int64_t M, int64_t N, int64_t lda,
+                                                  int64_t ldb, int64_t Kmain, int64_t m0, int64_t n0, int64_t kb,
+                                                  int64_t ksteps, int tid) {
+    const int lane = tid & 63, wave = tid >> 6;
     const int wr = wave >> 2, wc = wave & 3;  // 2 x 4 waves: rows wr*128, columns wc*64
-    const int64_t m0 = (int64_t)blockIdx.y * BM2, n0 = (int64_t)blockIdx.x * BN2;
 
-    f32x4 acc[8][4];
 #pragma unroll
     for (int i = 0; i < 8; ++i)
 #pragma unroll
@@ -492,6 +514,9 @@ __global__ __launch_bounds__(512, 2) void gemm_dma256_kernel(const uint16_t* __r
         b_dst[p] = A2_BYTES + half * (B2_BYTES / 2) + (q & 7) * 1024;
     }
     const int64_t b_dt = tail_delta_b(Bm, Bt, ldb, Kmain);
+    // Tile tn of the range into stage tn % 4. Past the last tile the DMA re-fetches tile ksteps-1 into a stage nobody reads
+    // again: the counts stay free of branches. An empty range (a split-K piece of a short K) re-fetches K-step kb, which
+    // lies inside both operands.
     auto dma_a = [&](int stage, int64_t k0, int p) {
         __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(a_src[p] + k0 + (k0 >= Kmain ? a_dt[p] : 0)),
                                          (__attribute__((address_space(3))) void*)(smem + stage * STAGE2_BYTES + (wave * 2 + p) * 1024),
@@ -501,12 +526,15 @@ __global__ __launch_bounds__(512, 2) void gemm_dma256_kernel(const uint16_t* __r
         __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(b_src[p] + k0 * ldb + (k0 >= Kmain ? b_dt : 0)),
                                          (__attribute__((address_space(3))) void*)(smem + stage * STAGE2_BYTES + b_dst[p]), 16, 0, 0);
     };
-    auto dma = [&](int stage, int64_t k0) {
+    auto dma = [&](int stage, int64_t k0) {   // k0 >= Kmain (uniform): the last K-tile comes from the zero-padded side copies
 #pragma unroll
         for (int p = 0; p < 2; ++p) {
             dma_a(stage, k0, p);
             dma_b(stage, k0, p);
         }
+    };
+    auto dma_tile = [&](int64_t tn) {
+        dma((int)(tn & (NST - 1)), (kb + (tn < ksteps ? tn : (ksteps > 0 ? ksteps - 1 : 0))) * BK4);
     };
 
     const int a_row = wr * 128 + (lane & 15);
@@ -524,19 +552,6 @@ __global__ __launch_bounds__(512, 2) void gemm_dma256_kernel(const uint16_t* __r
         b_hi_off[ni] = b_rd + b_off(b_row + 4, ch) + 8 * (b_p & 1);
     }
 
-    const int64_t ksteps = K / BK4;  // even: K is a multiple of 64
-    // Ping-pong: waves 0-3 and 4-7 — wave w and w + 4 share a SIMD — run half a K-step apart, so one partner's memory
-    // phase (16 fragment reads, 4 DMA pieces at ~100 cycles of issue each, their latency) runs under the other's 32
-    // back-to-back MFMAs (all eight waves in lockstep measured 0.88 against 0.79 ms at 8192^3 bf16). Still ONE barrier
-    // per K-step kt:
-    //   waves 0-3 reach it after the MFMAs of tile kt, waves 4-7 after reading tile kt's fragments (reads retired);
-    //   every wave has waited for its own DMA pieces of tile kt+1 (vmcnt(8): tiles kt+2, kt+3 stay in flight);
-    //   behind it waves 0-3 read tile kt+1 and refill tile kt's stage with tile kt+4, waves 4-7 multiply tile kt,
-    //   then read tile kt+1 and refill tile kt's stage too (their pieces of tile kt+4 = (kt+1)+3).
-    // Both groups execute 1 + ksteps barriers. Fragments are single-buffered: a wave's MFMAs have all issued before
-    // its next reads are. Fragment reads are inline asm: as builtins the transpose reads are ordered after EVERY
-    // outstanding LDS-DMA (s_waitcnt vmcnt(0)), which would undo the counted waits. Each s_waitcnt carries the registers
-    // it releases as operands, so no MFMA that uses them is scheduled above it.
     s16x8 af[8];
     s16x4 blo[4], bhi[4];
     auto read_all = [&](int64_t t) {
@@ -573,8 +588,6 @@ __global__ __launch_bounds__(512, 2) void gemm_dma256_kernel(const uint16_t* __r
             for (int ni = 0; ni < 4; ++ni) acc[mi][ni] = mfma16<IS_BF16>(af[mi], bf[ni], acc[mi][ni]);
         __builtin_amdgcn_sched_barrier(0);
     };
-    // past the last tile the DMA re-fetches tile ksteps-1 into a stage nobody reads again: the counts stay free of branches
-    auto dma_tile = [&](int64_t tn) { dma((int)(tn & (NST - 1)), (tn < ksteps ? tn : ksteps - 1) * BK4); };
     dma_tile(0);
     dma_tile(1);
     dma_tile(2);
@@ -611,20 +624,30 @@ __global__ __launch_bounds__(512, 2) void gemm_dma256_kernel(const uint16_t* __r
                    "+v"(af[6]), "+v"(af[7])
                  :
                  : "memory");
-    __syncthreads();  // all DMA (including the redundant tail fetches) landed, all reads done: the stages become the epilogue's
+    __syncthreads();  // all DMA (including the redundant tail fetches) landed, all reads done: the stages are free
+}
 
+// The epilogue of both 256 x 256 kernels: the 16-row blocks [mi_lo, mi_hi) of every wave's 128 x 64 accumulators, + addend,
+// one rounding, through EPI2_ROWS staged rows per wave and round (8 lanes x 8 columns per row: 16-B accesses).
+template <typename T>
+__device__ __forceinline__ void gemm256_epilogue(f32x4 (&acc)[8][4], unsigned char* smem, T* __restrict__ C,
+                                                 const T* __restrict__ addend, int64_t M, int64_t N, int64_t ldadd, int64_t m0,
+                                                 int64_t n0, int tid, bool vec_c, bool half_c, int mi_lo, int mi_hi) {
+    const int lane = tid & 63, wave = tid >> 6;
+    const int wr = wave >> 2, wc = wave & 3;
     float* ctile = reinterpret_cast<float*>(smem) + wave * (EPI2_ROWS * CS);
-    const bool vec_c = (N % 8 == 0) && ((uintptr_t)C % 16 == 0) && (addend == nullptr || (uintptr_t)addend % 16 == 0);
-    const bool half_c = (N % 4 == 0) && ((uintptr_t)C % 8 == 0) && (addend == nullptr || (uintptr_t)addend % 8 == 0);
     const int pr = lane >> 3, pc = (lane & 7) * 8;
     // Interior tile with an addend: all 16 addend pieces of this lane (one per staged row it stores) are requested here, in
     // one round trip under the staging below, instead of one dependent global load per store pass (16 round trips).
+    // Only pieces of blocks that are stored: the compiler keeps a load nobody reads pending across the persistent kernel's
+    // back edge and waits for it (vmcnt(0)) where its register is next written — the fragment reads of the next main loop.
     const bool pre_ok = vec_c && addend != nullptr && m0 + BM2 <= M && n0 + BN2 <= N;
     u32x4 pre[16];
     if (pre_ok) {
         const T* ap = addend + (m0 + wr * 128 + pr) * ldadd + n0 + wc * 64 + pc;
 #pragma unroll
-        for (int i = 0; i < 16; ++i) pre[i] = *reinterpret_cast<const u32x4*>(ap + (int64_t)i * 8 * ldadd);
+        for (int i = 0; i < 16; ++i)   // piece i belongs to 16-row block i / 2
+            if (i / 2 >= mi_lo && i / 2 < mi_hi) pre[i] = *reinterpret_cast<const u32x4*>(ap + (int64_t)i * 8 * ldadd);
     }
 #pragma unroll
     for (int c = 0; c < 128 / EPI2_ROWS; ++c) {
@@ -638,24 +661,34 @@ __global__ __launch_bounds__(512, 2) void gemm_dma256_kernel(const uint16_t* __r
         __builtin_amdgcn_wave_barrier();
 #pragma unroll
         for (int pass = 0; pass < EPI2_ROWS / 8; ++pass) {
+            if (c * 2 + pass / 2 < mi_lo || c * 2 + pass / 2 >= mi_hi) continue;
             const int rr = pass * 8 + pr;
-            float f[8];
-            const f32x4 lo = *reinterpret_cast<const f32x4*>(&ctile[rr * CS + pc]);
-            const f32x4 hi = *reinterpret_cast<const f32x4*>(&ctile[rr * CS + pc + 4]);
-            f[0] = lo[0]; f[1] = lo[1]; f[2] = lo[2]; f[3] = lo[3]; f[4] = hi[0]; f[5] = hi[1]; f[6] = hi[2]; f[7] = hi[3];
-            const int64_t row = m0 + wr * 128 + c * EPI2_ROWS + rr, col = n0 + wc * 64 + pc;
-            if (pre_ok) {
-                float g[8];
-                Elem<T>::unpack(pre[c * 4 + pass], g);
-#pragma unroll
-                for (int i = 0; i < 8; ++i) f[i] += g[i];
-                *reinterpret_cast<u32x4*>(C + row * N + col) = Elem<T>::pack(f);
-            } else {
-                epi_store8<T>(C, addend, row, col, M, N, f, vec_c, half_c, ldadd);
-            }
+            epi_staged_row8<T>(&ctile[rr * CS + pc], C, addend, m0 + wr * 128 + c * EPI2_ROWS + rr, n0 + wc * 64 + pc, M, N,
+                               pre_ok, pre[c * 4 + pass], vec_c, half_c, ldadd);
         }
         __builtin_amdgcn_wave_barrier();
     }
+}
+
+template <typename T, bool IS_BF16>
+__global__ __launch_bounds__(512, 2) void gemm_dma256_kernel(const uint16_t* __restrict__ A, const uint16_t* __restrict__ Bm,
+                                                             const T* __restrict__ addend, T* __restrict__ C, int64_t M,
+                                                             int64_t N, int64_t K, int64_t lda, int64_t ldb, int64_t ldadd,
+                                                             const uint16_t* __restrict__ At, const uint16_t* __restrict__ Bt,
+                                                             int64_t Kmain) {
+    extern __shared__ __attribute__((aligned(1024))) unsigned char smem256[];
+    unsigned char* smem = smem256;
+
+    const int tid = threadIdx.x;
+    const int64_t m0 = (int64_t)blockIdx.y * BM2, n0 = (int64_t)blockIdx.x * BN2;
+    const int64_t ksteps = K / BK4;  // even: K is a multiple of 64
+    __builtin_assume(ksteps > 0);    // the empty-range clamp of the main loop is the split-K kernel's alone
+    f32x4 acc[8][4];
+    gemm256_main_loop<IS_BF16>(acc, smem, A, Bm, At, Bt, M, N, lda, ldb, Kmain, m0, n0, 0, ksteps, tid);
+
+    const bool vec_c = (N % 8 == 0) && ((uintptr_t)C % 16 == 0) && (addend == nullptr || (uintptr_t)addend % 16 == 0);
+    const bool half_c = (N % 4 == 0) && ((uintptr_t)C % 8 == 0) && (addend == nullptr || (uintptr_t)addend % 8 == 0);
+    gemm256_epilogue<T>(acc, smem, C, addend, M, N, ldadd, m0, n0, tid, vec_c, half_c, 0, 8);
 }
 
 template <typename T, bool IS_BF16>
@@ -751,138 +784,12 @@ __global__ __launch_bounds__(512, 2) void gemm_sk256_kernel(const uint16_t* __re
         int tm, tn;
         sk_tile_rc(t, tiles_m, tiles_n, tm, tn);
         const int64_t m0 = (int64_t)tm * BM2, n0 = (int64_t)tn * BN2;
-        const int64_t ksteps = ke - kb;
         // per-lane constants are rebuilt for every piece from a value the compiler cannot see through: hoisted out of the
         // persistent loop they (and the epilogue's addresses) stay live across the main loop and spill
         int tid = threadIdx.x;
         asm volatile("" : "+v"(tid));
-        const int lane = tid & 63, wave = tid >> 6;
-        const int wr = wave >> 2, wc = wave & 3;
-        const int a_row = wr * 128 + (lane & 15);
-        const int a_kc = lane >> 4;
-        const int b_q = (lane & 15) >> 2, b_p = lane & 3;
-        const int b_row = 8 * (lane >> 4) + b_q;
-        const uint32_t smem_lds = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) const unsigned char*)smem;
-        const uint32_t a_rd = smem_lds + a4_off(a_row, a_kc);
-        const uint32_t b_rd = smem_lds + A2_BYTES + (wc >> 1) * (B2_BYTES / 2);
-        uint32_t b_lo_off[4], b_hi_off[4];
-#pragma unroll
-        for (int ni = 0; ni < 4; ++ni) {
-            const int ch = (wc & 1) * 8 + ni * 2 + (b_p >> 1);
-            b_lo_off[ni] = b_rd + b_off(b_row, ch) + 8 * (b_p & 1);
-            b_hi_off[ni] = b_rd + b_off(b_row + 4, ch) + 8 * (b_p & 1);
-        }
-
         f32x4 acc[8][4];
-#pragma unroll
-        for (int i = 0; i < 8; ++i)
-#pragma unroll
-            for (int j = 0; j < 4; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-
-        const uint16_t* a_src[2];
-        const uint16_t* b_src[2];
-        int64_t a_dt[2];
-        int b_dst[2];
-#pragma unroll
-        for (int p = 0; p < 2; ++p) {
-            const int ar = (wave * 2 + p) * 16 + (lane >> 2);
-            const int64_t arow = (m0 + ar < M) ? m0 + ar : M - 1;
-            a_src[p] = A + arow * lda + (((lane & 3) ^ a4_swz(ar)) << 3);
-            a_dt[p] = tail_delta_a(A, At, arow, lda, Kmain);
-            const int q = wave * 2 + p, half = q >> 3;
-            const int br = (q & 7) * 4 + (lane >> 4);
-            int64_t bcol = n0 + half * 128 + (((lane & 15) ^ (((br & 3) << 2) | ((br >> 2) & 3))) << 3);
-            if (bcol > ((N - 1) & ~(int64_t)7)) bcol = (N - 1) & ~(int64_t)7;
-            b_src[p] = Bm + (int64_t)br * ldb + bcol;
-            b_dst[p] = A2_BYTES + half * (B2_BYTES / 2) + (q & 7) * 1024;
-        }
-        const int64_t b_dt = tail_delta_b(Bm, Bt, ldb, Kmain);
-        auto dma_tile = [&](int64_t tn_) {
-            const int stage = (int)(tn_ & (NST - 1));
-            const int64_t k0 = (kb + (tn_ < ksteps ? tn_ : ksteps - 1)) * BK4;
-            const bool in_tail = k0 >= Kmain;
-#pragma unroll
-            for (int p = 0; p < 2; ++p) {
-                __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(a_src[p] + k0 + (in_tail ? a_dt[p] : 0)),
-                                                 (__attribute__((address_space(3))) void*)(smem + stage * STAGE2_BYTES + (wave * 2 + p) * 1024),
-                                                 16, 0, 0);
-                __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(b_src[p] + k0 * ldb + (in_tail ? b_dt : 0)),
-                                                 (__attribute__((address_space(3))) void*)(smem + stage * STAGE2_BYTES + b_dst[p]), 16, 0, 0);
-            }
-        };
-        s16x8 af[8];
-        s16x4 blo[4], bhi[4];
-        auto read_all = [&](int64_t tt) {
-            const uint32_t st = (uint32_t)(tt & (NST - 1)) * STAGE2_BYTES;
-#pragma unroll
-            for (int ni = 0; ni < 4; ++ni) {
-                asm volatile("ds_read_b64_tr_b16 %0, %1" : "=v"(blo[ni]) : "v"(b_lo_off[ni] + st));
-                asm volatile("ds_read_b64_tr_b16 %0, %1" : "=v"(bhi[ni]) : "v"(b_hi_off[ni] + st));
-            }
-            const uint32_t aa = a_rd + st;
-            asm volatile("ds_read_b128 %0, %1" : "=v"(af[0]) : "v"(aa));
-            asm volatile("ds_read_b128 %0, %1 offset:1024" : "=v"(af[1]) : "v"(aa));
-            asm volatile("ds_read_b128 %0, %1 offset:2048" : "=v"(af[2]) : "v"(aa));
-            asm volatile("ds_read_b128 %0, %1 offset:3072" : "=v"(af[3]) : "v"(aa));
-            asm volatile("ds_read_b128 %0, %1 offset:4096" : "=v"(af[4]) : "v"(aa));
-            asm volatile("ds_read_b128 %0, %1 offset:5120" : "=v"(af[5]) : "v"(aa));
-            asm volatile("ds_read_b128 %0, %1 offset:6144" : "=v"(af[6]) : "v"(aa));
-            asm volatile("ds_read_b128 %0, %1 offset:7168" : "=v"(af[7]) : "v"(aa));
-        };
-        auto wait_reads = [&]() {
-            asm volatile("s_waitcnt lgkmcnt(0)"
-                         : "+v"(blo[0]), "+v"(blo[1]), "+v"(blo[2]), "+v"(blo[3]), "+v"(bhi[0]), "+v"(bhi[1]), "+v"(bhi[2]),
-                           "+v"(bhi[3]), "+v"(af[0]), "+v"(af[1]), "+v"(af[2]), "+v"(af[3]), "+v"(af[4]), "+v"(af[5]),
-                           "+v"(af[6]), "+v"(af[7]));
-        };
-        auto compute = [&]() {
-            s16x8 bf[4];
-#pragma unroll
-            for (int ni = 0; ni < 4; ++ni)
-                bf[ni] = s16x8{blo[ni].x, blo[ni].y, blo[ni].z, blo[ni].w, bhi[ni].x, bhi[ni].y, bhi[ni].z, bhi[ni].w};
-#pragma unroll
-            for (int mi = 0; mi < 8; ++mi)
-#pragma unroll
-                for (int ni = 0; ni < 4; ++ni) acc[mi][ni] = mfma16<IS_BF16>(af[mi], bf[ni], acc[mi][ni]);
-            __builtin_amdgcn_sched_barrier(0);
-        };
-        // the ping-pong main loop of gemm_dma256_kernel, over K-steps kb .. ke-1 of this tile
-        dma_tile(0);
-        dma_tile(1);
-        dma_tile(2);
-        if (__builtin_amdgcn_readfirstlane(wave) < 4) {
-            dma_tile(3);
-            asm volatile("s_waitcnt vmcnt(12)" ::: "memory");
-            __builtin_amdgcn_s_barrier();
-            read_all(0);
-            for (int64_t kt = 0; kt < ksteps; ++kt) {
-                wait_reads();
-                compute();
-                asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-                __builtin_amdgcn_s_barrier();
-                read_all(kt + 1);
-                dma_tile(kt + 4);
-                __builtin_amdgcn_sched_barrier(0);
-            }
-        } else {
-            asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-            __builtin_amdgcn_s_barrier();
-            for (int64_t kt = 0; kt < ksteps; ++kt) {
-                read_all(kt);
-                dma_tile(kt + 3);
-                wait_reads();
-                asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-                __builtin_amdgcn_s_barrier();
-                compute();
-            }
-        }
-        asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)"
-                     : "+v"(blo[0]), "+v"(blo[1]), "+v"(blo[2]), "+v"(blo[3]), "+v"(bhi[0]), "+v"(bhi[1]), "+v"(bhi[2]),
-                       "+v"(bhi[3]), "+v"(af[0]), "+v"(af[1]), "+v"(af[2]), "+v"(af[3]), "+v"(af[4]), "+v"(af[5]),
-                       "+v"(af[6]), "+v"(af[7])
-                     :
-                     : "memory");
-        __syncthreads();  // every DMA landed, every fragment read: the stages are free (epilogue staging, next piece)
+        gemm256_main_loop<IS_BF16>(acc, smem, A, Bm, At, Bt, M, N, lda, ldb, Kmain, m0, n0, kb, ke - kb, tid);
 
         int mi_lo = 0, mi_hi = 8;   // the 16-row blocks of every wave's 128 rows this workgroup stores
         if (is_tail) {
@@ -938,47 +845,7 @@ __global__ __launch_bounds__(512, 2) void gemm_sk256_kernel(const uint16_t* __re
                     for (int j = 0; j < 4; ++j) acc[i][j] = f32x4{bad, bad, bad, bad};
             }
         }
-        // the epilogue of gemm_dma256_kernel
-        const int pr = lane >> 3, pc = (lane & 7) * 8;
-        float* ctile = reinterpret_cast<float*>(smem) + wave * (EPI2_ROWS * CS);
-        const bool pre_ok = vec_c && addend != nullptr && m0 + BM2 <= M && n0 + BN2 <= N;
-        u32x4 pre[16];
-        if (pre_ok) {
-            const T* ap = addend + (m0 + wr * 128 + pr) * ldadd + n0 + wc * 64 + pc;
-#pragma unroll
-            for (int i = 0; i < 16; ++i) pre[i] = *reinterpret_cast<const u32x4*>(ap + (int64_t)i * 8 * ldadd);
-        }
-#pragma unroll
-        for (int c = 0; c < 128 / EPI2_ROWS; ++c) {
-#pragma unroll
-            for (int h = 0; h < 2; ++h)
-#pragma unroll
-                for (int ni = 0; ni < 4; ++ni)
-#pragma unroll
-                    for (int r = 0; r < 4; ++r)
-                        ctile[(h * 16 + (lane >> 4) * 4 + r) * CS + ni * 16 + (lane & 15)] = acc[c * 2 + h][ni][r];
-            __builtin_amdgcn_wave_barrier();
-#pragma unroll
-            for (int pass = 0; pass < EPI2_ROWS / 8; ++pass) {
-                if (c * 2 + pass / 2 < mi_lo || c * 2 + pass / 2 >= mi_hi) continue;
-                const int rr = pass * 8 + pr;
-                float f[8];
-                const f32x4 lo = *reinterpret_cast<const f32x4*>(&ctile[rr * CS + pc]);
-                const f32x4 hi = *reinterpret_cast<const f32x4*>(&ctile[rr * CS + pc + 4]);
-                f[0] = lo[0]; f[1] = lo[1]; f[2] = lo[2]; f[3] = lo[3]; f[4] = hi[0]; f[5] = hi[1]; f[6] = hi[2]; f[7] = hi[3];
-                const int64_t row = m0 + wr * 128 + c * EPI2_ROWS + rr, col = n0 + wc * 64 + pc;
-                if (pre_ok) {
-                    float g[8];
-                    Elem<T>::unpack(pre[c * 4 + pass], g);
-#pragma unroll
-                    for (int i = 0; i < 8; ++i) f[i] += g[i];
-                    *reinterpret_cast<u32x4*>(C + row * N + col) = Elem<T>::pack(f);
-                } else {
-                    epi_store8<T>(C, addend, row, col, M, N, f, vec_c, half_c, ldadd);
-                }
-            }
-            __builtin_amdgcn_wave_barrier();
-        }
+        gemm256_epilogue<T>(acc, smem, C, addend, M, N, ldadd, m0, n0, tid, vec_c, half_c, mi_lo, mi_hi);
         __syncthreads();  // the staging rows of every wave are read: the next piece's DMA may overwrite them
     }
 }

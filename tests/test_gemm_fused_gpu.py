@@ -84,7 +84,8 @@ def test_addmm_big_tiles(gnnops, M, N, K, dname):
 
 @pytest.mark.parametrize("dname", ["bf16", "f16"])
 @pytest.mark.parametrize("M,N,K", [(4352, 4352, 192), (4352, 4096, 264), (4864, 4864, 128), (4249, 4249, 263),
-                                   (4100, 4600, 320), (4352, 4352, 2048), (512, 37000, 320), (37000, 512, 328)])
+                                   (4100, 4600, 320), (4352, 4352, 2048), (512, 37000, 320), (37000, 512, 328),
+                                   (4352, 4352, 64), (4352, 4096, 128)])  # fewer K-steps than pieces: 2 of 4, 4 of 8
 def test_addmm_split_k_tail(gnnops, M, N, K, dname):
     """More than one round of 256 x 256 tiles on the 256 CUs with a last round of at most half a round: the persistent kernel
     (gemm_sk256_kernel) cuts the last round's tiles along K into 8 / 4 / 2 pieces (272 tiles: 16 left, 289: 33, 361: 105;
