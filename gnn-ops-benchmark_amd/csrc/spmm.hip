@@ -146,6 +146,134 @@ __global__ __launch_bounds__(256) void spmm_widerows_kernel(const int32_t* __res
     }
 }
 
+// ---- tiled form: the rows of `mat` that a block of consecutive output rows shares are staged in LDS once ----
+// A plan (include/gnnops.h, "Tiled SpMM plan"; built by gnnops.spmm_tiles) names, per block of R = 1 << rshift output rows,
+// up to `slots` columns that at least two nonzeros of the block reference, and gives every nonzero its column's slot or
+// 0xFFFF. A workgroup takes (row block, 128-byte column chunk): it copies the chunk of each staged row of `mat` into its
+// LDS slot (16-byte loads, all of a thread's in flight together, then 16-byte LDS stores), and after one barrier runs the
+// row loop of spmm_rows_kernel with 8 lanes per row: an operand row comes from LDS when the nonzero has a slot and from
+// global memory otherwise. Products, their order and the single rounding are those of spmm_rows_kernel, so the bits are too.
+//
+// LDS image: slot s at byte 128 * s, lane gl's 16 bytes at 16 * gl — lane-linear, what the staging loop writes. A
+// ds_read_b128 is served in 16-lane groups that take lanes 0-3 of two rows and lanes 4-7 of two others: two slots of equal
+// parity sit on the same half of the 256-byte bank row, so such a pair reads 2-way. The slots are the data's, no swizzle of
+// the image removes that; a 256-byte pitch would (one slot = one bank row) at half the staged columns per workgroup.
+constexpr int TILE_THREADS = 1024;  // 16 waves on the CU beside up to 160 KiB of LDS: one workgroup per CU hides its own latency
+constexpr int TILE_LANES = 8;       // lanes per row = 16-byte pieces per 128-byte chunk
+constexpr int TILE_STAGE = 8;       // staging loads in flight per thread: 1024 slots x 8 pieces in one sweep
+constexpr int TILE_SLOT_BYTES = TILE_LANES * 16;
+constexpr int TILE_LDS_BYTES = 160 * 1024;
+constexpr int TILE_NONE = 0xFFFF;
+
+template <typename T>
+__global__ __launch_bounds__(TILE_THREADS) void spmm_tiled_kernel(const int32_t* __restrict__ rowptr,
+                                                                  const int64_t* __restrict__ col,
+                                                                  const uint16_t* __restrict__ slot,
+                                                                  const T* __restrict__ value, const T* __restrict__ mat,
+                                                                  T* __restrict__ out, const int32_t* __restrict__ tile_ptr,
+                                                                  const int64_t* __restrict__ tile_cols, int64_t M, int64_t D,
+                                                                  int rshift, int kchunks) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char tile_raw[];
+    u32x4* tile = reinterpret_cast<u32x4*>(tile_raw);  // [slot][TILE_LANES]
+    constexpr int VEC = Elem<T>::VEC;
+    // neighbouring row blocks stage overlapping columns: keep them on one XCD's L2; the chunks of one block share its CSR arrays
+    const int64_t item = xcd_contiguous(blockIdx.x, gridDim.x);
+    const int64_t b = item / kchunks;
+    const int chunk = (int)(item - b * kchunks);
+    const int tid = threadIdx.x;
+    const int gl = tid & (TILE_LANES - 1);
+    const int64_t c0 = ((int64_t)chunk * TILE_LANES + gl) * VEC;
+    const bool live = c0 < D;  // ragged last chunk: lanes past the row neither stage nor compute
+    const int32_t t0 = tile_ptr[b];
+    const int pieces = (tile_ptr[b + 1] - t0) * TILE_LANES;
+    for (int base = 0; base < pieces; base += TILE_THREADS * TILE_STAGE) {
+        int64_t c[TILE_STAGE];
+        u32x4 piece[TILE_STAGE];
+#pragma unroll
+        for (int u = 0; u < TILE_STAGE; ++u) {  // piece p = (slot p / 8, lane p % 8), and p % 8 == gl for every p this thread takes
+            const int p = base + u * TILE_THREADS + tid;
+            c[u] = (live && p < pieces) ? tile_cols[t0 + (p >> 3)] : -1;
+        }
+#pragma unroll
+        for (int u = 0; u < TILE_STAGE; ++u)
+            if (c[u] >= 0) piece[u] = load16<false>(mat + c[u] * D + c0);
+#pragma unroll
+        for (int u = 0; u < TILE_STAGE; ++u)
+            if (c[u] >= 0) tile[base + u * TILE_THREADS + tid] = piece[u];
+    }
+    __syncthreads();
+    if (!live) return;
+    const int64_t r0 = b << rshift;
+    const int nrows = (int)((M - r0) < ((int64_t)1 << rshift) ? (M - r0) : ((int64_t)1 << rshift));
+    for (int r = tid / TILE_LANES; r < nrows; r += TILE_THREADS / TILE_LANES) {
+        const int64_t i = r0 + r;
+        const int32_t beg = rowptr[i], end = rowptr[i + 1];
+        float acc[VEC];
+#pragma unroll
+        for (int v = 0; v < VEC; ++v) acc[v] = 0.f;
+        for (int32_t j = beg; j < end; j += U) {
+            int sl[U];  // -1: past the row's end; TILE_NONE: not staged; else the LDS slot
+            int64_t c[U];
+            T wraw[U];
+            u32x4 rows[U];
+            // as in spmm_rows_kernel, each phase has all its loads in flight together: (slot, value) pairs, then the column
+            // ids of the unstaged nonzeros only, then the operand rows from LDS or global memory
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                sl[u] = -1;
+                if (j + u < end) {
+                    sl[u] = slot[j + u];
+                    if (value) wraw[u] = value[j + u];
+                }
+            }
+#pragma unroll
+            for (int u = 0; u < U; ++u)
+                if (sl[u] == TILE_NONE) c[u] = col[j + u];
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                if (sl[u] == TILE_NONE)
+                    rows[u] = load16<false>(mat + c[u] * D + c0);
+                else if (sl[u] >= 0)
+                    rows[u] = tile[sl[u] * TILE_LANES + gl];
+            }
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                if (sl[u] >= 0) {
+                    float f[VEC];
+                    Elem<T>::unpack(rows[u], f);
+                    const float w = value ? Elem<T>::load(&wraw[u]) : 1.f;
+#pragma unroll
+                    for (int v = 0; v < VEC; ++v) acc[v] = __fadd_rn(acc[v], __fmul_rn(w, f[v]));
+                }
+            }
+        }
+        store16<true>(out + i * D + c0, Elem<T>::pack(acc));
+    }
+}
+
+template <typename T>
+int launch_tiled(const int32_t* rowptr, const int64_t* col, const void* value, const void* mat, void* out, int64_t M, int64_t D,
+                 const int32_t* tile_ptr, const int64_t* tile_cols, const uint16_t* slot, int rshift, int slots,
+                 hipStream_t stream) {
+    constexpr int VEC = Elem<T>::VEC;
+    GNNOPS_REQUIRE(D % VEC == 0 && (uintptr_t)mat % 16 == 0 && (uintptr_t)out % 16 == 0, GNNOPS_EINVAL,
+                   "spmm_tiled: D must be a multiple of %d and mat / out 16-byte aligned (use gnnops_spmm otherwise)", VEC);
+    const int kchunks = (int)gnnops_cdiv(D / VEC, TILE_LANES);
+    const int64_t nblocks = gnnops_cdiv(M, (int64_t)1 << rshift);
+    GNNOPS_REQUIRE(nblocks * kchunks < ((int64_t)1 << 31), GNNOPS_EUNSUPPORTED, "spmm_tiled: too many (row block, chunk) items");
+    static bool configured = false;
+    if (!configured) {
+        if (hipFuncSetAttribute(reinterpret_cast<const void*>(&spmm_tiled_kernel<T>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                TILE_LDS_BYTES) != hipSuccess)
+            return gnnops_check_launch("spmm_tiled attribute");
+        configured = true;
+    }
+    hipLaunchKernelGGL((spmm_tiled_kernel<T>), dim3((unsigned)(nblocks * kchunks)), dim3(TILE_THREADS),
+                       (size_t)slots * TILE_SLOT_BYTES, stream, rowptr, col, slot, (const T*)value, (const T*)mat, (T*)out,
+                       tile_ptr, tile_cols, M, D, rshift, kchunks);
+    return gnnops_check_launch("spmm_tiled");
+}
+
 // CSR materialisation of a plan-ordered COO operand: out[j] = in[perm[j]] for the column ids (8 B) or the values.
 template <typename U>
 __global__ void permute_kernel(const U* __restrict__ in, const int32_t* __restrict__ perm, U* __restrict__ out, int64_t n) {
@@ -222,6 +350,31 @@ extern "C" int gnnops_spmm_hubs(const int32_t* rowptr, const int32_t* perm, cons
         case GNNOPS_BF16: return launch<__hip_bfloat16>(rowptr, perm, col, value, mat, out, M, D, mat_rows, stream, nnz, hub_workspace, hub_workspace_bytes);
     }
     gnnops_set_error("spmm: unknown dtype %d", dtype);
+    return GNNOPS_EINVAL;
+}
+
+// CSR x dense through a tile plan (include/gnnops.h): bit-identical to gnnops_spmm(rowptr, NULL, col, ...).
+extern "C" int gnnops_spmm_tiled(const int32_t* rowptr, const int64_t* col, const void* value, const void* mat, void* out,
+                                 int64_t M, int64_t D, int64_t nnz, int dtype, const int32_t* tile_ptr, const int64_t* tile_cols,
+                                 const uint16_t* slot, int block_rows, int slots, gnnops_stream_t s) {
+    hipStream_t stream = (hipStream_t)s;
+    GNNOPS_REQUIRE(M >= 0 && D >= 0 && nnz >= 0, GNNOPS_EINVAL, "spmm_tiled: negative size");
+    GNNOPS_REQUIRE(nnz < ((int64_t)1 << 31), GNNOPS_EUNSUPPORTED, "spmm_tiled: nnz must be < 2^31");
+    GNNOPS_REQUIRE(block_rows >= 1 && (block_rows & (block_rows - 1)) == 0, GNNOPS_EINVAL,
+                   "spmm_tiled: block_rows %d is not a power of two", block_rows);
+    GNNOPS_REQUIRE(slots >= 1 && slots <= TILE_LDS_BYTES / TILE_SLOT_BYTES, GNNOPS_EINVAL,
+                   "spmm_tiled: slots %d outside [1, %d] (%d bytes of LDS each)", slots, TILE_LDS_BYTES / TILE_SLOT_BYTES,
+                   TILE_SLOT_BYTES);
+    if (M * D == 0) return GNNOPS_OK;
+    GNNOPS_REQUIRE(rowptr && out && tile_ptr && (nnz == 0 || (col && mat && slot)), GNNOPS_EINVAL, "spmm_tiled: null pointer");
+    int rshift = 0;
+    while ((1 << rshift) < block_rows) ++rshift;
+    switch (dtype) {
+        case GNNOPS_F32: return launch_tiled<float>(rowptr, col, value, mat, out, M, D, tile_ptr, tile_cols, slot, rshift, slots, stream);
+        case GNNOPS_F16: return launch_tiled<__half>(rowptr, col, value, mat, out, M, D, tile_ptr, tile_cols, slot, rshift, slots, stream);
+        case GNNOPS_BF16: return launch_tiled<__hip_bfloat16>(rowptr, col, value, mat, out, M, D, tile_ptr, tile_cols, slot, rshift, slots, stream);
+    }
+    gnnops_set_error("spmm_tiled: unknown dtype %d", dtype);
     return GNNOPS_EINVAL;
 }
 

@@ -91,18 +91,142 @@ def sddmm(rows_a, rows_b, a, b):
     return out
 
 
-def spmm_csr(rowptr, col, value, matrix):
-    """CSR x dense (BASELINE config 3's layout): rowptr int32/int64 [M+1], col int64 [nnz], value [nnz] or None."""
+def spmm_csr(rowptr, col, value, matrix, tiles=None):
+    """CSR x dense (BASELINE config 3's layout): rowptr int32/int64 [M+1], col int64 [nnz], value [nnz] or None.
+
+    ``tiles``: a plan from :func:`spmm_tiles` for these very ``rowptr`` and ``col`` tensors. The product then runs the tiled
+    kernel, which stages the rows of ``matrix`` that a block of output rows shares in LDS; when the row length of
+    ``matrix`` is not a multiple of 16 bytes (or ``matrix`` is not 16-byte aligned) the call falls through to the untiled
+    kernels. Either way the result is identical bit for bit to the call without ``tiles``: same products, same order."""
     if _needs_grad(value, matrix):
         raise NotImplementedError("gnnops.spmm_csr has no backward: use gnnops.spmm (COO) inside a training graph, or detach")
     _require_gpu(rowptr, col, value, matrix)
     _check_index(col, "spmm_csr")
+    if tiles is not None:
+        tiles._check(rowptr, col)
     if rowptr.dtype == torch.int64:
         rowptr = rowptr.to(torch.int32)  # kernel ABI is int32 row pointers (nnz < 2^31)
     elif rowptr.dtype != torch.int32:
         raise RuntimeError("spmm_csr: rowptr must be int32 or int64")
     dt = _dtype_code(matrix, "spmm_csr")
-    return _spmm_launch(rowptr.contiguous(), None, col.contiguous(), value, matrix.contiguous(), rowptr.numel() - 1, dt)
+    rowptr, col, matrix = rowptr.contiguous(), col.contiguous(), matrix.contiguous()
+    if tiles is not None and matrix.dim() == 2:
+        if value is not None and value.dtype != matrix.dtype:
+            raise RuntimeError("spmm_csr: value and matrix must have the same dtype")
+        m, D = rowptr.numel() - 1, matrix.size(1)
+        out = torch.empty((m, D), dtype=matrix.dtype, device=matrix.device)
+        if (D * matrix.element_size()) % 16 == 0 and matrix.data_ptr() % 16 == 0 and out.data_ptr() % 16 == 0:
+            value_c = value.contiguous() if value is not None else None
+            with _on(matrix.device):
+                rc = _lib.load().gnnops_spmm_tiled(rowptr.data_ptr(), col.data_ptr(),
+                                                   value_c.data_ptr() if value_c is not None else None, matrix.data_ptr(),
+                                                   out.data_ptr(), m, D, col.numel(), dt, tiles.tile_ptr.data_ptr(),
+                                                   tiles.tile_cols.data_ptr(), tiles.slot.data_ptr(), tiles.block_rows,
+                                                   tiles.slots, _stream())
+            check(rc, "spmm_tiled")
+            return out
+    return _spmm_launch(rowptr, None, col, value, matrix, rowptr.numel() - 1, dt)
+
+
+_T_HUB = 8192           # hub::T_HUB of csrc/hub.h: longer rows belong to the hub path of the untiled kernels
+_TILE_SLOT_BYTES = 128  # one slot = one 128-byte column chunk of a row of the dense operand (csrc/spmm.hip)
+_TILE_LDS_BYTES = 160 * 1024
+
+
+class SpmmTiles:
+    """Tile plan of a CSR matrix for ``spmm_csr(..., tiles=plan)``; built by :func:`spmm_tiles`, layout in include/gnnops.h.
+
+    ``tile_ptr`` int32 [nblocks+1], ``tile_cols`` int64 (staged column ids, ascending within each block), ``slot`` int16
+    [nnz] holding the 16-bit slot of each nonzero (0xFFFF, i.e. -1, when its column is not staged). ``staged_share`` is the
+    fraction of nonzeros with a slot."""
+
+    __slots__ = ("tile_ptr", "tile_cols", "slot", "block_rows", "slots", "M", "nnz", "staged_share", "_src", "__weakref__")
+
+    def _check(self, rowptr, col):
+        ref_r, ver_r, ref_c, ver_c = self._src
+        if ref_r() is not rowptr or ref_c() is not col:
+            raise RuntimeError("spmm_csr: tiles were built from other rowptr / col tensors; build a plan with gnnops.spmm_tiles(rowptr, col)")
+        from .ops import _version_of
+
+        if _version_of(rowptr) != ver_r or _version_of(col) != ver_c:
+            raise RuntimeError("spmm_csr: rowptr or col was modified in place after the tiles were built; rebuild the plan")
+        if rowptr.numel() - 1 != self.M or col.numel() != self.nnz:
+            raise RuntimeError(f"spmm_csr: tiles were built for M={self.M}, nnz={self.nnz}")
+
+
+def spmm_tiles(rowptr, col, block_rows=None, slots=None):
+    """Analyse a CSR matrix once for the tiled ``spmm_csr``: per block of ``block_rows`` consecutive rows (a power of two,
+    default 256), the up to ``slots`` (default 1024, at most 1280) most-referenced columns among those that at least two
+    nonzeros of the block reference (ties to the smaller id) are staged in LDS by the kernel; every nonzero learns its
+    column's slot. Built on the GPU with torch ops (one-time plumbing; synchronises). The plan is tied to these ``rowptr``
+    and ``col`` tensor objects and their version counters; tensors created under torch.inference_mode() have no counter,
+    for them only the identity is checked. Raises ValueError if a row has more than 8192 nonzeros (use the untiled call:
+    its hub path handles those)."""
+    import weakref
+
+    from .ops import _version_of
+
+    _require_gpu(rowptr, col)
+    _check_index(col, "spmm_tiles")
+    if rowptr.dtype not in (torch.int32, torch.int64) or rowptr.dim() != 1 or rowptr.numel() < 1 or col.dim() != 1:
+        raise RuntimeError("spmm_tiles: rowptr must be int32 or int64 [M+1] and col int64 [nnz]")
+    R = 256 if block_rows is None else int(block_rows)
+    S = 1024 if slots is None else int(slots)
+    if R < 1 or R & (R - 1):
+        raise ValueError(f"spmm_tiles: block_rows={R} is not a power of two")
+    if not 1 <= S <= _TILE_LDS_BYTES // _TILE_SLOT_BYTES:
+        raise ValueError(f"spmm_tiles: slots={S} outside [1, {_TILE_LDS_BYTES // _TILE_SLOT_BYTES}] ({_TILE_SLOT_BYTES} bytes of LDS per slot)")
+    dev = col.device
+    M, nnz = rowptr.numel() - 1, col.numel()
+    if nnz >= 1 << 31:
+        raise NotImplementedError("gnnops.spmm_tiles: nnz must be < 2^31")
+    nblocks = (M + R - 1) // R
+    t = SpmmTiles()
+    t.block_rows, t.slots, t.M, t.nnz = R, S, M, nnz
+    t._src = (weakref.ref(rowptr), _version_of(rowptr), weakref.ref(col), _version_of(col))
+    with _on(dev):
+        rp = rowptr.to(torch.int64)
+        deg = rp[1:] - rp[:-1]
+        if M and nnz and int(deg.max()) > _T_HUB:
+            raise ValueError(f"spmm_tiles: a row has more than {_T_HUB} nonzeros; such matrices belong to the hub path of spmm_csr (tiles=None)")
+        if nnz == 0 or M == 0:
+            t.tile_ptr = torch.zeros(nblocks + 1, dtype=torch.int32, device=dev)
+            t.tile_cols = torch.empty(0, dtype=torch.int64, device=dev)
+            t.slot = torch.empty(0, dtype=torch.int16, device=dev)
+            t.staged_share = 0.0
+            return t
+        lo, hi = int(col.min()), int(col.max())
+        if lo < 0 or nblocks * (hi + 1) >= 1 << 62:
+            raise ValueError("spmm_tiles: column ids must be non-negative and nblocks * (max column + 1) < 2^62")
+        n = hi + 1
+        blk = torch.repeat_interleave(torch.arange(M, device=dev) // R, deg, output_size=nnz)
+        key = blk * n + col                                              # (block, column) of every nonzero
+        ukey, counts = torch.unique(key, return_counts=True)             # ascending in (block, column)
+        cand = counts >= 2
+        ckey, ccnt = ukey[cand], counts[cand]
+        del ukey, counts, cand
+        cblk = ckey // n
+        # rank inside the block by (references descending, column ascending): a stable sort of the (block, column)-ordered
+        # candidates on (block, -references)
+        cmax = int(ccnt.max()) if ckey.numel() else 0
+        order = torch.sort(cblk * (cmax + 1) + (cmax - ccnt), stable=True).indices
+        start = torch.zeros(nblocks + 1, dtype=torch.int64, device=dev)
+        start[1:] = torch.bincount(cblk, minlength=nblocks).cumsum(0)
+        sblk = cblk[order]
+        keep = torch.arange(order.numel(), device=dev) - start[sblk] < S
+        skey = torch.sort(ckey[order][keep]).values                       # staged (block, column), ascending: the slot order
+        tile_ptr = torch.zeros(nblocks + 1, dtype=torch.int64, device=dev)
+        tile_ptr[1:] = torch.bincount(skey // n, minlength=nblocks).cumsum(0)
+        if skey.numel():
+            pos = torch.searchsorted(skey, key).clamp_(max=skey.numel() - 1)
+            slot = torch.where(skey[pos] == key, pos - tile_ptr[blk], torch.full_like(pos, -1))
+        else:
+            slot = torch.full_like(key, -1)
+        t.tile_ptr = tile_ptr.to(torch.int32)
+        t.tile_cols = skey % n
+        t.slot = slot.to(torch.int16)
+        t.staged_share = float((slot >= 0).sum()) / nnz
+    return t
 
 
 def _permute(t, perm, n):

@@ -258,6 +258,29 @@ int gnnops_spmm_hubs(const int32_t* rowptr, const int32_t* perm, const int64_t* 
                      const void* mat, void* out, int64_t M, int64_t D, int64_t nnz, int64_t mat_rows, int dtype,
                      void* hub_workspace, size_t hub_workspace_bytes, gnnops_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Tiled SpMM: CSR x dense with the rows of `mat` that a block of output rows shares staged in LDS once per block.
+ * Same products in the same order as gnnops_spmm(rowptr, NULL, col, ...): the result is bit-identical; what changes is
+ * where an operand row is fetched from. Pays on matrices whose neighbouring rows share columns (communities, bands).
+ *
+ * Tiled SpMM plan (what gnnops.spmm_tiles builds; any caller may build one), for R = block_rows (a power of two) and
+ * S = slots (1 .. 1280: a slot holds one 128-byte column chunk of a row of `mat`, S * 128 bytes of LDS per workgroup):
+ *   row block b     = rows [b * R, min((b + 1) * R, M)),  nblocks = ceil(M / R)
+ *   candidate of b  = a column that at least 2 nonzeros of the block reference (repeats inside one row count)
+ *   staged by b     = its S most-referenced candidates, ties to the smaller column id
+ *   tile_ptr  int32 [nblocks + 1]   tile_cols[tile_ptr[b] .. tile_ptr[b + 1]) are block b's staged columns
+ *   tile_cols int64 [tile_ptr[nblocks]]  staged column ids, ascending within each block
+ *   slot      uint16 [nnz]          position of the nonzero's column in its block's staged list, or 0xFFFF if not staged
+ * The kernel needs only: tile_ptr[b + 1] - tile_ptr[b] <= S, and slot[e] == 0xFFFF or
+ * tile_cols[tile_ptr[b] + slot[e]] == col[e] for every nonzero e of block b. `col` is read for unstaged nonzeros only.
+ * No row may hold more than 8192 nonzeros (those belong to gnnops_spmm_hubs). Preconditions, else GNNOPS_EINVAL:
+ * D a multiple of 16 bytes / element size, mat and out 16-byte aligned. value == NULL means all ones.
+ * Allocates nothing and does not synchronise; one launch on `stream`.
+ * ------------------------------------------------------------------------------------------- */
+int gnnops_spmm_tiled(const int32_t* rowptr, const int64_t* col, const void* value, const void* mat, void* out,
+                      int64_t M, int64_t D, int64_t nnz, int dtype, const int32_t* tile_ptr, const int64_t* tile_cols,
+                      const uint16_t* slot, int block_rows, int slots, gnnops_stream_t stream);
+
 /* out[j] = in[perm[j]] (elements of 2, 4 or 8 bytes): materialises the CSR column / value arrays of a plan-ordered COO
  * operand once, so gnnops_spmm can be called with perm == NULL and stream them. */
 int gnnops_permute(const void* in, const int32_t* perm, void* out, int64_t n, int elem_bytes, gnnops_stream_t stream);
