@@ -322,10 +322,11 @@ def spspmm(indexA, valueA, indexB, valueB, m, k, n, coalesced=False):
             raise NotImplementedError(f"gnnops.spspmm: {P} partial products exceed the 2^32 limit")
         ex_index = torch.empty((2, P), dtype=torch.int64, device=dev)
         ex_value = torch.empty(P, dtype=valueA.dtype, device=dev)
-        check(L.gnnops_spspmm_expand(rowA.data_ptr(), colA.data_ptr(), valueA.data_ptr(), nnzA, planB.rowptr.data_ptr(),
-                                     planB.perm.data_ptr(), colB.data_ptr(), valueB.data_ptr(), ex_index[0].data_ptr(),
-                                     ex_index[1].data_ptr(), ex_value.data_ptr(), dt, ws.data_ptr(), _stream()),
-              "spspmm_expand")
+        if P:  # no products (every column of A meets an empty row of B): the empty outputs have no address to pass
+            check(L.gnnops_spspmm_expand(rowA.data_ptr(), colA.data_ptr(), valueA.data_ptr(), nnzA, planB.rowptr.data_ptr(),
+                                         planB.perm.data_ptr(), colB.data_ptr(), valueB.data_ptr(), ex_index[0].data_ptr(),
+                                         ex_index[1].data_ptr(), ex_value.data_ptr(), dt, ws.data_ptr(), _stream()),
+                  "spspmm_expand")
     return coalesce(ex_index, ex_value, m, n)
 
 

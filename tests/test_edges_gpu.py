@@ -138,7 +138,8 @@ def test_skewed_and_maximal_degree(gnnops, oracle):
                       oracle.scatter(src[:8000].numpy(), few_idx.numpy(), 0, dim_size=5), "8000 rows -> one destination")
     mx, arg = gnnops.scatter_max(src.cuda(), idx.cuda(), 0, dim_size=5)
     emx, earg = oracle.scatter(src.numpy(), idx.numpy(), 0, dim_size=5, reduce="max")
-    assert_bits_equal(mx.cpu().numpy(), emx, "max") and assert_bits_equal(arg.cpu().numpy(), earg, "argmax")
+    assert_bits_equal(mx.cpu().numpy(), emx, "max")
+    assert_bits_equal(arg.cpu().numpy(), earg, "argmax")
     few = torch.rand(10, 16, generator=g)
     far = torch.tensor([0, 2_999_999, 17, 17, 2_000_000, 5, 5, 5, 1_000_000, 0])
     got = gnnops.scatter_add(few.cuda(), far.cuda(), 0)              # dim_size discovered: 3,000,000 rows, 6 non-empty
@@ -181,7 +182,8 @@ def test_less_travelled_shapes(gnnops, oracle):
     val = torch.rand(400, 3, generator=g)
     ci, cv = gnnops.coalesce(coo.cuda(), val.cuda(), 30, 20)
     ei, ev = oracle.coalesce(coo.numpy(), val.numpy(), 30, 20)
-    assert_bits_equal(ci.cpu().numpy(), ei, "coalesce index") and assert_bits_equal(cv.cpu().numpy(), ev, "coalesce [nnz, 3] values")
+    assert_bits_equal(ci.cpu().numpy(), ei, "coalesce index")
+    assert_bits_equal(cv.cpu().numpy(), ev, "coalesce [nnz, 3] values")
     vec = torch.rand(20, generator=g)
     v1 = torch.rand(400, generator=g)
     got = gnnops.spmm(coo.cuda(), v1.cuda(), 30, 20, vec.cuda())
