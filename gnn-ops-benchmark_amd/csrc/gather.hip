@@ -297,12 +297,9 @@ __global__ __launch_bounds__(SK1_THREADS) void select_k1_kernel(const U* __restr
 }
 
 template <typename U>
-int launch_select_k1(const void* in, const int64_t* index, void* out, int64_t B, int64_t N, int64_t E, hipStream_t stream) {
-    int tb = (int)(SK1_LDS_TARGET / ((size_t)N * sizeof(U)));
-    if (tb < 1) tb = 1;
-    if (tb > SK1_MAX_TB) tb = SK1_MAX_TB;
-    if (tb > B) tb = (int)B;
-    hipLaunchKernelGGL((select_k1_kernel<U>), dim3((unsigned)gnnops_cdiv(B, tb)), dim3(SK1_THREADS), (size_t)tb * N * sizeof(U),
+int launch_select_k1(const void* in, const int64_t* index, void* out, int64_t B, int64_t N, int64_t E, int tb, int grid,
+                     hipStream_t stream) {
+    hipLaunchKernelGGL((select_k1_kernel<U>), dim3((unsigned)grid), dim3(SK1_THREADS), (size_t)tb * N * sizeof(U),
                        stream, (const U*)in, index, (U*)out, B, N, E, tb);
     return gnnops_check_launch("index_select");
 }
@@ -323,9 +320,22 @@ inline int gather_lds_width(int64_t N, int64_t K, int64_t E, int elem_bytes, int
     return (int)tc;
 }
 
+// strips, thread count and column shift of a launch with strips of tc columns: detail[] of the LDS route
+inline void gather_lds_geom(int64_t N, int64_t K, int elem_bytes, int tc, int* d) {
+    int tshift = 0;
+    while ((1 << tshift) < tc) ++tshift;
+    const size_t lds = (size_t)N * tc * elem_bytes;
+    d[0] = tc;
+    // smaller workgroups when several fit a CU: their stage / gather phases overlap
+    d[1] = lds > 80 * 1024 ? GL_THREADS : lds > 40 * 1024 ? 512 : 256;
+    d[2] = (int)gnnops_cdiv(K, tc);
+    d[3] = tshift;
+}
+
 template <typename U, bool FULL_INDEX>
-int launch_gather_lds(const void* in, const int64_t* index, void* out, int64_t B, int64_t N, int64_t K, int64_t E, int tc,
-                      hipStream_t stream) {
+int launch_gather_lds(const void* in, const int64_t* index, void* out, int64_t B, int64_t N, int64_t K, int64_t E,
+                      const int* geom, hipStream_t stream) {
+    const int tc = geom[0], threads = geom[1], strips = geom[2], tshift = geom[3];   // gather_lds_geom
     static bool configured = false;
     if (!configured) {
         if (hipFuncSetAttribute(reinterpret_cast<const void*>(&gather_lds_kernel<U, FULL_INDEX>),
@@ -333,12 +343,7 @@ int launch_gather_lds(const void* in, const int64_t* index, void* out, int64_t B
             return gnnops_check_launch("gather_lds attribute");
         configured = true;
     }
-    const int strips = (int)gnnops_cdiv(K, tc);
-    int tshift = 0;
-    while ((1 << tshift) < tc) ++tshift;
     const size_t lds = (size_t)N * tc * sizeof(U);
-    // smaller workgroups when several fit a CU: their stage / gather phases overlap
-    const int threads = lds > 80 * 1024 ? GL_THREADS : lds > 40 * 1024 ? 512 : 256;
     hipLaunchKernelGGL((gather_lds_kernel<U, FULL_INDEX>), dim3((unsigned)(B * strips)), dim3(threads), lds, stream,
                        (const U*)in, index, (U*)out, B, N, K, E, tc, strips, tshift);
     return gnnops_check_launch("gather_lds");
@@ -581,16 +586,16 @@ constexpr int64_t LONGROW_MIN_UNITS = 512;  // from here on a wave per row beats
 template <typename T>
 int launch_select_sum(const void* input, const int64_t* index, float* d_sum, int64_t B, int64_t N, int64_t K,
                       int64_t E, float* partial, hipStream_t stream) {
-    constexpr int VEC = Elem<T>::VEC;
+    int d[4];
+    const int dtype = std::is_same<T, float>::value ? GNNOPS_F32 : std::is_same<T, __half>::value ? GNNOPS_F16 : GNNOPS_BF16;
+    const int route = gnnops_fused_select_sum_route(B, N, K, E, dtype, (uintptr_t)input, d);
     int grid;
-    if (K % VEC == 0 && (uintptr_t)input % 16 == 0) {
-        RowGeom g = row_geom(K / VEC);
-        const int64_t items = B * g.chunks * E;
+    if (route == GNNOPS_ROUTE_ROWS) {
         // 4 rows in flight per lane group: 2 and 4 tie, 8 loses a third (register pressure) — tools/time_selsum.py
-        grid = gnnops_grid_cap(gnnops_cdiv(items, (256 >> g.gshift) * ROWS_IN_FLIGHT), FUSED_BLOCKS);
+        grid = d[3];
         hipLaunchKernelGGL((select_sum_rows_kernel<T, ROWS_IN_FLIGHT>), dim3(grid), dim3(256), 0, stream, (const T*)input,
-                           index, partial, B, N, K, E, g.gshift, g.chunks);
-    } else if (K == 1 && (size_t)N * sizeof(T) <= GL_BUDGET && E * 32 >= N * (int64_t)sizeof(T)) {
+                           index, partial, B, N, K, E, d[0], d[1]);
+    } else if (route == GNNOPS_ROUTE_LDS) {
         static bool configured = false;
         if (!configured) {
             if (hipFuncSetAttribute(reinterpret_cast<const void*>(&select_sum_lds_kernel<T>),
@@ -598,19 +603,19 @@ int launch_select_sum(const void* input, const int64_t* index, float* d_sum, int
                 return gnnops_check_launch("select_sum_lds attribute");
             configured = true;
         }
-        grid = gnnops_grid_cap(B, FUSED_BLOCKS);
-        hipLaunchKernelGGL((select_sum_lds_kernel<T>), dim3(grid), dim3(1024), (size_t)N * sizeof(T), stream, (const T*)input,
+        grid = d[2];   // d[1] is 1024: select_sum_lds_kernel strides by 1024 and sums 16 wave partials
+        hipLaunchKernelGGL((select_sum_lds_kernel<T>), dim3(grid), dim3(d[1]), (size_t)N * sizeof(T), stream, (const T*)input,
                            index, partial, B, N, E);
-    } else if (K >= LONGROW_MIN_UNITS) {
-        grid = gnnops_grid_cap(gnnops_cdiv(B * E, 4), FUSED_BLOCKS);
-        if (sizeof(T) == 2 && K % 2 == 0 && (uintptr_t)input % 4 == 0)
+    } else if (route == GNNOPS_ROUTE_LONGROWS) {
+        grid = d[2];
+        if (d[0] == 2)
             hipLaunchKernelGGL((select_sum_longrows_kernel<T, 2>), dim3(grid), dim3(256), 0, stream, (const T*)input, index,
                                partial, B, N, K, E);
         else
             hipLaunchKernelGGL((select_sum_longrows_kernel<T, 1>), dim3(grid), dim3(256), 0, stream, (const T*)input, index,
                                partial, B, N, K, E);
     } else {
-        grid = gnnops_grid_cap(gnnops_cdiv(B * E * K, 256 * 4), FUSED_BLOCKS);
+        grid = d[2];
         hipLaunchKernelGGL((select_sum_elems_kernel<T>), dim3(grid), dim3(256), 0, stream, (const T*)input, index,
                            partial, B, N, K, E);
     }
@@ -619,6 +624,119 @@ int launch_select_sum(const void* input, const int64_t* index, float* d_sum, int
 }
 
 }  // namespace
+
+// ---- route queries: every threshold of the three dispatchers below lives here (include/gnnops.h) ----
+static inline int route_done(int route, const int64_t* d, int* detail) {
+    if (detail)
+        for (int i = 0; i < 4; ++i) detail[i] = (int)(d[i] < INT32_MAX ? d[i] : INT32_MAX);
+    return route;
+}
+
+extern "C" int gnnops_index_select_route(int64_t B, int64_t N, int64_t K, int64_t E, int elem_bytes, uintptr_t input_addr,
+                                         uintptr_t out_addr, int* detail) {
+    int64_t d[4] = {0, 0, 0, 0};
+    if (B < 0 || N < 0 || K < 0 || E < 0 || B * E * K == 0 ||
+        !(elem_bytes == 1 || elem_bytes == 2 || elem_bytes == 4 || elem_bytes == 8))
+        return route_done(GNNOPS_ROUTE_NONE, d, detail);
+    const int64_t rowbytes = K * elem_bytes;
+    if (rowbytes % 16 == 0 && input_addr % 16 == 0 && out_addr % 16 == 0) {
+        const RowGeom g = row_geom(rowbytes / 16);
+        const int64_t items = B * g.chunks * E;
+        // nontemporal on both sides, 4 rows in flight per lane group, 64 workgroups per CU of grid:
+        // the fastest of the variants swept with tools/time_sel.py at config 2
+        d[0] = g.gshift;
+        d[1] = g.chunks;
+        d[2] = B == 1 && g.chunks == 1 && ((int64_t)16 << g.gshift) == rowbytes;   // `whole` of select_rows_kernel
+        d[3] = gnnops_grid_cap(gnnops_cdiv(items, (256 >> g.gshift) * ROWS_IN_FLIGHT), 256 * 64);
+        return route_done(GNNOPS_ROUTE_ROWS, d, detail);
+    }
+    // K == 1 with a batch of rows that fit 64 KiB of LDS: rows parked on chip, the index shared by TB rows
+    if (K == 1 && B > 1 && N >= 512 && E >= 256 && (size_t)N * elem_bytes <= 64 * 1024 && E * 32 >= N * elem_bytes &&
+        gnnops_cdiv(B, 1) < ((int64_t)1 << 31)) {
+        int64_t tb = (int64_t)(SK1_LDS_TARGET / ((size_t)N * elem_bytes));
+        if (tb < 1) tb = 1;
+        if (tb > SK1_MAX_TB) tb = SK1_MAX_TB;
+        if (tb > B) tb = B;
+        d[0] = tb;
+        d[1] = gnnops_cdiv(B, tb);
+        return route_done(GNNOPS_ROUTE_K1, d, detail);
+    }
+    // a row index with K > 1 is already coalesced along k in the element kernel; LDS staging pays for K == 1 rows
+    if (const int tc = gather_lds_width(N, K, E, elem_bytes, B);
+        tc > 0 && K * elem_bytes <= 8 && B * gnnops_cdiv(K, tc) < ((int64_t)1 << 31)) {
+        int g[4];
+        gather_lds_geom(N, K, elem_bytes, tc, g);
+        if (detail)
+            for (int i = 0; i < 4; ++i) detail[i] = g[i];
+        return GNNOPS_ROUTE_LDS;
+    }
+    // copy in the widest unit that divides the row and the base alignment (a row is one opaque byte string)
+    const uintptr_t al = input_addr | out_addr | (uintptr_t)rowbytes;
+    const int unit = al % 8 == 0 ? 8 : al % 4 == 0 ? 4 : al % 2 == 0 ? 2 : 1;
+    const int64_t KU = rowbytes / unit;
+    d[0] = unit;
+    d[1] = KU;
+    if (KU >= LONGROW_MIN_UNITS) {
+        d[2] = gnnops_grid_cap(gnnops_cdiv(B * E * gnnops_cdiv(KU, 512), 4), 256 * 32);
+        return route_done(GNNOPS_ROUTE_LONGROWS, d, detail);
+    }
+    d[2] = gnnops_grid_cap(gnnops_cdiv(B * E * K, 256), 256 * 32);
+    return route_done(GNNOPS_ROUTE_ELEMS, d, detail);
+}
+
+extern "C" int gnnops_gather_route(int64_t B, int64_t N, int64_t K, int64_t E, int elem_bytes, int* detail) {
+    int64_t d[4] = {0, 0, 0, 0};
+    if (B < 0 || N < 0 || K < 0 || E < 0 || B * E * K == 0 ||
+        !(elem_bytes == 1 || elem_bytes == 2 || elem_bytes == 4 || elem_bytes == 8))
+        return route_done(GNNOPS_ROUTE_NONE, d, detail);
+    const int tc = gather_lds_width(N, K, E, elem_bytes, B);
+    if (tc > 0 && B * gnnops_cdiv(K, tc) < ((int64_t)1 << 31)) {
+        int g[4];
+        gather_lds_geom(N, K, elem_bytes, tc, g);
+        if (detail)
+            for (int i = 0; i < 4; ++i) detail[i] = g[i];
+        return GNNOPS_ROUTE_LDS;
+    }
+    d[0] = elem_bytes;
+    d[1] = K;
+    d[2] = gnnops_grid_cap(gnnops_cdiv(B * E * K, 256), 256 * 32);
+    return route_done(GNNOPS_ROUTE_ELEMS, d, detail);
+}
+
+extern "C" int gnnops_fused_select_sum_route(int64_t B, int64_t N, int64_t K, int64_t E, int dtype, uintptr_t input_addr,
+                                             int* detail) {
+    int64_t d[4] = {0, 0, 0, 0};
+    if (B < 0 || N < 0 || K < 0 || E < 0 || B * E * K == 0 || !(dtype == GNNOPS_F32 || dtype == GNNOPS_F16 || dtype == GNNOPS_BF16))
+        return route_done(GNNOPS_ROUTE_NONE, d, detail);
+    const int64_t eb = dtype == GNNOPS_F32 ? 4 : 2, VEC = 16 / eb;   // Elem<T>::VEC
+    if (K % VEC == 0 && input_addr % 16 == 0) {
+        const RowGeom g = row_geom(K / VEC);
+        const int64_t items = B * g.chunks * E;
+        const bool simple = B == 1 && g.chunks == 1;                 // as in select_sum_rows_kernel
+        const bool whole = simple && ((int64_t)VEC << g.gshift) == K;
+        d[0] = g.gshift;
+        d[1] = g.chunks;
+        d[2] = (whole ? 1 : 0) | (simple ? 2 : 0);
+        d[3] = gnnops_grid_cap(gnnops_cdiv(items, (256 >> g.gshift) * ROWS_IN_FLIGHT), FUSED_BLOCKS);
+        return route_done(GNNOPS_ROUTE_ROWS, d, detail);
+    }
+    if (K == 1 && (size_t)N * eb <= GL_BUDGET && E * 32 >= N * eb) {
+        d[0] = 1;
+        d[1] = 1024;
+        d[2] = gnnops_grid_cap(B, FUSED_BLOCKS);
+        return route_done(GNNOPS_ROUTE_LDS, d, detail);
+    }
+    if (K >= LONGROW_MIN_UNITS) {
+        d[0] = (eb == 2 && K % 2 == 0 && input_addr % 4 == 0) ? 2 : 1;
+        d[1] = K / d[0];
+        d[2] = gnnops_grid_cap(gnnops_cdiv(B * E, 4), FUSED_BLOCKS);
+        return route_done(GNNOPS_ROUTE_LONGROWS, d, detail);
+    }
+    d[0] = 1;
+    d[1] = K;
+    d[2] = gnnops_grid_cap(gnnops_cdiv(B * E * K, 256 * 4), FUSED_BLOCKS);
+    return route_done(GNNOPS_ROUTE_ELEMS, d, detail);
+}
 
 extern "C" int gnnops_index_select(const void* input, const int64_t* index, void* out, int64_t B, int64_t N,
                                    int64_t K, int64_t E, int elem_bytes, gnnops_stream_t s) {
@@ -629,43 +747,32 @@ extern "C" int gnnops_index_select(const void* input, const int64_t* index, void
     if (B * E * K == 0) return GNNOPS_OK;
     GNNOPS_REQUIRE(input && index && out, GNNOPS_EINVAL, "index_select: null pointer");
     const int64_t rowbytes = K * elem_bytes;
-    if (rowbytes % 16 == 0 && (uintptr_t)input % 16 == 0 && (uintptr_t)out % 16 == 0) {
-        RowGeom g = row_geom(rowbytes / 16);
-        const int64_t items = B * g.chunks * E;
-        // nontemporal on both sides, 4 rows in flight per lane group, 64 workgroups per CU of grid:
-        // the fastest of the variants swept with tools/time_sel.py at config 2
-        const int sgrid = gnnops_grid_cap(gnnops_cdiv(items, (256 >> g.gshift) * ROWS_IN_FLIGHT), 256 * 64);
-        const char* mapenv = getenv("GNNOPS_PULL_MAP");   // g: the grid-strided map of rounds 1-2 (A/B: tools/ab_store_map.py; contiguous is 1.1-1.3 % faster)
-        const int blk_map = !(mapenv && mapenv[0] == 'g');
-        hipLaunchKernelGGL((select_rows_kernel<true, true, ROWS_IN_FLIGHT>), dim3(sgrid), dim3(256), 0, stream,
-                           (const char*)input, index, (char*)out, B, N, E, rowbytes, g.gshift, g.chunks, blk_map);
-    } else {
-        // K == 1 with a batch of rows that fit 64 KiB of LDS: rows parked on chip, the index shared by TB rows
-        if (K == 1 && B > 1 && N >= 512 && E >= 256 && (size_t)N * elem_bytes <= 64 * 1024 && E * 32 >= N * elem_bytes &&
-            gnnops_cdiv(B, 1) < ((int64_t)1 << 31)) {
-            switch (elem_bytes) {
-                case 1: return launch_select_k1<uint8_t>(input, index, out, B, N, E, stream);
-                case 2: return launch_select_k1<uint16_t>(input, index, out, B, N, E, stream);
-                case 4: return launch_select_k1<uint32_t>(input, index, out, B, N, E, stream);
-                default: return launch_select_k1<uint64_t>(input, index, out, B, N, E, stream);
-            }
+    int d[4];
+    switch (gnnops_index_select_route(B, N, K, E, elem_bytes, (uintptr_t)input, (uintptr_t)out, d)) {
+        case GNNOPS_ROUTE_ROWS: {
+            const char* mapenv = getenv("GNNOPS_PULL_MAP");   // g: the grid-strided map of rounds 1-2 (A/B: tools/ab_store_map.py; contiguous is 1.1-1.3 % faster)
+            const int blk_map = !(mapenv && mapenv[0] == 'g');
+            hipLaunchKernelGGL((select_rows_kernel<true, true, ROWS_IN_FLIGHT>), dim3(d[3]), dim3(256), 0, stream,
+                               (const char*)input, index, (char*)out, B, N, E, rowbytes, d[0], d[1], blk_map);
+            break;
         }
-        // a row index with K > 1 is already coalesced along k in the element kernel; LDS staging pays for K == 1 rows
-        if (const int tc = gather_lds_width(N, K, E, elem_bytes, B);
-            tc > 0 && K * elem_bytes <= 8 && B * gnnops_cdiv(K, tc) < ((int64_t)1 << 31)) {
+        case GNNOPS_ROUTE_K1:
             switch (elem_bytes) {
-                case 1: return launch_gather_lds<uint8_t, false>(input, index, out, B, N, K, E, tc, stream);
-                case 2: return launch_gather_lds<uint16_t, false>(input, index, out, B, N, K, E, tc, stream);
-                case 4: return launch_gather_lds<uint32_t, false>(input, index, out, B, N, K, E, tc, stream);
-                default: return launch_gather_lds<uint64_t, false>(input, index, out, B, N, K, E, tc, stream);
+                case 1: return launch_select_k1<uint8_t>(input, index, out, B, N, E, d[0], d[1], stream);
+                case 2: return launch_select_k1<uint16_t>(input, index, out, B, N, E, d[0], d[1], stream);
+                case 4: return launch_select_k1<uint32_t>(input, index, out, B, N, E, d[0], d[1], stream);
+                default: return launch_select_k1<uint64_t>(input, index, out, B, N, E, d[0], d[1], stream);
             }
-        }
-        // copy in the widest unit that divides the row and the base alignment (a row is one opaque byte string)
-        const uintptr_t al = (uintptr_t)input | (uintptr_t)out | (uintptr_t)rowbytes;
-        const int unit = al % 8 == 0 ? 8 : al % 4 == 0 ? 4 : al % 2 == 0 ? 2 : 1;
-        if (rowbytes / unit >= LONGROW_MIN_UNITS) {
+        case GNNOPS_ROUTE_LDS:
+            switch (elem_bytes) {
+                case 1: return launch_gather_lds<uint8_t, false>(input, index, out, B, N, K, E, d, stream);
+                case 2: return launch_gather_lds<uint16_t, false>(input, index, out, B, N, K, E, d, stream);
+                case 4: return launch_gather_lds<uint32_t, false>(input, index, out, B, N, K, E, d, stream);
+                default: return launch_gather_lds<uint64_t, false>(input, index, out, B, N, K, E, d, stream);
+            }
+        case GNNOPS_ROUTE_LONGROWS: {
+            const int unit = d[0], lgrid = d[2];
             const int64_t KU = rowbytes / unit;
-            const int lgrid = gnnops_grid_cap(gnnops_cdiv(B * E * gnnops_cdiv(KU, 512), 4), 256 * 32);
             if (unit == 8)
                 hipLaunchKernelGGL((select_longrows_kernel<uint64_t>), dim3(lgrid), dim3(256), 0, stream, (const uint64_t*)input,
                                    index, (uint64_t*)out, B, N, KU, E);
@@ -678,21 +785,23 @@ extern "C" int gnnops_index_select(const void* input, const int64_t* index, void
             else
                 hipLaunchKernelGGL((select_longrows_kernel<uint8_t>), dim3(lgrid), dim3(256), 0, stream, (const uint8_t*)input,
                                    index, (uint8_t*)out, B, N, KU, E);
-            return gnnops_check_launch("index_select");
+            break;
         }
-        int grid = gnnops_grid_cap(gnnops_cdiv(B * E * K, 256), 256 * 32);
-        if (al % 8 == 0)
-            hipLaunchKernelGGL((select_elems_kernel<uint64_t, false>), dim3(grid), dim3(256), 0, stream,
-                               (const uint64_t*)input, index, (uint64_t*)out, B, N, rowbytes / 8, E);
-        else if (al % 4 == 0)
-            hipLaunchKernelGGL((select_elems_kernel<uint32_t, false>), dim3(grid), dim3(256), 0, stream,
-                               (const uint32_t*)input, index, (uint32_t*)out, B, N, rowbytes / 4, E);
-        else if (al % 2 == 0)
-            hipLaunchKernelGGL((select_elems_kernel<uint16_t, false>), dim3(grid), dim3(256), 0, stream,
-                               (const uint16_t*)input, index, (uint16_t*)out, B, N, rowbytes / 2, E);
-        else
-            hipLaunchKernelGGL((select_elems_kernel<uint8_t, false>), dim3(grid), dim3(256), 0, stream,
-                               (const uint8_t*)input, index, (uint8_t*)out, B, N, rowbytes, E);
+        default: {
+            const int unit = d[0], grid = d[2];
+            if (unit == 8)
+                hipLaunchKernelGGL((select_elems_kernel<uint64_t, false>), dim3(grid), dim3(256), 0, stream,
+                                   (const uint64_t*)input, index, (uint64_t*)out, B, N, rowbytes / 8, E);
+            else if (unit == 4)
+                hipLaunchKernelGGL((select_elems_kernel<uint32_t, false>), dim3(grid), dim3(256), 0, stream,
+                                   (const uint32_t*)input, index, (uint32_t*)out, B, N, rowbytes / 4, E);
+            else if (unit == 2)
+                hipLaunchKernelGGL((select_elems_kernel<uint16_t, false>), dim3(grid), dim3(256), 0, stream,
+                                   (const uint16_t*)input, index, (uint16_t*)out, B, N, rowbytes / 2, E);
+            else
+                hipLaunchKernelGGL((select_elems_kernel<uint8_t, false>), dim3(grid), dim3(256), 0, stream,
+                                   (const uint8_t*)input, index, (uint8_t*)out, B, N, rowbytes, E);
+        }
     }
     return gnnops_check_launch("index_select");
 }
@@ -746,11 +855,11 @@ extern "C" int gnnops_gather(const void* input, const int64_t* index, void* out,
                    "gather: elem_bytes %d", elem_bytes);
     if (B * E * K == 0) return GNNOPS_OK;
     GNNOPS_REQUIRE(input && index && out, GNNOPS_EINVAL, "gather: null pointer");
-    const int tc = gather_lds_width(N, K, E, elem_bytes, B);
-    const bool lds = tc > 0 && B * gnnops_cdiv(K, tc) < ((int64_t)1 << 31);
-    const int grid = gnnops_grid_cap(gnnops_cdiv(B * E * K, 256), 256 * 32);
+    int d[4];
+    const bool lds = gnnops_gather_route(B, N, K, E, elem_bytes, d) == GNNOPS_ROUTE_LDS;
+    const int grid = d[2];   // of the element route
 #define GATHER_CASE(U)                                                                                              \
-    if (lds) return launch_gather_lds<U, true>(input, index, out, B, N, K, E, tc, stream);                          \
+    if (lds) return launch_gather_lds<U, true>(input, index, out, B, N, K, E, d, stream);                           \
     hipLaunchKernelGGL((select_elems_kernel<U, true>), dim3(grid), dim3(256), 0, stream, (const U*)input, index,     \
                        (U*)out, B, N, K, E);                                                                         \
     break

@@ -14,6 +14,7 @@ ABI_VERSION = 2   # GNNOPS_ABI_VERSION of include/gnnops.h
 F32, F16, BF16 = 0, 1, 2
 SUM, MEAN, MIN, MAX, MUL = 0, 1, 2, 3, 4
 OK, EINVAL, EWORKSPACE, ELAUNCH, EUNSUPPORTED = 0, 1, 2, 3, 4  # status codes of include/gnnops.h
+ROUTE_NONE, ROUTE_ROWS, ROUTE_K1, ROUTE_LDS, ROUTE_LONGROWS, ROUTE_ELEMS = -1, 0, 1, 2, 3, 4  # enum gnnops_route
 REDUCE_CODE = {"sum": SUM, "add": SUM, "mean": MEAN, "min": MIN, "max": MAX, "mul": MUL}
 
 # name -> (restype, argtypes); must list every symbol include/gnnops.h declares (tests check this).
@@ -55,6 +56,9 @@ SIGNATURES = {
     "gnnops_gather": (_ci, [_vp, _vp, _vp, _i64, _i64, _i64, _i64, _ci, _vp]),
     "gnnops_fused_select_sum_workspace_bytes": (_sz, []),
     "gnnops_fused_index_select_sum": (_ci, [_vp, _vp, _vp, _i64, _i64, _i64, _i64, _ci, _vp, _sz, _vp]),
+    "gnnops_index_select_route": (_ci, [_i64, _i64, _i64, _i64, _ci, _sz, _sz, ctypes.POINTER(_ci)]),
+    "gnnops_gather_route": (_ci, [_i64, _i64, _i64, _i64, _ci, ctypes.POINTER(_ci)]),
+    "gnnops_fused_select_sum_route": (_ci, [_i64, _i64, _i64, _i64, _ci, _sz, ctypes.POINTER(_ci)]),
     "gnnops_spmm": (_ci, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _ci, _vp]),
     "gnnops_spmm_hubs": (_ci, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _ci, _vp, _sz, _vp]),
     "gnnops_spmm_tiled": (_ci, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _ci, _vp, _vp, _vp, _ci, _ci, _vp]),

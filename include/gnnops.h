@@ -243,6 +243,38 @@ int gnnops_fused_index_select_sum(const void* input, const int64_t* index, float
                                   gnnops_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Route queries (host only, no device is touched): which kernel the three entry points above launch
+ * for a shape and base alignment, and with what geometry. The entry points call these and switch on
+ * the result, so the thresholds exist here only. `input_addr` / `out_addr` are the base addresses
+ * (only their low four bits matter). Returns a gnnops_route code, GNNOPS_ROUTE_NONE when nothing is
+ * launched (an empty result, an elem_bytes / dtype the entry point refuses), and fills detail[0..3]
+ * (may be NULL):
+ *   ROWS      gshift (2^gshift lanes per row), chunks, flags, grid.
+ *             flags bit 0: a full workgroup step takes the straight-line "whole" form.
+ *             flags bit 1 (fused sum only): the division-free "simple" form (one matrix, one chunk).
+ *   K1        tb (rows parked per workgroup), grid.
+ *   LDS       tc (columns per strip), threads, strips, tshift.
+ *             Fused sum (one row parked per step): 1, 1024, grid, 0.
+ *   LONGROWS  index_select: copy unit in bytes, KU (units per row, saturated at INT_MAX), grid.
+ *             Fused sum: PAIR (2 = two 16-bit values per 4-byte load, else 1), K / PAIR, grid.
+ *   ELEMS     index_select: copy unit in bytes, KU, grid. gather: elem_bytes, K, grid.
+ *             Fused sum: 1, K, grid.
+ * ------------------------------------------------------------------------------------------- */
+enum gnnops_route {
+    GNNOPS_ROUTE_NONE = -1,
+    GNNOPS_ROUTE_ROWS = 0,
+    GNNOPS_ROUTE_K1 = 1,
+    GNNOPS_ROUTE_LDS = 2,
+    GNNOPS_ROUTE_LONGROWS = 3,
+    GNNOPS_ROUTE_ELEMS = 4
+};
+int gnnops_index_select_route(int64_t B, int64_t N, int64_t K, int64_t E, int elem_bytes, uintptr_t input_addr,
+                              uintptr_t out_addr, int* detail);
+int gnnops_gather_route(int64_t B, int64_t N, int64_t K, int64_t E, int elem_bytes, int* detail);
+int gnnops_fused_select_sum_route(int64_t B, int64_t N, int64_t K, int64_t E, int dtype, uintptr_t input_addr,
+                                  int* detail);
+
+/* ---------------------------------------------------------------------------------------------
  * torch_sparse.spmm(index, value, m, n, matrix) / torch.sparse.mm(COO, dense)
  * (benchmark_sparse_spmm.py:12-14; BASELINE config 3). Row-split over a CSR view of the sparse operand:
  *   out[i,:] = sum_{j in [rowptr[i], rowptr[i+1])} value[e_j] * mat[col[e_j], :],  e_j = perm ? perm[j] : j
