@@ -1,5 +1,6 @@
 """Single-layer forward benchmarks — counterpart of the reference's app_bm/benchmark_convs.py:146-246 (FiLMConv, GINConv,
-CGConv on QM9; PNAConv on MNIST superpixels; SAGEConv on IMDB-MULTI with OneHotDegree(88)), hidden width 2048, fp16
+CGConv on QM9; PNAConv on MNIST superpixels; SAGEConv on IMDB-MULTI with OneHotDegree(88); plus GATv2Conv on QM9, the attention
+layer of the reference's model zoo, which its app_bm list does not time), hidden width 2048, fp16
 (`.to(torch.float16)`, :147) or fp32, batch size 512 (apps_bm_data/model_data_fp16.txt:2) or 1 (`Config.batch_size`, :26,
 apps_bm_data/model_data_fp16_no_batching.txt).
 
@@ -140,6 +141,20 @@ def chain_forward(name, layer, x, ei):
         amp, att = torch.log(deg + 1) / layer.avg_deg["log"], layer.avg_deg["log"] / torch.log(deg + 1)
         out = torch.cat([x, out, out * amp, out * att], dim=-1)
         return layer.lin(layer.post_nns[0](out))
+    if name == "GATv2":
+        H, C = layer.heads, layer.out_channels
+        keep = src != dst                                     # remove_self_loops, add_self_loops
+        loops = torch.arange(n, device=x.device)
+        src, dst = torch.cat([src[keep], loops]), torch.cat([dst[keep], loops])
+        xl, xr = layer.lin_l(x).view(n, H, C), layer.lin_r(x).view(n, H, C)
+        xj = xl[src]
+        s = (F.leaky_relu(xr[dst] + xj, layer.negative_slope) * layer.att).sum(-1)
+        mx = s.new_full((n, H), float("-inf")).scatter_reduce_(0, dst.view(-1, 1).expand_as(s), s, "amax", include_self=True)
+        ex = (s - mx[dst]).exp()
+        alpha = ex / _scatter(ex, dst, n, "sum")[dst]
+        out = _scatter(xj * alpha.unsqueeze(-1), dst, n, "sum")
+        out = out.view(n, H * C) if layer.concat else out.mean(dim=1)
+        return out if layer.bias is None else out + layer.bias
     raise KeyError(name)
 
 
@@ -173,6 +188,9 @@ def build_models(dtype, deg_hist):
         ("CGConv", "QM9", conv.CGConv(11, 0).to(dtype).cuda()),
         ("PNA", "MNIST", conv.PNAConv(in_channels=1, out_channels=2048, aggregators=aggr, scalers=scal, deg=deg_hist).to(dtype).cuda()),
         ("GraphSAGE", "IMDB-MULTI", conv.SAGEConv(89, 2048).to(dtype).cuda()),
+        # not in the reference's app_bm list: the attention layer of its model zoo (graph_benchmark/models/ptg_models.py:208-236,
+        # GATv2Conv(in, hidden, heads, concat=False)); 8 heads x 256 = the 2048-wide rows of the other five
+        ("GATv2", "QM9", conv.GATv2Conv(11, 256, heads=8, concat=False).to(dtype).cuda()),
     ]
 
 

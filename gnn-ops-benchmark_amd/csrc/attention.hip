@@ -1,0 +1,551 @@
+// attention.hip — the softmax-weighted aggregation of a GATv2 layer in ONE pass over the destination-sorted edge list, and its
+// backward (gnnops.conv.edge_attention / GATv2Conv; the reference's model zoo builds GATv2REG from GATv2Conv,
+// graph_benchmark/models/ptg_models.py:208-236, and trains it, OpProfiler.py:97-112).
+//
+//   z[e,h,c]   = p[i,h,c] + q[j,h,c]                          edge e = (j -> i)
+//   s[e,h]     = sum_c att[h,c] * leaky_relu(z[e,h,c], slope)
+//   a[e,h]     = exp(s[e,h] - lse[i,h]),   lse[i,h] = log sum_{e into i} exp(s[e,h])
+//   out[i,h,:] = sum_{e into i} a[e,h] * q[j,h,:]
+//
+// The weight of an edge depends on ALL the edges of its destination, which the elementwise messages of conv.hip cannot say.
+// The forward keeps, per (destination, head), a running maximum m, a denominator l and the accumulators (online softmax):
+// a step of U edges may raise the maximum, l and the accumulators are then rescaled by exp(m_old - m_new). Each gathered q row
+// is read once and serves the score and the weighted sum; no [E, H] score and no [E, H, C] message is written.
+//
+// Layout: ONE WAVE per (destination, block of 64 / G heads), one group of G = 2^gshift lanes per head, lane gl of a group on
+// the columns (k * G + gl) * VEC .. + VEC of its head, k < NCH. The whole wave walks the same edges, so the edge loop, its
+// bounds and the row base addresses are scalar, the ids of a run of 64 edges are one coalesced load handed out by
+// v_readlane (as conv.hip's WAVE_ROW form), and the per-head dot product is a butterfly of DPP moves inside the group with every
+// lane active (quad_perm, row_half_mirror, row_mirror; groups of 32 / 64 lanes add the four row sums read by v_readlane).
+// Rows of more than 256 pieces per head (C > 256 * VEC) take the NCH = 128, VEC = 1 instance: correct at any C <= 8192, its
+// operand rows of p and att re-read per edge (cache hits) and its accumulators wherever the compiler finds room.
+// Heavy destinations are walked by their one wave (no piecewise pass yet: the (m, l, accumulator) triple merges across
+// pieces, so the cure of hub.h applies).
+//
+// Algorithmic bytes per launch, forward: E * H * (C * elem + 8 / heads-per-wave-block) gathered + N * (p row + out row + 4 H);
+// the unfused chain on this package's ops moves at least three [E, H, C] tensors and two [E, H] ones, each written and read.
+// Backward (destination-ordered too, no atomics): s is recomputed from the same rows, a = exp(s - lse); one [E, H * C] tensor gq
+// is written (d q = its segment sum over the source plan), d p is summed in registers and stored once per destination, d att is
+// summed per wave in fp32 and the [waves, H * C] partials are added in a fixed order by a second small kernel.
+#include <initializer_list>
+#include <utility>
+#include "common.h"
+
+namespace {
+
+struct AttArgs {
+    const void *q, *p, *att, *g, *o;    // o, g: the stored forward output and its gradient (backward only)
+    const int32_t *rowptr, *perm;
+    const int64_t* col;
+    void *out, *dp, *gq;
+    float *lse, *partial;
+    int64_t N, ldq, ldp, ldo, ldg;
+    int H, C, gshift, hblocks, nwaves;
+    float slope;
+};
+
+template <typename T, int VEC>
+__device__ inline u32x4 att_load_raw(const T* p) {
+    constexpr int BYTES = VEC * (int)sizeof(T);
+    u32x4 r = {0u, 0u, 0u, 0u};
+    if constexpr (BYTES == 16) {
+        r = load16<false>(p);
+    } else if constexpr (BYTES == 8) {
+        const uint2 t = *reinterpret_cast<const uint2*>(p);
+        r.x = t.x; r.y = t.y;
+    } else if constexpr (BYTES == 4) {
+        r.x = *reinterpret_cast<const uint32_t*>(p);
+    } else {
+        r.x = *reinterpret_cast<const uint16_t*>(p);
+    }
+    return r;
+}
+template <typename T, int VEC>
+__device__ inline void att_unpack(const u32x4& r, float* f) {
+    float g[Elem<T>::VEC];
+    Elem<T>::unpack(r, g);
+#pragma unroll
+    for (int v = 0; v < VEC; ++v) f[v] = g[v];
+}
+template <typename T, int VEC>
+__device__ inline void att_store(T* p, const float* f) {
+    constexpr int BYTES = VEC * (int)sizeof(T);
+    if constexpr (VEC == 1) {
+        Elem<T>::store(p, f[0]);
+    } else {
+        float g[Elem<T>::VEC];
+#pragma unroll
+        for (int v = 0; v < Elem<T>::VEC; ++v) g[v] = v < VEC ? f[v] : 0.f;
+        const u32x4 r = Elem<T>::pack(g);
+        if constexpr (BYTES == 16) store16<false>(p, r);
+        else if constexpr (BYTES == 8) *reinterpret_cast<uint2*>(p) = uint2{r.x, r.y};
+        else *reinterpret_cast<uint32_t*>(p) = r.x;
+    }
+}
+
+template <int CTRL>
+__device__ inline float dpp_move(float v) {
+    return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, 0xf, 0xf, false));
+}
+__device__ inline float read_lane(float v, int l) { return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), l)); }
+
+// Sum over each group of 2^gshift consecutive lanes, every lane of a group gets it; gshift is wave-uniform and EVERY lane of
+// the wave is active (the callers' control flow is scalar). Steps 1, 2: quad_perm [1,0,3,2] and [2,3,0,1]; 4: row_half_mirror
+// (lane k <-> 7 - k of its half row: the two quads there already hold their sums); 8: row_mirror; 16, 32: the four row sums.
+__device__ inline float group_sum(float v, int gshift, int lane) {
+    if (gshift >= 1) v = v + dpp_move<0xB1>(v);
+    if (gshift >= 2) v = v + dpp_move<0x4E>(v);
+    if (gshift >= 3) v = v + dpp_move<0x141>(v);
+    if (gshift >= 4) v = v + dpp_move<0x140>(v);
+    if (gshift >= 5) {
+        const float lo = read_lane(v, 0) + read_lane(v, 16), hi = read_lane(v, 32) + read_lane(v, 48);
+        v = gshift == 5 ? (lane < 32 ? lo : hi) : lo + hi;
+    }
+    return v;
+}
+
+template <int NCH> struct Unroll { static constexpr int U = NCH == 1 ? 8 : NCH == 2 ? 4 : NCH <= 4 ? 2 : 1; };
+
+// where a lane stands: its head, and per piece k its element offset inside a row of H * C (0 and !ok past the head's end)
+struct Place {
+    int lane, gl, G, h, C;
+    bool head_ok;
+    __device__ inline Place(const AttArgs& a, int hb) {
+        lane = threadIdx.x & 63;
+        G = 1 << a.gshift;
+        gl = lane & (G - 1);
+        h = hb * (64 >> a.gshift) + (lane >> a.gshift);
+        C = a.C;
+        head_ok = h < a.H;
+    }
+    template <int VEC> __device__ inline bool live(int k) const { return k * G * VEC < C; }   // wave-uniform: some lane has piece k
+    template <int VEC> __device__ inline bool ok(int k) const { return head_ok && (k * G + gl) * VEC < C; }
+    template <int VEC> __device__ inline int off(int k) const { return ok<VEC>(k) ? h * C + (k * G + gl) * VEC : 0; }
+};
+
+template <typename T, int VEC, int NCH>
+__global__ __launch_bounds__(256) void attention_fwd_kernel(const AttArgs a) {
+    constexpr int U = Unroll<NCH>::U;
+    constexpr bool HOLD = NCH <= 4;   // p and att pieces stay in registers
+    const T* __restrict__ q = (const T*)a.q;
+    const T* __restrict__ p = (const T*)a.p;
+    const T* __restrict__ att = (const T*)a.att;
+    const int64_t* __restrict__ col = a.col;
+    const int wave = __builtin_amdgcn_readfirstlane((int)(((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6));
+    const int64_t items = a.N * a.hblocks;
+    const int ldq = (int)a.ldq;
+    const float slope = a.slope;
+    const float NEG_INF = -__builtin_huge_valf();
+    for (int64_t it = wave; it < items; it += a.nwaves) {
+        const int i = __builtin_amdgcn_readfirstlane((int)(it / a.hblocks));
+        const int hb = __builtin_amdgcn_readfirstlane((int)(it % a.hblocks));
+        const Place pl(a, hb);
+        const int lane = pl.lane;
+        const int32_t jb = __builtin_amdgcn_readfirstlane(a.rowptr[i]), je = __builtin_amdgcn_readfirstlane(a.rowptr[i + 1]);
+        float pv[HOLD ? NCH : 1][VEC], av[HOLD ? NCH : 1][VEC];
+        if constexpr (HOLD) {
+#pragma unroll
+            for (int k = 0; k < NCH; ++k) {
+                att_unpack<T, VEC>(att_load_raw<T, VEC>(p + (int64_t)i * a.ldp + pl.off<VEC>(k)), pv[k]);
+                att_unpack<T, VEC>(att_load_raw<T, VEC>(att + pl.off<VEC>(k)), av[k]);
+            }
+        }
+        float acc[NCH][VEC];
+#pragma unroll
+        for (int k = 0; k < NCH; ++k)
+#pragma unroll
+            for (int v = 0; v < VEC; ++v) acc[k][v] = 0.f;
+        float m = NEG_INF, l = 0.f;
+        for (int32_t jrun = jb; jrun < je; jrun += 64) {
+            const int32_t jrun_end = min(jrun + 64, je);
+            int cl = 0;
+            if (jrun + lane < je) cl = (int)col[jrun + lane];   // one coalesced load: lane l holds id l of the run
+            for (int32_t j = jrun; j < jrun_end; j += U) {
+                int64_t qrow[U];
+#pragma unroll
+                for (int u = 0; u < U; ++u) {
+                    qrow[u] = (int64_t)__builtin_amdgcn_readlane(cl, (j - jrun + u) & 63) * ldq;
+                    asm volatile("" : "+s"(qrow[u]));   // the row bases are computed HERE, ahead of every row load (conv.hip:209-224)
+                }
+                u32x4 qr[U][NCH];
+#pragma unroll
+                for (int u = 0; u < U; ++u) {           // every row load of the step in flight before the first is consumed
+                    if (j + u < jrun_end) {
+#pragma unroll
+                        for (int k = 0; k < NCH; ++k)
+                            if (pl.live<VEC>(k)) qr[u][k] = att_load_raw<T, VEC>(q + qrow[u] + pl.off<VEC>(k));
+                    }
+                }
+                float s[U];
+#pragma unroll
+                for (int u = 0; u < U; ++u) {
+                    s[u] = 0.f;
+                    if (j + u < jrun_end) {
+                        float part = 0.f;
+#pragma unroll
+                        for (int k = 0; k < NCH; ++k) {
+                            if (!pl.live<VEC>(k)) continue;
+                            float qv[VEC], pk[VEC], ak[VEC];
+                            att_unpack<T, VEC>(qr[u][k], qv);
+                            if constexpr (!HOLD) {
+                                att_unpack<T, VEC>(att_load_raw<T, VEC>(p + (int64_t)i * a.ldp + pl.off<VEC>(k)), pk);
+                                att_unpack<T, VEC>(att_load_raw<T, VEC>(att + pl.off<VEC>(k)), ak);
+                            }
+                            float sub = 0.f;
+#pragma unroll
+                            for (int v = 0; v < VEC; ++v) {
+                                const float z = (HOLD ? pv[k][v] : pk[v]) + qv[v];
+                                sub += (HOLD ? av[k][v] : ak[v]) * (z > 0.f ? z : z * slope);
+                            }
+                            part += pl.ok<VEC>(k) ? sub : 0.f;
+                        }
+                        s[u] = group_sum(part, a.gshift, lane);
+                    }
+                }
+                float mn = m;
+#pragma unroll
+                for (int u = 0; u < U; ++u)
+                    if (j + u < jrun_end) mn = fmaxf(mn, s[u]);
+                const float scale = expf(m - mn);   // 0 on the first step (m = -inf): nothing to rescale yet
+                m = mn;
+                l = l * scale;
+#pragma unroll
+                for (int k = 0; k < NCH; ++k)
+#pragma unroll
+                    for (int v = 0; v < VEC; ++v) acc[k][v] = acc[k][v] * scale;
+#pragma unroll
+                for (int u = 0; u < U; ++u) {
+                    if (j + u < jrun_end) {
+                        const float w = expf(s[u] - mn);
+                        l = l + w;
+#pragma unroll
+                        for (int k = 0; k < NCH; ++k) {
+                            if (!pl.live<VEC>(k)) continue;
+                            float qv[VEC];
+                            att_unpack<T, VEC>(qr[u][k], qv);
+#pragma unroll
+                            for (int v = 0; v < VEC; ++v) acc[k][v] = acc[k][v] + w * qv[v];
+                        }
+                    }
+                }
+            }
+        }
+        const bool any = je > jb;
+#pragma unroll
+        for (int k = 0; k < NCH; ++k) {
+            if (!pl.live<VEC>(k)) continue;
+            float o[VEC];
+#pragma unroll
+            for (int v = 0; v < VEC; ++v) o[v] = any ? acc[k][v] / l : 0.f;
+            if (pl.ok<VEC>(k)) att_store<T, VEC>((T*)a.out + (int64_t)i * a.ldo + pl.off<VEC>(k), o);
+        }
+        if (pl.head_ok && pl.gl == 0) a.lse[(int64_t)i * a.H + pl.h] = any ? m + logf(l) : NEG_INF;
+    }
+}
+
+// Backward. The wave's head block is the same for all its destinations (nwaves is a multiple of hblocks), so the d att sums
+// of its lanes stay in registers across destinations and are written once, to row wave / hblocks of the partials.
+template <typename T, int VEC, int NCH>
+__global__ __launch_bounds__(256) void attention_bwd_kernel(const AttArgs a) {
+    constexpr int U = NCH == 1 ? 4 : NCH == 2 ? 2 : 1;
+    constexpr bool HOLD = NCH <= 4;
+    const T* __restrict__ q = (const T*)a.q;
+    const T* __restrict__ p = (const T*)a.p;
+    const T* __restrict__ att = (const T*)a.att;
+    const T* __restrict__ g = (const T*)a.g;
+    const T* __restrict__ o = (const T*)a.o;
+    const int64_t* __restrict__ col = a.col;
+    const int32_t* __restrict__ perm = a.perm;
+    const int wave = __builtin_amdgcn_readfirstlane((int)(((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6));
+    if (wave >= a.nwaves) return;
+    const int64_t items = a.N * a.hblocks;
+    const int ldq = (int)a.ldq;
+    const int HC = a.H * a.C;
+    const float slope = a.slope;
+    const int hb = __builtin_amdgcn_readfirstlane(wave % a.hblocks);
+    const Place pl(a, hb);
+    const int lane = pl.lane;
+    float datt[NCH][VEC];
+#pragma unroll
+    for (int k = 0; k < NCH; ++k)
+#pragma unroll
+        for (int v = 0; v < VEC; ++v) datt[k][v] = 0.f;
+    float av[HOLD ? NCH : 1][VEC];
+    if constexpr (HOLD) {
+#pragma unroll
+        for (int k = 0; k < NCH; ++k) att_unpack<T, VEC>(att_load_raw<T, VEC>(att + pl.off<VEC>(k)), av[k]);
+    }
+    for (int64_t it = wave; it < items; it += a.nwaves) {
+        const int i = __builtin_amdgcn_readfirstlane((int)(it / a.hblocks));
+        const int32_t jb = __builtin_amdgcn_readfirstlane(a.rowptr[i]), je = __builtin_amdgcn_readfirstlane(a.rowptr[i + 1]);
+        float pv[HOLD ? NCH : 1][VEC], gv[HOLD ? NCH : 1][VEC], dp[NCH][VEC];
+        float dpart = 0.f;
+#pragma unroll
+        for (int k = 0; k < NCH; ++k) {
+#pragma unroll
+            for (int v = 0; v < VEC; ++v) dp[k][v] = 0.f;
+            if (!pl.live<VEC>(k)) continue;
+            float gk[VEC], ok_[VEC];
+            att_unpack<T, VEC>(att_load_raw<T, VEC>(g + (int64_t)i * a.ldg + pl.off<VEC>(k)), gk);
+            att_unpack<T, VEC>(att_load_raw<T, VEC>(o + (int64_t)i * a.ldo + pl.off<VEC>(k)), ok_);
+            float sub = 0.f;
+#pragma unroll
+            for (int v = 0; v < VEC; ++v) sub += gk[v] * ok_[v];
+            dpart += pl.ok<VEC>(k) ? sub : 0.f;
+            if constexpr (HOLD) {
+                att_unpack<T, VEC>(att_load_raw<T, VEC>(p + (int64_t)i * a.ldp + pl.off<VEC>(k)), pv[k]);
+#pragma unroll
+                for (int v = 0; v < VEC; ++v) gv[k][v] = gk[v];
+            }
+        }
+        const float delta = group_sum(dpart, a.gshift, lane);                    // sum_c g * out of this head
+        const float lse = pl.head_ok ? a.lse[(int64_t)i * a.H + pl.h] : 0.f;
+        for (int32_t jrun = jb; jrun < je; jrun += 64) {
+            const int32_t jrun_end = min(jrun + 64, je);
+            int cl = 0, el = 0;
+            if (jrun + lane < je) {
+                cl = (int)col[jrun + lane];
+                el = perm ? perm[jrun + lane] : jrun + lane;
+            }
+            for (int32_t j = jrun; j < jrun_end; j += U) {
+                int64_t qrow[U], erow[U];
+#pragma unroll
+                for (int u = 0; u < U; ++u) {
+                    qrow[u] = (int64_t)__builtin_amdgcn_readlane(cl, (j - jrun + u) & 63) * ldq;
+                    erow[u] = (int64_t)__builtin_amdgcn_readlane(el, (j - jrun + u) & 63) * HC;
+                    asm volatile("" : "+s"(qrow[u]));
+                    asm volatile("" : "+s"(erow[u]));
+                }
+                u32x4 qr[U][NCH];
+#pragma unroll
+                for (int u = 0; u < U; ++u) {
+                    if (j + u < jrun_end) {
+#pragma unroll
+                        for (int k = 0; k < NCH; ++k)
+                            if (pl.live<VEC>(k)) qr[u][k] = att_load_raw<T, VEC>(q + qrow[u] + pl.off<VEC>(k));
+                    }
+                }
+#pragma unroll
+                for (int u = 0; u < U; ++u) {
+                    if (j + u >= jrun_end) continue;
+                    float spart = 0.f, dapart = 0.f;
+#pragma unroll
+                    for (int k = 0; k < NCH; ++k) {
+                        if (!pl.live<VEC>(k)) continue;
+                        float qv[VEC], pk[VEC], ak[VEC], gk[VEC];
+                        att_unpack<T, VEC>(qr[u][k], qv);
+                        if constexpr (!HOLD) {
+                            att_unpack<T, VEC>(att_load_raw<T, VEC>(p + (int64_t)i * a.ldp + pl.off<VEC>(k)), pk);
+                            att_unpack<T, VEC>(att_load_raw<T, VEC>(att + pl.off<VEC>(k)), ak);
+                            att_unpack<T, VEC>(att_load_raw<T, VEC>(g + (int64_t)i * a.ldg + pl.off<VEC>(k)), gk);
+                        }
+                        float s1 = 0.f, s2 = 0.f;
+#pragma unroll
+                        for (int v = 0; v < VEC; ++v) {
+                            const float z = (HOLD ? pv[k][v] : pk[v]) + qv[v];
+                            s1 += (HOLD ? av[k][v] : ak[v]) * (z > 0.f ? z : z * slope);
+                            s2 += (HOLD ? gv[k][v] : gk[v]) * qv[v];
+                        }
+                        const bool ok = pl.ok<VEC>(k);
+                        spart += ok ? s1 : 0.f;
+                        dapart += ok ? s2 : 0.f;
+                    }
+                    const float s = group_sum(spart, a.gshift, lane), da = group_sum(dapart, a.gshift, lane);
+                    const float w = expf(s - lse);
+                    const float ds = w * (da - delta);
+#pragma unroll
+                    for (int k = 0; k < NCH; ++k) {
+                        if (!pl.live<VEC>(k)) continue;
+                        float qv[VEC], pk[VEC], ak[VEC], gk[VEC], row[VEC];
+                        att_unpack<T, VEC>(qr[u][k], qv);
+                        if constexpr (!HOLD) {
+                            att_unpack<T, VEC>(att_load_raw<T, VEC>(p + (int64_t)i * a.ldp + pl.off<VEC>(k)), pk);
+                            att_unpack<T, VEC>(att_load_raw<T, VEC>(att + pl.off<VEC>(k)), ak);
+                            att_unpack<T, VEC>(att_load_raw<T, VEC>(g + (int64_t)i * a.ldg + pl.off<VEC>(k)), gk);
+                        }
+#pragma unroll
+                        for (int v = 0; v < VEC; ++v) {
+                            const float z = (HOLD ? pv[k][v] : pk[v]) + qv[v];
+                            const float t = ds * (HOLD ? av[k][v] : ak[v]) * (z > 0.f ? 1.f : slope);
+                            dp[k][v] = dp[k][v] + t;
+                            datt[k][v] = datt[k][v] + ds * (z > 0.f ? z : z * slope);
+                            row[v] = w * (HOLD ? gv[k][v] : gk[v]) + t;
+                        }
+                        if (pl.ok<VEC>(k)) att_store<T, VEC>((T*)a.gq + erow[u] + pl.off<VEC>(k), row);
+                    }
+                }
+            }
+        }
+#pragma unroll
+        for (int k = 0; k < NCH; ++k)
+            if (pl.live<VEC>(k) && pl.ok<VEC>(k)) att_store<T, VEC>((T*)a.dp + (int64_t)i * HC + pl.off<VEC>(k), dp[k]);
+    }
+    float* prow = a.partial + (int64_t)(wave / a.hblocks) * HC;
+#pragma unroll
+    for (int k = 0; k < NCH; ++k) {
+        if (!pl.live<VEC>(k) || !pl.ok<VEC>(k)) continue;
+#pragma unroll
+        for (int v = 0; v < VEC; ++v) prow[pl.off<VEC>(k) + v] = datt[k][v];
+    }
+}
+
+// d att[c] = the partial rows added top to bottom: the same bits every run
+template <typename T>
+__global__ __launch_bounds__(256) void attention_datt_kernel(const float* __restrict__ partial, int rows, int HC, T* __restrict__ datt) {
+    const int c = blockIdx.x * blockDim.x + threadIdx.x;
+    if (c >= HC) return;
+    float s = 0.f;
+    for (int r = 0; r < rows; ++r) s = s + partial[(int64_t)r * HC + c];
+    Elem<T>::store(datt + c, s);
+}
+
+struct Geometry { int vec, nch, gshift, hblocks; };
+
+// widest piece the operands allow, narrowed while the heads of a row leave half the wave idle; NCH pieces per lane
+inline Geometry geometry(int H, int C, int max_vec, int es) {
+    int vec = max_vec;
+    while (vec > 1 && C % vec != 0) vec >>= 1;
+    auto gshift_of = [&](int v) { int s = 0; while ((1 << s) < C / v && s < 6) ++s; return s; };
+    while (vec > 1 && vec * es > 4 && (int64_t)H << gshift_of(vec) <= 32 && C / vec <= 32) vec >>= 1;
+    Geometry g{};
+    const int pieces = C / vec;
+    g.vec = vec;
+    g.gshift = gshift_of(vec);
+    g.nch = pieces <= 64 ? 1 : pieces <= 128 ? 2 : pieces <= 256 ? 4 : 128;
+    if (g.nch == 128) { g.vec = 1; g.gshift = 6; }   // 64 lanes x 128 single elements: any C <= 8192
+    const int hp = 64 >> g.gshift;
+    g.hblocks = (H + hp - 1) / hp;
+    return g;
+}
+
+inline int rows_of_partials(int64_t N, int H, int C) {
+    const int64_t HC = (int64_t)H * C;
+    int64_t rows = ((int64_t)1 << 22) / HC;            // 16 MiB of fp32 partials at the most
+    rows = rows < 256 ? 256 : rows > 2048 ? 2048 : rows;
+    if (rows > N) rows = N;
+    return (int)(rows < 1 ? 1 : rows);
+}
+
+inline int max_vec_of(int es, std::initializer_list<std::pair<const void*, int64_t>> operands) {
+    int max_vec = 16 / es;
+    for (const auto& op : operands) {
+        if (!op.first) continue;
+        while (max_vec > 1 && ((uintptr_t)op.first % (max_vec * es) != 0 || (op.second * es) % (max_vec * es) != 0)) max_vec >>= 1;
+    }
+    return max_vec;
+}
+
+template <typename T, bool BW, int VEC, int NCH>
+void launch_kernel(const AttArgs& a, int grid, hipStream_t stream) {
+    if constexpr (BW) hipLaunchKernelGGL((attention_bwd_kernel<T, VEC, NCH>), dim3(grid), dim3(256), 0, stream, a);
+    else hipLaunchKernelGGL((attention_fwd_kernel<T, VEC, NCH>), dim3(grid), dim3(256), 0, stream, a);
+}
+
+template <typename T, bool BW, int VEC>
+void launch_nch(const AttArgs& a, int nch, int grid, hipStream_t stream) {
+    if (nch == 1) launch_kernel<T, BW, VEC, 1>(a, grid, stream);
+    else if (nch == 2) launch_kernel<T, BW, VEC, 2>(a, grid, stream);
+    else launch_kernel<T, BW, VEC, 4>(a, grid, stream);
+}
+
+template <typename T, bool BW>
+void launch(const AttArgs& a, const Geometry& geo, int grid, hipStream_t stream) {
+    if (geo.nch == 128) return launch_kernel<T, BW, 1, 128>(a, grid, stream);
+    if constexpr (Elem<T>::VEC == 8) {
+        if (geo.vec == 8) return launch_nch<T, BW, 8>(a, geo.nch, grid, stream);
+    }
+    if (geo.vec == 4) return launch_nch<T, BW, 4>(a, geo.nch, grid, stream);
+    if (geo.vec == 2) return launch_nch<T, BW, 2>(a, geo.nch, grid, stream);
+    return launch_nch<T, BW, 1>(a, geo.nch, grid, stream);
+}
+
+int check_sizes(const char* what, int64_t N, int64_t E, int64_t H, int64_t C, int64_t ldq, int64_t ldp, int dtype, int* es) {
+    GNNOPS_REQUIRE(N >= 0 && E >= 0, GNNOPS_EINVAL, "%s: negative size", what);
+    GNNOPS_REQUIRE(H >= 1 && C >= 1 && H * C <= 8192, GNNOPS_EINVAL, "%s: needs heads >= 1, channels >= 1 and heads * channels <= 8192 (got %lld x %lld)",
+                   what, (long long)H, (long long)C);
+    GNNOPS_REQUIRE(N < ((int64_t)1 << 31) && E < ((int64_t)1 << 31) && ldq < ((int64_t)1 << 31), GNNOPS_EUNSUPPORTED,
+                   "%s: N, E and the row pitch must be < 2^31", what);
+    GNNOPS_REQUIRE(ldq >= H * C && ldp >= H * C, GNNOPS_EINVAL, "%s: a row pitch is shorter than the row", what);
+    switch (dtype) {
+        case GNNOPS_F32: *es = 4; break;
+        case GNNOPS_F16: case GNNOPS_BF16: *es = 2; break;
+        default: gnnops_set_error("%s: unknown dtype %d", what, dtype); return GNNOPS_EINVAL;
+    }
+    return GNNOPS_OK;
+}
+
+}  // namespace
+
+extern "C" int gnnops_edge_attention(const void* q, int64_t ldq, const void* p, int64_t ldp, const void* att, const int32_t* rowptr,
+                                     const int64_t* col, void* out, int64_t ldo, float* lse, int64_t N, int64_t E, int64_t H,
+                                     int64_t C, float negative_slope, int dtype, gnnops_stream_t s) {
+    int es = 0;
+    const int rc = check_sizes("edge_attention", N, E, H, C, ldq, ldp, dtype, &es);
+    if (rc != GNNOPS_OK) return rc;
+    GNNOPS_REQUIRE(ldo >= H * C, GNNOPS_EINVAL, "edge_attention: a row pitch is shorter than the row");
+    if (N == 0) return GNNOPS_OK;
+    GNNOPS_REQUIRE(rowptr && out && lse && p && att && (E == 0 || (q && col)), GNNOPS_EINVAL, "edge_attention: null pointer");
+    const int max_vec = max_vec_of(es, {{q, ldq}, {p, ldp}, {att, 0}, {out, ldo}});
+    const Geometry geo = geometry((int)H, (int)C, max_vec, es);
+    AttArgs a{};
+    a.q = q; a.p = p; a.att = att; a.rowptr = rowptr; a.col = col; a.out = out; a.lse = lse;
+    a.N = N; a.ldq = ldq; a.ldp = ldp; a.ldo = ldo; a.H = (int)H; a.C = (int)C; a.slope = negative_slope;
+    a.gshift = geo.gshift; a.hblocks = geo.hblocks;
+    const int grid = gnnops_grid_cap(gnnops_cdiv(N * geo.hblocks, 4), 256 * 32);
+    a.nwaves = grid * 4;
+    hipStream_t stream = (hipStream_t)s;
+    switch (dtype) {
+        case GNNOPS_F32: launch<float, false>(a, geo, grid, stream); break;
+        case GNNOPS_F16: launch<__half, false>(a, geo, grid, stream); break;
+        default: launch<__hip_bfloat16, false>(a, geo, grid, stream); break;
+    }
+    return gnnops_check_launch("edge_attention");
+}
+
+extern "C" size_t gnnops_edge_attention_backward_workspace_bytes(int64_t N, int64_t H, int64_t C) {
+    if (N <= 0 || H < 1 || C < 1 || H * C > 8192) return 0;
+    return (size_t)rows_of_partials(N, (int)H, (int)C) * (size_t)(H * C) * sizeof(float);
+}
+
+extern "C" int gnnops_edge_attention_backward(const void* q, int64_t ldq, const void* p, int64_t ldp, const void* att,
+                                              const void* out, int64_t ldo, const float* lse, const void* grad_out, int64_t ldg,
+                                              const int32_t* rowptr, const int32_t* perm, const int64_t* col, void* grad_p,
+                                              void* gq, void* grad_att, int64_t N, int64_t E, int64_t H, int64_t C,
+                                              float negative_slope, int dtype, void* workspace, size_t workspace_bytes,
+                                              gnnops_stream_t s) {
+    int es = 0;
+    const int rc = check_sizes("edge_attention_backward", N, E, H, C, ldq, ldp, dtype, &es);
+    if (rc != GNNOPS_OK) return rc;
+    GNNOPS_REQUIRE(ldo >= H * C && (ldg >= H * C || ldg == 0), GNNOPS_EINVAL, "edge_attention_backward: a row pitch is shorter than the row");
+    GNNOPS_REQUIRE(grad_att, GNNOPS_EINVAL, "edge_attention_backward: null pointer");
+    hipStream_t stream = (hipStream_t)s;
+    const int HC = (int)(H * C);
+    if (N == 0) return GNNOPS_OK;   // no destination: nothing is written
+    GNNOPS_REQUIRE(rowptr && out && lse && p && att && grad_out && grad_p && (E == 0 || (q && col && gq)), GNNOPS_EINVAL,
+                   "edge_attention_backward: null pointer");
+    const size_t need = gnnops_edge_attention_backward_workspace_bytes(N, H, C);
+    GNNOPS_REQUIRE(workspace && workspace_bytes >= need && (uintptr_t)workspace % 16 == 0, GNNOPS_EWORKSPACE,
+                   "edge_attention_backward: workspace %zu < %zu", workspace_bytes, need);
+    const int max_vec = max_vec_of(es, {{q, ldq}, {p, ldp}, {att, 0}, {out, ldo}, {grad_out, ldg}, {grad_p, HC}, {gq, HC}});
+    const Geometry geo = geometry((int)H, (int)C, max_vec, es);
+    const int rows = rows_of_partials(N, (int)H, (int)C);
+    AttArgs a{};
+    a.q = q; a.p = p; a.att = att; a.g = grad_out; a.o = out; a.rowptr = rowptr; a.perm = perm; a.col = col;
+    a.dp = grad_p; a.gq = gq; a.lse = const_cast<float*>(lse); a.partial = (float*)workspace;
+    a.N = N; a.ldq = ldq; a.ldp = ldp; a.ldo = ldo; a.ldg = ldg; a.H = (int)H; a.C = (int)C; a.slope = negative_slope;
+    a.gshift = geo.gshift; a.hblocks = geo.hblocks;
+    a.nwaves = rows * geo.hblocks;
+    const int grid = (int)gnnops_cdiv(a.nwaves, 4);
+    switch (dtype) {
+        case GNNOPS_F32: launch<float, true>(a, geo, grid, stream); break;
+        case GNNOPS_F16: launch<__half, true>(a, geo, grid, stream); break;
+        default: launch<__hip_bfloat16, true>(a, geo, grid, stream); break;
+    }
+    const dim3 dgrid((unsigned)gnnops_cdiv(HC, 256));
+    switch (dtype) {
+        case GNNOPS_F32: hipLaunchKernelGGL(attention_datt_kernel<float>, dgrid, dim3(256), 0, stream, a.partial, rows, HC, (float*)grad_att); break;
+        case GNNOPS_F16: hipLaunchKernelGGL(attention_datt_kernel<__half>, dgrid, dim3(256), 0, stream, a.partial, rows, HC, (__half*)grad_att); break;
+        default: hipLaunchKernelGGL(attention_datt_kernel<__hip_bfloat16>, dgrid, dim3(256), 0, stream, a.partial, rows, HC, (__hip_bfloat16*)grad_att); break;
+    }
+    return gnnops_check_launch("edge_attention_backward");
+}

@@ -18,6 +18,9 @@ segment sums over the plans the forward already holds (by destination for the p 
 weight operands are cached only while nothing requires grad. PNAConv (min / max / std aggregators with degree scalers): the
 fused multi-aggregator pass has no backward, so in a graph that needs gradients the layer runs the propagate-order chain
 (`_forward_train`: per-edge messages, one differentiable scatter per aggregator) on this package's differentiable ops.
+
+Attention: `GATv2Conv` (the reference's model zoo, graph_benchmark/models/ptg_models.py:208-236) is one dense product and one
+attention pass, `edge_attention` (csrc/attention.hip: online softmax per destination and head, trainable) — SURVEY.md §8(f) rank 1.
 """
 import ctypes
 
@@ -34,12 +37,12 @@ AGGREGATORS = {"sum": 0, "add": 0, "mean": 1, "min": 2, "max": 3, "std": 4}
 SCALERS = {"identity": 0, "amplification": 1, "attenuation": 2, "linear": 3, "inverse_linear": 4}
 
 
-def _rows(t, what, parts, K):
+def _rows(t, what, parts, K, op="edge_reduce"):
     """A [rows, >= parts*K] operand whose rows are contiguous runs (column blocks of a wider matrix are fine)."""
     if t is None:
         return None, 0
     if t.dim() != 2 or (t.size(1) > 1 and t.stride(1) != 1) or t.size(1) < parts * K:
-        raise RuntimeError(f"edge_reduce: {what} must be 2-D with unit column stride and at least {parts * K} columns")
+        raise RuntimeError(f"{op}: {what} must be 2-D with unit column stride and at least {parts * K} columns")
     return t, (t.stride(0) if t.size(0) > 1 else t.size(1))
 
 
@@ -597,3 +600,167 @@ class SplineConv(_Layer):
 
         return spline_conv(x, self._flip(edge_index), edge_attr, self.weight, self.kernel_size, self.is_open_spline, self.degree,
                            self.aggr == "mean", self.root, self.bias)
+
+
+# ---- attention: GATv2 (csrc/attention.hip) ---------------------------------------------------------------------------------
+def _attention_operands(q, p, att, edge_index, num_dst, heads):
+    _require_gpu(q, p, att, edge_index)
+    HC = att.numel()
+    if heads < 1 or HC == 0 or HC % heads:
+        raise RuntimeError(f"edge_attention: heads = {heads} does not divide the row width {HC} (att has one entry per head and channel)")
+    if q.dtype != p.dtype or q.dtype != att.dtype:
+        raise RuntimeError("edge_attention: operands must have the same dtype")
+    q, ldq = _rows(q, "q", 1, HC, op="edge_attention")
+    p, ldp = _rows(p, "p", 1, HC, op="edge_attention")
+    if p.size(0) != num_dst:
+        raise RuntimeError("edge_attention: p has one row per destination")
+    if q.size(0) >= 2 ** 31:
+        raise NotImplementedError("edge_attention: 2^31 or more source rows")
+    edge_index, src_rows, dst_rows = _coo_rows_cols(edge_index, "edge_attention")
+    plan = get_plan(dst_rows, num_dst, owner=edge_index, tag=1, companion=src_rows)   # the plans of edge_reduce: nothing new on a warm call
+    E = edge_index.size(1)
+    if plan.col is not None or E == 0:
+        col = plan.col if E else src_rows
+    else:
+        col, _ = _csr_arrays(plan, src_rows, None, owner=edge_index, tag=0)
+    return q, ldq, p, ldp, att.contiguous().view(-1), edge_index, src_rows, plan, col, E, HC
+
+
+def _attention_forward(q, p, att, edge_index, num_dst, heads, negative_slope):
+    """(out [num_dst, H * C], lse fp32 [num_dst, H]) of one launch of gnnops_edge_attention."""
+    q, ldq, p, ldp, att, edge_index, _, plan, col, E, HC = _attention_operands(q, p, att, edge_index, num_dst, heads)
+    out = torch.empty((num_dst, HC), dtype=q.dtype, device=q.device)
+    lse = torch.empty((num_dst, heads), dtype=torch.float32, device=q.device)
+    with _on(q.device):
+        check(_lib.load().gnnops_edge_attention(q.data_ptr(), ldq, p.data_ptr(), ldp, att.data_ptr(), plan.rowptr.data_ptr(),
+                                                col.data_ptr(), out.data_ptr(), HC, lse.data_ptr(), num_dst, E, heads, HC // heads,
+                                                float(negative_slope), _dtype_code(q, "edge_attention"), _stream()), "edge_attention")
+    return out, lse
+
+
+def edge_attention(q, p, att, edge_index, num_dst, heads, negative_slope=0.2):
+    """out[i, h, :] = sum over the edges (j -> i) of softmax_e(s[e, h]) * q[j, h, :],  s[e, h] = att[h] . leaky_relu(p[i, h] + q[j, h])
+    — GATv2's message and aggregation in one pass with an online softmax (csrc/attention.hip). q [N_src, H * C] and p [num_dst, H * C]
+    may be column blocks of one product; att holds H * C entries (any shape); edge_index int64 [2, E] = (source, destination). A
+    destination without edges gets a zero row. Differentiable in q, p and att."""
+    if _wants_grad(q, p, att):
+        return _EdgeAttention.apply(q, p, att, edge_index, num_dst, heads, float(negative_slope))
+    return _attention_forward(q, p, att, edge_index, num_dst, heads, negative_slope)[0]
+
+
+class _EdgeAttention(torch.autograd.Function):
+    """backward (gnnops_edge_attention_backward, destination-ordered like the forward): d p and d att from the kernel, and one
+    per-edge tensor gq [E, H * C] in edge order whose segment sum over the plan of the source ids is d q — as `_EdgeReduce`."""
+
+    @staticmethod
+    def forward(ctx, q, p, att, edge_index, num_dst, heads, negative_slope):
+        out, lse = _attention_forward(q, p, att, edge_index, num_dst, heads, negative_slope)
+        ctx.meta = (num_dst, heads, negative_slope)
+        ctx.save_for_backward(q, p, att, edge_index, out, lse)
+        return out
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        q0, p0, att0, edge_index, out, lse = ctx.saved_tensors
+        num_dst, heads, slope = ctx.meta
+        q, ldq, p, ldp, att, edge_index, src_rows, plan, col, E, HC = _attention_operands(q0, p0, att0, edge_index, num_dst, heads)
+        need_q, need_p, need_att = ctx.needs_input_grad[:3]
+        if E == 0 or num_dst == 0:
+            return (torch.zeros_like(q0) if need_q else None, torch.zeros_like(p0) if need_p else None,
+                    torch.zeros_like(att0) if need_att else None, None, None, None, None)
+        # autograd hands over whatever layout the consumer made: out.sum() an expanded scalar (strides 0, 0), W @ out.t() a
+        # transposed one. Rows of unit column stride are read in place (pitch 0 = one row for all); anything else is copied.
+        g = grad_out if grad_out.dim() == 2 and (grad_out.stride(1) == 1 or grad_out.size(1) == 1) else grad_out.contiguous()
+        g, ldg = _rows(g, "the output gradient", 1, HC, op="edge_attention")
+        if g.size(0) > 1 and g.stride(0) == 0:
+            ldg = 0
+        d_p = torch.empty((num_dst, HC), dtype=q.dtype, device=q.device)
+        gq = torch.empty((E, HC), dtype=q.dtype, device=q.device)
+        d_att = torch.empty(HC, dtype=q.dtype, device=q.device)
+        L = _lib.load()
+        ws_bytes = L.gnnops_edge_attention_backward_workspace_bytes(num_dst, heads, HC // heads)
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=q.device)
+        with _on(q.device):
+            check(L.gnnops_edge_attention_backward(q.data_ptr(), ldq, p.data_ptr(), ldp, att.data_ptr(), out.data_ptr(), HC,
+                                                   lse.data_ptr(), g.data_ptr(), ldg, plan.rowptr.data_ptr(), plan.perm.data_ptr(),
+                                                   col.data_ptr(), d_p.data_ptr(), gq.data_ptr(), d_att.data_ptr(), num_dst, E, heads,
+                                                   HC // heads, slope, _dtype_code(q, "edge_attention"), ws.data_ptr(), ws_bytes,
+                                                   _stream()), "edge_attention_backward")
+        d_q = None
+        if need_q:
+            plan_src = get_plan(src_rows, q.size(0), owner=edge_index, tag=0)
+            d_q = ops.scatter(gq, plan_src, 0, None, None, "sum")
+            if q0.size(1) != HC:         # q was a column block wider than the H * C the pass reads
+                d_q = torch.nn.functional.pad(d_q, (0, q0.size(1) - HC))
+        if need_p and p0.size(1) != HC:
+            d_p = torch.nn.functional.pad(d_p, (0, p0.size(1) - HC))
+        return d_q, (d_p if need_p else None), (d_att.view(att0.shape) if need_att else None), None, None, None, None
+
+
+class GATv2Conv(_Layer):
+    """x'_i = sum_j alpha_ij W_l x_j (+ bias),  alpha_ij = softmax_j(att . leaky_relu(W_l x_j + W_r x_i))  per head
+    (torch_geometric 2.0.2 GATv2Conv, Brody et al. 2021; the reference's GATv2REG, graph_benchmark/models/ptg_models.py:208-236,
+    calls GATv2Conv(in, hidden, heads=heads, concat=False)). One product x @ [W_l^T | W_r^T] (one block when the weights are
+    shared), one attention pass (`edge_attention`), then the mean over heads (concat=False) and the bias. Parameter names and shapes
+    follow PyG so a state_dict moves across; torch_geometric is not available to compare against: parity unpinned. Self loops:
+    existing ones are removed, then one is added per node, and the augmented index is kept per edge_index object so that its
+    plans stay cached. Attention dropout is not implemented (the reference uses the default 0)."""
+
+    def __init__(self, in_channels, out_channels, heads=1, concat=True, negative_slope=0.2, dropout=0.0, add_self_loops=True,
+                 bias=True, share_weights=False):
+        super().__init__()
+        self.in_channels, self.out_channels, self.heads, self.concat = in_channels, out_channels, heads, concat
+        self.negative_slope, self.dropout, self.add_self_loops, self.share_weights = negative_slope, dropout, add_self_loops, share_weights
+        in_l, in_r = (in_channels, in_channels) if isinstance(in_channels, int) else in_channels
+        self.lin_l = torch.nn.Linear(in_l, heads * out_channels, bias=bias)
+        self.lin_r = self.lin_l if share_weights else torch.nn.Linear(in_r, heads * out_channels, bias=bias)
+        self.att = torch.nn.Parameter(torch.empty(1, heads, out_channels))
+        self.bias = torch.nn.Parameter(torch.zeros(heads * out_channels if concat else out_channels)) if bias else None
+        for w in (self.lin_l.weight, self.lin_r.weight, self.att):      # glorot, as PyG
+            torch.nn.init.xavier_uniform_(w)
+        for lin in (self.lin_l, self.lin_r):
+            if lin.bias is not None:
+                torch.nn.init.zeros_(lin.bias)
+        self._pk_both, self._pk_l, self._pk_r = _Packed(), _Packed(), _Packed()
+        self._looped = None   # (weakref to edge_index, its version, number of nodes, augmented copy)
+
+    def _with_self_loops(self, edge_index, n):
+        import weakref
+
+        cacheable = ops._plan_cache_enabled and ops._version_of(edge_index) is not None
+        hit = self._looped if cacheable else None
+        if hit is not None and hit[0]() is edge_index and hit[1] == ops._version_of(edge_index) and hit[2] == n:
+            return hit[3]
+        keep = edge_index[0] != edge_index[1]
+        loops = torch.arange(n, dtype=edge_index.dtype, device=edge_index.device)
+        looped = torch.cat([edge_index[:, keep], torch.stack([loops, loops])], dim=1).contiguous()
+        self._looped = (weakref.ref(edge_index), edge_index._version, n, looped) if cacheable else None
+        return looped
+
+    def forward(self, x, edge_index, size=None):
+        if self.dropout > 0.0 and self.training:
+            raise NotImplementedError("gnnops.conv.GATv2Conv: attention dropout is not implemented in the fused pass; construct the "
+                                      "layer with dropout=0.0 (the reference's default) or call it in eval mode")
+        H, C = self.heads, self.out_channels
+        HC = H * C
+        ll, lr = self.lin_l, self.lin_r
+        if isinstance(x, (tuple, list)):
+            if self.add_self_loops:
+                raise RuntimeError("GATv2Conv: a bipartite pair needs add_self_loops=False")
+            x_src, x_dst = x
+            q = _dense(x_src.contiguous(), self._pk_l.get([ll.weight, ll.bias], [(ll.weight, ll.bias)]))
+            p = _dense(x_dst.contiguous(), self._pk_r.get([lr.weight, lr.bias], [(lr.weight, lr.bias)]))
+            n_dst = x_dst.size(0) if size is None else size[1]
+        else:
+            n_dst = x.size(0)
+            if self.share_weights:
+                q = p = _dense(x.contiguous(), self._pk_l.get([ll.weight, ll.bias], [(ll.weight, ll.bias)]))
+            else:       # [q | p] = x @ [W_l^T | W_r^T]: the two projections reach the kernel as column blocks
+                qp = _dense(x.contiguous(), self._pk_both.get([ll.weight, lr.weight, ll.bias, lr.bias], [(ll.weight, ll.bias), (lr.weight, lr.bias)]))
+                q, p = qp[:, :HC], qp[:, HC:]
+            if self.add_self_loops:
+                edge_index = self._with_self_loops(edge_index, n_dst)
+        out = edge_attention(q, p, self.att, edge_index, n_dst, H, self.negative_slope)
+        if not self.concat:
+            out = out.view(n_dst, H, C).mean(dim=1)
+        return out if self.bias is None else out + self.bias

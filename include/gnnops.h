@@ -509,6 +509,32 @@ int gnnops_edge_grad(int functor, const void* p, int64_t ldp, const void* q, int
                      int64_t K, int dtype, gnnops_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Attention edge pass (csrc/attention.hip): the softmax-weighted aggregation of GATv2Conv — the reference's model zoo builds
+ * GATv2REG from it (graph_benchmark/models/ptg_models.py:208-236) — in one pass with an online softmax. Operands as
+ * gnnops_edge_reduce: destination-sorted plan (rowptr int32 [N+1], col int64 [E] = source row of each sorted position,
+ * perm int32 [E] = original edge id of that position, NULL = identity), ld* = row pitches in elements.
+ *   z[e,h,c] = p[i,h,c] + q[j,h,c]   s[e,h] = sum_c att[h,c] * leaky_relu(z[e,h,c], negative_slope)      edge e = (j -> i)
+ *   out[i,h,:] = sum_{e into i} exp(s[e,h] - lse[i,h]) * q[j,h,:],   lse[i,h] = log sum_{e into i} exp(s[e,h])
+ * q [N_src, >= H*C], p [N, >= H*C], att [H*C], out [N, H*C] (pitch ldo) in `dtype`; lse fp32 [N, H], always written.
+ * A destination without edges gets a zero row and lse = -inf. 1 <= H, 1 <= C, H*C <= 8192 (GNNOPS_EINVAL otherwise);
+ * N, E, ldq and every value of col (so N_src) below 2^31: the kernels narrow source ids to 32 bits.
+ * One launch on `stream`, no allocation, no synchronisation.
+ * Backward, given grad_out [N, >= H*C] (pitch ldg; 0 = one row for all), the forward's out and lse:
+ *   grad_p [N, H*C] dense; gq [E, H*C] dense, row = ORIGINAL edge id: d q = its segment sum over the plan of the source ids
+ *   (gnnops_segment_reduce); grad_att [H*C]. workspace = gnnops_edge_attention_backward_workspace_bytes(N, H, C) bytes of
+ *   fp32 partial sums of d att, added in a fixed order (the same bits every run). N == 0: nothing is written.
+ * ------------------------------------------------------------------------------------------- */
+int gnnops_edge_attention(const void* q, int64_t ldq, const void* p, int64_t ldp, const void* att, const int32_t* rowptr,
+                          const int64_t* col, void* out, int64_t ldo, float* lse, int64_t N, int64_t E, int64_t H, int64_t C,
+                          float negative_slope, int dtype, gnnops_stream_t stream);
+size_t gnnops_edge_attention_backward_workspace_bytes(int64_t N, int64_t H, int64_t C);
+int gnnops_edge_attention_backward(const void* q, int64_t ldq, const void* p, int64_t ldp, const void* att, const void* out,
+                                   int64_t ldo, const float* lse, const void* grad_out, int64_t ldg, const int32_t* rowptr,
+                                   const int32_t* perm, const int64_t* col, void* grad_p, void* gq, void* grad_att, int64_t N,
+                                   int64_t E, int64_t H, int64_t C, float negative_slope, int dtype, void* workspace,
+                                   size_t workspace_bytes, gnnops_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
  * The remaining ops of the reference's list (ops.txt:17-19, 29-41) - SURVEY.md 8(f) rank 4. Neither package is in the
  * reference tree (torch-spline-conv 1.2.1, torch-cluster 1.5.9: requirements.txt:214, :210) and the reference has no
  * script or output for them: the packages' published definitions, parity unpinned (oracle/spatial_oracle.py).
