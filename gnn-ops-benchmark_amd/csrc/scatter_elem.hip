@@ -8,6 +8,8 @@
 // path. fp32 adds are single `global_atomic_add_f32` instructions; 16-bit sums/products accumulate in
 // an fp32 scratch and are rounded once; min/max (and products) use a CAS loop on the 32-bit word. The arg pass
 // picks the smallest position among ties (atomicMin on int64), which is what a sequential CPU loop gives.
+// Which form takes a call — one LDS strip, chunked LDS strips or memory-side atomics — and with what geometry is decided
+// in elem_route() alone; gnnops_scatter_elementwise_route reports it.
 #include "common.h"
 
 namespace {
@@ -141,10 +143,54 @@ __global__ void scatter_arg_kernel(const T* __restrict__ src, const int64_t* __r
             atomicMin(reinterpret_cast<unsigned long long*>(arg_out + d), (unsigned long long)e);
     }
 }
-// torch_scatter: groups nothing reached (arg == E) become 0.
+// The same pass for a call that started from `out`: a destination no contribution IMPROVED keeps out and arg = E even where a
+// contribution ties with what out held — the sequential loop replaces on a strict improvement only. The value pass works in
+// place, so what out held is parked in arg_out (its bits) before that pass and compared after it: equal bits = not improved
+// (an improvement is a strictly smaller / larger value), marked ARG_KEPT, skipped here and set to E afterwards.
+constexpr int64_t ARG_KEPT = -1;
 template <typename T>
-__global__ void zero_empty_kernel(T* __restrict__ out, const int64_t* __restrict__ arg_out, int64_t n, int64_t E) {
-    GRID_STRIDE(i, n) if (arg_out[i] == E) Elem<T>::store(out + i, 0.f);
+__device__ inline int64_t elem_bits(const T* p) {
+    if constexpr (sizeof(T) == 4) return (int64_t)*reinterpret_cast<const uint32_t*>(p);
+    else return (int64_t)*reinterpret_cast<const uint16_t*>(p);
+}
+template <typename T>
+__global__ void park_out_kernel(const T* __restrict__ out, int64_t* __restrict__ arg_out, int64_t n) {
+    GRID_STRIDE(i, n) arg_out[i] = elem_bits(out + i);
+}
+template <typename T>
+__global__ void mark_kept_kernel(const T* __restrict__ out, int64_t* __restrict__ arg_out, int64_t n, int64_t E) {
+    GRID_STRIDE(i, n) arg_out[i] = (elem_bits(out + i) == arg_out[i]) ? ARG_KEPT : E;
+}
+template <typename T>
+__global__ void scatter_arg_improved_kernel(const T* __restrict__ src, const int64_t* __restrict__ index,
+                                            const T* __restrict__ out, int64_t* arg_out, int64_t B, int64_t E, int64_t K,
+                                            int64_t N) {
+    GRID_STRIDE(o, B * E * K) {
+        int64_t b, e, k;
+        decode(o, E, K, b, e, k);
+        const int64_t d = (b * N + index[o]) * K + k;
+        // a kept destination is written by nobody in this pass; an improved one holds E or a position, never ARG_KEPT
+        if (arg_out[d] != ARG_KEPT && Elem<T>::load(src + o) == Elem<T>::load(out + d))
+            atomicMin(reinterpret_cast<unsigned long long*>(arg_out + d), (unsigned long long)e);
+    }
+}
+// Last pass of the atomic min / max form, over the destinations. arg == E (nothing reached it; ARG_KEPT: nothing improved
+// out): torch_scatter's 0 for a call that did not start from out, out itself otherwise. A zero extremum takes the bits of
+// src at its arg: -0.0 and +0.0 compare equal, so the value pass keeps whichever arrived first, while the sequential loop
+// keeps the one at the smallest position — the element arg names.
+template <typename T>
+__global__ void finish_minmax_kernel(const T* __restrict__ src, T* __restrict__ out, int64_t* __restrict__ arg_out, int64_t E,
+                                     int64_t K, int64_t N, int64_t n, int init_from_out) {
+    GRID_STRIDE(i, n) {
+        const int64_t a = arg_out[i];
+        if (a == ARG_KEPT) {
+            arg_out[i] = E;
+        } else if (a == E) {
+            if (!init_from_out) Elem<T>::store(out + i, 0.f);
+        } else if (Elem<T>::load(out + i) == 0.f) {
+            out[i] = src[((i / (K * N)) * E + a) * K + i % K];
+        }
+    }
 }
 
 // ---- LDS-privatised form ---------------------------------------------------------------------------------
@@ -155,6 +201,10 @@ __global__ void zero_empty_kernel(T* __restrict__ out, const int64_t* __restrict
 // the full shape, dim 0 or 1, L <= 6708) all take this path: HBM-bound on the 8-B index.
 constexpr int LDS_THREADS = 1024;
 constexpr size_t LDS_BUDGET = 160 * 1024 - 512;
+// K == 1, 4-byte elements, whole 16-B pieces of both operands: a lane takes four consecutive elements per load. One text for
+// the two LDS kernels, which decide it themselves, and for elem_route(), which reports it.
+#define GNNOPS_FOUR_PER_LANE(K, E, elem_bytes, src, index) \
+    ((K) == 1 && ((E) & 3) == 0 && (elem_bytes) == 4 && ((uintptr_t)(src) % 16) == 0 && ((uintptr_t)(index) % 16) == 0)
 
 template <typename T, int R, typename I>
 __global__ __launch_bounds__(LDS_THREADS) void scatter_lds_kernel(const T* __restrict__ src,
@@ -233,7 +283,7 @@ __global__ __launch_bounds__(LDS_THREADS) void scatter_lds_kernel(const T* __res
     // K == 1, 4-byte elements: four consecutive elements per lane and load (see scatter_lds_minmax_kernel)
     struct alignas(sizeof(T) * 4) TV { T v[4]; };
     struct alignas(sizeof(I) * 4 > 16 ? 16 : sizeof(I) * 4) IV { I v[4]; };
-    const bool vec4 = !IS_ARG && K == 1 && (E & 3) == 0 && sizeof(T) == 4 && ((uintptr_t)src % 16) == 0 && ((uintptr_t)index % 16) == 0;
+    const bool vec4 = !IS_ARG && GNNOPS_FOUR_PER_LANE(K, E, sizeof(T), src, index);
     if (vec4) {
         constexpr int VU = 4;
         for (int64_t e0 = (int64_t)er * 4; e0 < E; e0 += (int64_t)rpi * 4 * VU) {
@@ -420,7 +470,7 @@ __global__ __launch_bounds__(LDS_THREADS) void scatter_lds_minmax_kernel(const T
     constexpr int VU = 4;
     struct alignas(sizeof(T) * 4) TV { T v[4]; };
     struct alignas(sizeof(I) * 4 > 16 ? 16 : sizeof(I) * 4) IV { I v[4]; };
-    const bool vec4 = K == 1 && (E & 3) == 0 && sizeof(T) == 4 && ((uintptr_t)src % 16) == 0 && ((uintptr_t)index % 16) == 0;
+    const bool vec4 = GNNOPS_FOUR_PER_LANE(K, E, sizeof(T), src, index);
     if (vec4) {
         for (int64_t e0 = (int64_t)er * 4; e0 < E; e0 += (int64_t)rpi * 4 * VU) {
             TV vt4[VU];
@@ -516,9 +566,14 @@ constexpr int LDS_MAX_CHUNKS = 16;
 inline bool small_cells(int reduce, int elem_bytes, int64_t E) {
     return (reduce == GNNOPS_MIN || reduce == GNNOPS_MAX) && elem_bytes == 2 && E < 65535;
 }
+// LDS bytes per destination and column: an fp32 accumulator (sums, products), accumulator + count (mean), or the packed
+// value image | position of min / max in 32 or 64 bits
+inline int lds_cell_bytes(int reduce, int elem_bytes, int64_t E) {
+    return (reduce == GNNOPS_SUM || reduce == GNNOPS_MUL || small_cells(reduce, elem_bytes, E)) ? 4 : 8;
+}
 
-inline LdsGeom lds_geometry(int64_t N, int64_t K, int reduce, bool small_cell = false, int64_t B = 1) {
-    const size_t per = (reduce == GNNOPS_SUM || reduce == GNNOPS_MUL || small_cell) ? 4 : 8;
+inline LdsGeom lds_geometry(int64_t N, int64_t K, int cell_bytes, int64_t B) {
+    const size_t per = (size_t)cell_bytes;
     LdsGeom g{0, 0, 0};
     if (N <= 0) return g;
     if ((size_t)N * per <= LDS_BUDGET) {
@@ -538,9 +593,45 @@ inline LdsGeom lds_geometry(int64_t N, int64_t K, int reduce, bool small_cell = 
     return LdsGeom{(int)tc, rows, (int)nchunks};
 }
 
+inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
+inline int grid_for(int64_t n) { return gnnops_grid_cap(gnnops_cdiv(n, 256), 256 * 16); }
+
+// The whole dispatch of a call with B * N * K > 0: which form takes it and with what launch geometry. run() and launch_lds()
+// launch what this says; gnnops_scatter_elementwise_route reports it (include/gnnops.h).
+struct ElemRoute {
+    int route = GNNOPS_ROUTE_NONE;
+    LdsGeom g{0, 0, 0};
+    int threads = 0, cell_bytes = 0, tshift = 0;
+    int64_t grid = 0;
+    bool vec4 = false;
+};
+inline ElemRoute elem_route(int64_t B, int64_t E, int64_t K, int64_t N, int elem_bytes, int reduce, int index_bytes, int arg32,
+                            uintptr_t src_addr, uintptr_t index_addr) {
+    ElemRoute r;
+    r.cell_bytes = lds_cell_bytes(reduce, elem_bytes, E);
+    if (const LdsGeom g = lds_geometry(N, K, r.cell_bytes, B);
+        g.tc > 0 && B * gnnops_cdiv(K, g.tc) * g.nchunks < ((int64_t)1 << 31) && E < ((int64_t)1 << 31)) {
+        r.route = g.nchunks == 1 ? GNNOPS_ROUTE_LDS : GNNOPS_ROUTE_LDS_CHUNKS;
+        r.g = g;
+        r.grid = B * gnnops_cdiv(K, g.tc) * g.nchunks;
+        while ((1 << r.tshift) < g.tc) ++r.tshift;
+        // a strip that leaves room for several workgroups per CU gets smaller ones: more of them resident, their
+        // init / stream / write-back phases overlap (the kernel needs ~70 VGPRs: one 1024-thread workgroup per CU otherwise)
+        const size_t lds = (size_t)g.rows * g.tc * r.cell_bytes;
+        r.threads = lds > 80 * 1024 ? LDS_THREADS : lds > 40 * 1024 ? 512 : 256;
+        r.vec4 = GNNOPS_FOUR_PER_LANE(K, E, elem_bytes, src_addr, index_addr);   // reported only: `vec4` of the LDS kernels
+        return r;
+    }
+    if (index_bytes != 8 || arg32) return r;     // a narrowed index / int32 arg is taken by the LDS forms only
+    r.route = GNNOPS_ROUTE_ATOMICS;
+    r.threads = 256;
+    r.grid = grid_for(B * E * K);                // the source-side launches; the fills and the finish cover B * N * K
+    return r;
+}
+
 template <typename T, int R, typename I>
 int launch_lds(const T* src, const I* index, T* out, int64_t* arg_out, int64_t B, int64_t E, int64_t K, int64_t N,
-               LdsGeom g, int init_from_out, hipStream_t stream, int arg32 = 0) {
+               const ElemRoute& r, int init_from_out, hipStream_t stream, int arg32 = 0) {
     static bool configured = false;
     if (!configured) {
         if (hipFuncSetAttribute(reinterpret_cast<const void*>(&scatter_lds_kernel<T, R, I>),
@@ -548,14 +639,9 @@ int launch_lds(const T* src, const I* index, T* out, int64_t* arg_out, int64_t B
             return gnnops_check_launch("scatter_lds attribute");
         configured = true;
     }
-    const size_t per = (R == GNNOPS_SUM || R == GNNOPS_MUL) ? 4 : 8;
+    const LdsGeom& g = r.g;
     const int strips = (int)gnnops_cdiv(K, g.tc);
-    const size_t lds = (size_t)g.rows * g.tc * per;
-    int tshift = 0;
-    while ((1 << tshift) < g.tc) ++tshift;
-    // a strip that leaves room for several workgroups per CU gets smaller ones: more of them resident, their
-    // init / stream / write-back phases overlap (the kernel needs ~70 VGPRs: one 1024-thread workgroup per CU otherwise)
-    const int threads = lds > 80 * 1024 ? LDS_THREADS : lds > 40 * 1024 ? 512 : 256;
+    const size_t lds = (size_t)g.rows * g.tc * r.cell_bytes;
     if constexpr (R == GNNOPS_MIN || R == GNNOPS_MAX) {
         auto go = [&](auto cell_tag) -> int {
             using CellT = decltype(cell_tag);
@@ -566,24 +652,22 @@ int launch_lds(const T* src, const I* index, T* out, int64_t* arg_out, int64_t B
                     return gnnops_check_launch("scatter_lds attribute");
                 configured_mm = true;
             }
-            const size_t lds_mm = (size_t)g.rows * g.tc * sizeof(CellT);
-            const int th = lds_mm > 80 * 1024 ? LDS_THREADS : lds_mm > 40 * 1024 ? 512 : 256;
-            hipLaunchKernelGGL((scatter_lds_minmax_kernel<T, R, CellT, I>), dim3((unsigned)(B * strips * g.nchunks)), dim3(th),
-                               lds_mm, stream, src, index, out, arg_out, B, E, K, N, g.tc, strips, g.rows, g.nchunks,
-                               init_from_out, tshift, arg32);
+            hipLaunchKernelGGL((scatter_lds_minmax_kernel<T, R, CellT, I>), dim3((unsigned)r.grid), dim3(r.threads), lds, stream,
+                               src, index, out, arg_out, B, E, K, N, g.tc, strips, g.rows, g.nchunks, init_from_out, r.tshift,
+                               arg32);
             return gnnops_check_launch("scatter_lds");
         };
-        if (small_cells(R, (int)sizeof(T), E)) return go(uint32_t{});
+        if (r.cell_bytes == 4) return go(uint32_t{});
         return go((unsigned long long)0);
     }
-    hipLaunchKernelGGL((scatter_lds_kernel<T, R, I>), dim3((unsigned)(B * strips * g.nchunks)), dim3(threads), lds, stream,
-                       src, index, out, arg_out, B, E, K, N, g.tc, strips, g.rows, g.nchunks, init_from_out, tshift);
+    hipLaunchKernelGGL((scatter_lds_kernel<T, R, I>), dim3((unsigned)r.grid), dim3(r.threads), lds, stream, src, index, out,
+                       arg_out, B, E, K, N, g.tc, strips, g.rows, g.nchunks, init_from_out, r.tshift);
     return gnnops_check_launch("scatter_lds");
 }
 
 template <typename T, typename I>
 int dispatch_lds(int reduce, const T* src, const I* index, T* out, int64_t* arg_out, int64_t B, int64_t E,
-                 int64_t K, int64_t N, LdsGeom g, int init_from_out, hipStream_t stream, int arg32 = 0) {
+                 int64_t K, int64_t N, const ElemRoute& g, int init_from_out, hipStream_t stream, int arg32 = 0) {
     switch (reduce) {
         case GNNOPS_SUM: return launch_lds<T, GNNOPS_SUM, I>(src, index, out, arg_out, B, E, K, N, g, init_from_out, stream);
         case GNNOPS_MEAN: return launch_lds<T, GNNOPS_MEAN, I>(src, index, out, arg_out, B, E, K, N, g, init_from_out, stream);
@@ -594,9 +678,6 @@ int dispatch_lds(int reduce, const T* src, const I* index, T* out, int64_t* arg_
     return GNNOPS_EINVAL;
 }
 
-inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
-inline int grid_for(int64_t n) { return gnnops_grid_cap(gnnops_cdiv(n, 256), 256 * 16); }
-
 template <typename T>
 int run(const void* src_, const void* index_, int index_bytes, void* out_, int64_t* arg_out, int64_t B, int64_t E, int64_t K,
         int64_t N, int reduce, int init_from_out, void* workspace, hipStream_t stream, int arg32 = 0) {
@@ -604,23 +685,23 @@ int run(const void* src_, const void* index_, int index_bytes, void* out_, int64
     const T* src = (const T*)src_;
     T* out = (T*)out_;
     const int64_t nout = B * N * K, nsrc = B * E * K;
-    const int gs = grid_for(nsrc), go = grid_for(nout);
     constexpr bool IS_F32 = sizeof(T) == 4;
     char* w = (char*)workspace;
 
-    if (const LdsGeom g = lds_geometry(N, K, reduce, small_cells(reduce, (int)sizeof(T), E), B);
-        g.tc > 0 && B * gnnops_cdiv(K, g.tc) * g.nchunks < ((int64_t)1 << 31) && E < ((int64_t)1 << 31)) {
+    const ElemRoute r = elem_route(B, E, K, N, (int)sizeof(T), reduce, index_bytes, arg32, (uintptr_t)src_, (uintptr_t)index_);
+    if (r.route == GNNOPS_ROUTE_LDS || r.route == GNNOPS_ROUTE_LDS_CHUNKS) {
         if (index_bytes == 4)
-            return dispatch_lds<T, int32_t>(reduce, src, (const int32_t*)index_, out, arg_out, B, E, K, N, g, init_from_out, stream, arg32);
+            return dispatch_lds<T, int32_t>(reduce, src, (const int32_t*)index_, out, arg_out, B, E, K, N, r, init_from_out, stream, arg32);
         if (index_bytes == 2)
-            return dispatch_lds<T, uint16_t>(reduce, src, (const uint16_t*)index_, out, arg_out, B, E, K, N, g, init_from_out, stream, arg32);
-        return dispatch_lds<T, int64_t>(reduce, src, index, out, arg_out, B, E, K, N, g, init_from_out, stream, arg32);
+            return dispatch_lds<T, uint16_t>(reduce, src, (const uint16_t*)index_, out, arg_out, B, E, K, N, r, init_from_out, stream, arg32);
+        return dispatch_lds<T, int64_t>(reduce, src, index, out, arg_out, B, E, K, N, r, init_from_out, stream, arg32);
     }
-    if (index_bytes != 8 || arg32) {
+    if (r.route != GNNOPS_ROUTE_ATOMICS) {
         gnnops_set_error("scatter_elementwise: a narrowed index / int32 arg is taken by the LDS-strip form only (B=%lld N=%lld K=%lld)",
                          (long long)B, (long long)N, (long long)K);
         return GNNOPS_EUNSUPPORTED;
     }
+    const int gs = (int)r.grid, go = grid_for(nout);
 
     if (reduce == GNNOPS_SUM || reduce == GNNOPS_MEAN || reduce == GNNOPS_MUL) {
         // fp32 accumulator: `out` itself for fp32, a scratch for 16-bit types (rounded once at the end)
@@ -658,6 +739,8 @@ int run(const void* src_, const void* index_, int index_bytes, void* out_, int64
     if (!init_from_out) {
         const float ident = reduce == GNNOPS_MIN ? __builtin_huge_valf() : -__builtin_huge_valf();
         hipLaunchKernelGGL((fill_kernel<T>), dim3(go), dim3(256), 0, stream, out, nout, ident);
+    } else if (arg_out) {
+        hipLaunchKernelGGL((park_out_kernel<T>), dim3(go), dim3(256), 0, stream, out, arg_out, nout);
     }
     if (nsrc > 0) {
         if (reduce == GNNOPS_MIN)
@@ -665,13 +748,17 @@ int run(const void* src_, const void* index_, int index_bytes, void* out_, int64
         else
             hipLaunchKernelGGL((scatter_cas_kernel<T, GNNOPS_MAX>), dim3(gs), dim3(256), 0, stream, src, index, out, B, E, K, N);
     }
-    if (arg_out) {
+    if (arg_out && init_from_out) {
+        hipLaunchKernelGGL((mark_kept_kernel<T>), dim3(go), dim3(256), 0, stream, out, arg_out, nout, E);
+        if (nsrc > 0)
+            hipLaunchKernelGGL((scatter_arg_improved_kernel<T>), dim3(gs), dim3(256), 0, stream, src, index, out, arg_out, B, E, K, N);
+        hipLaunchKernelGGL((finish_minmax_kernel<T>), dim3(go), dim3(256), 0, stream, src, out, arg_out, E, K, N, nout, 1);
+    } else if (arg_out) {
         hipLaunchKernelGGL(fill_i64_kernel, dim3(go), dim3(256), 0, stream, arg_out, nout, E);
         if (nsrc > 0)
             hipLaunchKernelGGL((scatter_arg_kernel<T>), dim3(gs), dim3(256), 0, stream, src, index, out, arg_out, B, E, K, N,
                                reduce == GNNOPS_MIN ? __builtin_huge_valf() : -__builtin_huge_valf());
-        if (!init_from_out)
-            hipLaunchKernelGGL((zero_empty_kernel<T>), dim3(go), dim3(256), 0, stream, out, arg_out, nout, E);
+        hipLaunchKernelGGL((finish_minmax_kernel<T>), dim3(go), dim3(256), 0, stream, src, out, arg_out, E, K, N, nout, 0);
     }
     return gnnops_check_launch("scatter_elementwise min/max");
 }
@@ -686,6 +773,34 @@ extern "C" size_t gnnops_scatter_elementwise_workspace_bytes(int64_t B, int64_t 
         b += align_up(nout * 4, 256);
     if (reduce == GNNOPS_MEAN) b += align_up(nout * 4, 256);
     return b;
+}
+
+// What the entry point refuses with GNNOPS_EINVAL before it looks at pointers (NULL: nothing), shared with the route query.
+static const char* elem_args_refused(int64_t B, int64_t E, int64_t K, int64_t N, int reduce, int index_bytes, int arg_bytes) {
+    if (!(arg_bytes == 8 || (arg_bytes == 4 && (reduce == GNNOPS_MIN || reduce == GNNOPS_MAX) && E < ((int64_t)1 << 31))))
+        return "arg_bytes (4: min / max with E < 2^31 only)";
+    if (!(B >= 0 && E >= 0 && K >= 0 && N >= 0)) return "negative size";
+    if (!(reduce >= GNNOPS_SUM && reduce <= GNNOPS_MUL)) return "unknown reduce";
+    if (!(index_bytes == 8 || index_bytes == 4 || (index_bytes == 2 && N <= 65536))) return "index_bytes (2: N <= 65536 only)";
+    return nullptr;
+}
+
+// Host only (include/gnnops.h "Route query of the element-wise scatter"): what gnnops_scatter_elementwise_ixa launches for
+// these arguments. GNNOPS_ROUTE_NONE wherever the entry point launches nothing: an empty output, an argument it refuses
+// (GNNOPS_EINVAL), a narrowed index or int32 arg on a shape the LDS forms do not take (GNNOPS_EUNSUPPORTED).
+extern "C" int gnnops_scatter_elementwise_route(int64_t B, int64_t E, int64_t K, int64_t N, int dtype, int reduce, int index_bytes,
+                                                int arg_bytes, uintptr_t src_addr, uintptr_t index_addr, int64_t* detail) {
+    ElemRoute r;
+    const bool ok = !elem_args_refused(B, E, K, N, reduce, index_bytes, arg_bytes) &&
+                    (dtype == GNNOPS_F32 || dtype == GNNOPS_F16 || dtype == GNNOPS_BF16);   // the entry point's switch
+    if (ok && B * N * K != 0)
+        r = elem_route(B, E, K, N, dtype == GNNOPS_F32 ? 4 : 2, reduce, index_bytes, arg_bytes == 4, src_addr, index_addr);
+    if (r.route == GNNOPS_ROUTE_NONE) r = ElemRoute{};
+    if (detail) {
+        const int64_t d[8] = {r.g.tc, r.g.rows, r.g.nchunks, r.threads, r.cell_bytes, r.tshift, r.grid, r.vec4 ? 1 : 0};
+        for (int i = 0; i < 8; ++i) detail[i] = d[i];
+    }
+    return r.route;
 }
 
 extern "C" int gnnops_scatter_elementwise(const void* src, const int64_t* index, void* out, int64_t* arg_out,
@@ -714,13 +829,10 @@ extern "C" int gnnops_scatter_elementwise_ixa(const void* src, const void* index
                                               int init_from_out, void* workspace, size_t workspace_bytes, gnnops_stream_t s) {
     int64_t* arg_out = (int64_t*)arg_out_;
     const int arg32 = arg_bytes == 4 ? 1 : 0;
-    GNNOPS_REQUIRE(arg_bytes == 8 || (arg_bytes == 4 && (reduce == GNNOPS_MIN || reduce == GNNOPS_MAX) && E < ((int64_t)1 << 31)),
-                   GNNOPS_EINVAL, "scatter_elementwise: arg_bytes %d", arg_bytes);
     hipStream_t stream = (hipStream_t)s;
-    GNNOPS_REQUIRE(B >= 0 && E >= 0 && K >= 0 && N >= 0, GNNOPS_EINVAL, "scatter_elementwise: negative size");
-    GNNOPS_REQUIRE(reduce >= GNNOPS_SUM && reduce <= GNNOPS_MUL, GNNOPS_EINVAL, "scatter_elementwise: reduce %d", reduce);
-    GNNOPS_REQUIRE(index_bytes == 8 || index_bytes == 4 || (index_bytes == 2 && N <= 65536), GNNOPS_EINVAL,
-                   "scatter_elementwise: index_bytes %d (N=%lld)", index_bytes, (long long)N);
+    const char* refused = elem_args_refused(B, E, K, N, reduce, index_bytes, arg_bytes);
+    GNNOPS_REQUIRE(!refused, GNNOPS_EINVAL, "scatter_elementwise: %s (reduce=%d index_bytes=%d arg_bytes=%d N=%lld)", refused, reduce,
+                   index_bytes, arg_bytes, (long long)N);
     GNNOPS_REQUIRE(!(reduce == GNNOPS_MEAN && init_from_out), GNNOPS_EINVAL,
                    "scatter_elementwise: mean cannot start from out");
     GNNOPS_REQUIRE((reduce != GNNOPS_MIN && reduce != GNNOPS_MAX) || arg_out != nullptr || init_from_out,

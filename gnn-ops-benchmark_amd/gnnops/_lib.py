@@ -14,7 +14,7 @@ ABI_VERSION = 2   # GNNOPS_ABI_VERSION of include/gnnops.h
 F32, F16, BF16 = 0, 1, 2
 SUM, MEAN, MIN, MAX, MUL = 0, 1, 2, 3, 4
 OK, EINVAL, EWORKSPACE, ELAUNCH, EUNSUPPORTED = 0, 1, 2, 3, 4  # status codes of include/gnnops.h
-ROUTE_NONE, ROUTE_ROWS, ROUTE_K1, ROUTE_LDS, ROUTE_LONGROWS, ROUTE_ELEMS = -1, 0, 1, 2, 3, 4  # enum gnnops_route
+ROUTE_NONE, ROUTE_ROWS, ROUTE_K1, ROUTE_LDS, ROUTE_LONGROWS, ROUTE_ELEMS, ROUTE_LDS_CHUNKS, ROUTE_ATOMICS = -1, 0, 1, 2, 3, 4, 5, 6  # enum gnnops_route
 REDUCE_CODE = {"sum": SUM, "add": SUM, "mean": MEAN, "min": MIN, "max": MAX, "mul": MUL}
 
 # name -> (restype, argtypes); must list every symbol include/gnnops.h declares (tests check this).
@@ -44,6 +44,7 @@ SIGNATURES = {
     "gnnops_scatter_elementwise_workspace_bytes": (_sz, [_i64, _i64, _i64, _ci, _ci]),
     "gnnops_scatter_elementwise": (_ci, [_vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _ci, _ci, _ci, _vp, _sz, _vp]),
     "gnnops_scatter_elementwise_ix": (_ci, [_vp, _vp, _ci, _vp, _vp, _i64, _i64, _i64, _i64, _ci, _ci, _ci, _vp, _sz, _vp]),
+    "gnnops_scatter_elementwise_route": (_ci, [_i64, _i64, _i64, _i64, _ci, _ci, _ci, _ci, _sz, _sz, ctypes.POINTER(_i64)]),
     "gnnops_scatter1d_workspace_bytes": (_sz, [_i64, _i64]),
     "gnnops_scatter1d_minmax": (_ci, [_vp, _vp, _vp, _vp, _i64, _i64, _ci, _ci, _vp, _sz, _vp]),
     "gnnops_scatter1d_sum": (_ci, [_vp, _vp, _vp, _i64, _i64, _ci, _ci, _vp, _sz, _vp]),

@@ -330,6 +330,14 @@ _FUSED_MAX_MIN_NUMEL = 1 << 26        # from here on a pass over the index costs
 _FUSED_MAX_SAMPLE = 1 << 20           # ids looked at to guess whether the destinations will fit an LDS strip
 
 
+def _strip_overflows(N, reduce, elem_size, E):
+    """Whether N destinations of ONE column do not fit an LDS strip of the layout-F kernel (csrc/scatter_elem.hip: 4-byte
+    cells for sums, products and 16-bit min / max with E < 65535, 8-byte cells otherwise) — where
+    gnnops_scatter_elementwise_route stops answering LDS for a single column (tests/test_scatter_elem_routes_cpu.py)."""
+    cell = 4 if (reduce in ("sum", "add", "mul") or (reduce in ("min", "max") and elem_size == 2 and E < 65535)) else 8
+    return N * cell > _LDS_STRIP_BYTES
+
+
 def _row_index_of(index, src, dim):
     """Return a contiguous 1-D index if `index` is (a broadcast of) a row index along `dim`, else None."""
     if index.dim() == 1 and index.numel() == src.size(dim):
@@ -461,9 +469,8 @@ def scatter(src, index, dim=-1, out=None, dim_size=None, reduce="sum"):
                 # it takes the transposed route below, whose index transpose can find index.max() on the way. Whether they
                 # fit is a question about that same max: the first 2^20 ids answer it (uniform ids: to a part in a million);
                 # a wrong guess costs time, never correctness — both routes are complete for any N.
-                cell = 4 if (reduce in ("sum", "add", "mul") or (reduce in ("min", "max") and src.element_size() == 2 and E < 65535)) else 8
                 guess = _index_max_now(index.view(-1)[:_FUSED_MAX_SAMPLE]) + 1
-                if guess * cell > _LDS_STRIP_BYTES:
+                if _strip_overflows(guess, reduce, src.element_size(), E):
                     res = _scatter_transposed(src.view(E, K), index.view(E, K), None, reduce, rcode, dt, L)
                     if isinstance(res, int):
                         N = res                      # route refused after the size was found: carry on with the size
@@ -479,8 +486,7 @@ def scatter(src, index, dim=-1, out=None, dim_size=None, reduce="sum"):
             if N is None:
                 N = index_max(index if row_index is None else row_index) + 1 if index.numel() else 0
         if row_index is None and B == 1 and K > 1 and E < 2 ** 31:
-            cell = 4 if (reduce in ("sum", "add", "mul") or (reduce in ("min", "max") and src.element_size() == 2 and E < 65535)) else 8
-            if N * cell > _LDS_STRIP_BYTES:
+            if _strip_overflows(N, reduce, src.element_size(), E):
                 # layout F along dim 0 of a matrix whose destinations do not fit an LDS strip (the reference's (38000, 38000)
                 # shapes, data/scatter_max.csv:32-33): the element kernel would re-scan every column strip once per chunk of
                 # destinations, through 16-B-wide column pieces. Along the LAST dim the same problem streams whole rows, so:

@@ -165,8 +165,16 @@ int gnnops_index_select_planned_hubs(const void* input, const int32_t* rowptr, c
  *   init_from_out == 0 : the call initialises out itself (0 / identity) and, for MIN/MAX, sets groups
  *                        nothing reached to 0 (needs arg_out); MEAN divides by max(count, 1).
  *   init_from_out != 0 : contributions are combined into the existing out (`out=` / in-place forms).
- * SUM/MEAN on 16-bit types use an fp32 scratch of B*N*K floats in `workspace` (MEAN: one more for
- * the counts). MIN/MAX: value pass, then an arg pass choosing the smallest e among ties.
+ * The memory-side-atomic form of SUM/MEAN/MUL on 16-bit types uses an fp32 scratch of B*N*K floats in
+ * `workspace` (MEAN: one more for the counts), and its MIN/MAX is a value pass, then an arg pass choosing
+ * the smallest e among ties. The LDS-strip forms use no workspace and are ONE pass: a min / max cell holds
+ * the value's order image and the position together, so the extremum and its smallest position come out of
+ * the same sweep. An id outside [0, N) is dropped by the LDS-strip forms; the atomic form does not look at
+ * ids, so every id must lie in [0, N) there. gnnops_scatter_elementwise_route tells which form takes a call.
+ * MIN/MAX in every form: the sequential loop's result — a contribution replaces on a strict improvement only, so out
+ * (init_from_out) wins a tie and keeps arg = E, the smallest position wins among contributions, and a zero extremum has
+ * the sign of the element arg names (-0.0 == +0.0). The atomic form needs arg_out for that last point: with
+ * arg_out == NULL (init_from_out only) the sign of a zero extremum is that of any of the tied zeros.
  * ------------------------------------------------------------------------------------------- */
 size_t gnnops_scatter_elementwise_workspace_bytes(int64_t B, int64_t N, int64_t K, int dtype, int reduce);
 int gnnops_scatter_elementwise(const void* src, const int64_t* index, void* out, int64_t* arg_out,
@@ -190,6 +198,24 @@ int gnnops_scatter_elementwise_ixa(const void* src, const void* index, int index
 /* out[i] = (int32 / uint16) index[i], i < n, for ids in [0, bound); an id outside becomes all ones (-1 / 0xFFFF — never a valid
  * id: bound <= 65535 for out_bytes 2, < 2^31 for 4), which the element kernels drop as they drop it in the int64 index. */
 int gnnops_narrow_index(const int64_t* index, void* out, int64_t n, int out_bytes, int64_t bound, gnnops_stream_t stream);
+
+/* Route query of the element-wise scatter (host only, no device is touched): the form gnnops_scatter_elementwise_ixa
+ * launches for these arguments — it calls the same function and launches what it says, so the thresholds exist there only.
+ * `src_addr` / `index_addr` are the base addresses (only their low four bits matter). Returns
+ *   GNNOPS_ROUTE_LDS         one LDS strip of all N destinations per (b, column strip)
+ *   GNNOPS_ROUTE_LDS_CHUNKS  the destinations cut into nchunks (2 .. 16) chunks of `rows`; each re-scans the strip's source
+ *   GNNOPS_ROUTE_ATOMICS     memory-side atomics (int64 index and int64 arg rows only)
+ *   GNNOPS_ROUTE_NONE        nothing is launched: B*N*K == 0, an argument the entry point refuses (GNNOPS_EINVAL), or a
+ *                            narrowed index / int32 arg on a shape the LDS forms do not take (GNNOPS_EUNSUPPORTED)
+ * and fills detail[0..7] (may be NULL):
+ *   [0] tc       columns per strip                     [4] cell_bytes  LDS bytes per destination and column (4 or 8)
+ *   [1] rows     destinations per chunk (N: one chunk) [5] tshift      2^tshift >= tc lanes per source row
+ *   [2] nchunks                                        [6] grid        workgroups: B * ceil(K / tc) * nchunks
+ *   [3] threads  per workgroup (256 / 512 / 1024)      [7] flags       bit 0: K == 1 fp32, four elements per lane and load
+ * ATOMICS: threads = 256, grid = that of the launches over the source, cell_bytes as the LDS forms would have had; the rest 0.
+ * NONE: all 0. */
+int gnnops_scatter_elementwise_route(int64_t B, int64_t E, int64_t K, int64_t N, int dtype, int reduce, int index_bytes,
+                                     int arg_bytes, uintptr_t src_addr, uintptr_t index_addr, int64_t* detail);
 
 /* torch_scatter.scatter_min / scatter_max of a LONG 1-D tensor (benchmark_scatter_min.py:15-18 at the reference's ">= 95 % of
  * memory" shapes, data/scatter_min.csv:2: 1 472 353 280 fp32 elements): src [E], index [E] int64, out [N], arg_out [N] int64.
@@ -266,7 +292,9 @@ enum gnnops_route {
     GNNOPS_ROUTE_K1 = 1,
     GNNOPS_ROUTE_LDS = 2,
     GNNOPS_ROUTE_LONGROWS = 3,
-    GNNOPS_ROUTE_ELEMS = 4
+    GNNOPS_ROUTE_ELEMS = 4,
+    GNNOPS_ROUTE_LDS_CHUNKS = 5,   /* gnnops_scatter_elementwise_route only */
+    GNNOPS_ROUTE_ATOMICS = 6       /* gnnops_scatter_elementwise_route only */
 };
 int gnnops_index_select_route(int64_t B, int64_t N, int64_t K, int64_t E, int elem_bytes, uintptr_t input_addr,
                               uintptr_t out_addr, int* detail);

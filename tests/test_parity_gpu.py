@@ -170,7 +170,8 @@ def test_scatter_row_index_bit_exact(gnnops, oracle, shape, dim, N, dname):
                                          ((3000, 300), 0, 1500),     # LDS form, strips of 12-24 columns
                                          ((50000, 6), 0, 45000),     # destinations cut into LDS chunks (re-scan form)
                                          ((700000, 2), 0, 690000),   # too many chunks: global atomics
-                                         ((7, 60000), 1, 50000)])    # K == 1, global atomics
+                                         ((7, 60000), 1, 50000),     # K == 1, chunked LDS form: 2 chunks of 40832 (4-byte cells), 3 of 20416 (8-byte)
+                                         ((3, 3000), 1, 660000)])    # K == 1, global atomics: more than 16 chunks of 40832
 def test_scatter_full_index(gnnops, oracle, shape, dim, N, dname):
     g = torch.Generator().manual_seed(43)
     src = (torch.rand(shape, generator=g) + 0.5).to(TORCH_DT[dname])  # positive, O(1): products stay finite
