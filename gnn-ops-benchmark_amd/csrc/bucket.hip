@@ -6,7 +6,7 @@
 //      bucket = destination >> 8 (256 consecutive output rows), in source order inside a bucket;
 //   2. bucket_bounds_kernel: one binary search per bucket boundary (no pass over the keys);
 //   3. bucket_reduce_kernel: a workgroup takes a bucket, finishes the sort ON CHIP — a stable counting sort of its
-//      (destination & 255, source position) pairs in LDS, ballot ranking as in sort_engine_impl.h — and then runs the
+//      (destination & 255, source position) pairs in LDS, the chunk sort of lds_sort.h — and then runs the
 //      segment reduction of segment.hip with the permutation and row pointers read from LDS instead of HBM.
 //
 // Same arithmetic and order as seg_rows_kernel (contributions of a destination in ascending source position), so the
@@ -19,6 +19,7 @@
 // 16-bit sums / means / products on the plan path, where the fp32 accumulator is rounded once.
 #include "common.h"
 #include "hub.h"
+#include "lds_sort.h"
 #include "sort_engine.h"
 
 namespace {
@@ -29,7 +30,6 @@ constexpr int ROUNDS = 16, CAP = THREADS * ROUNDS;  // entries sorted on chip at
 constexpr int U = 8;                                // contribution rows in flight per lane group
 constexpr bool NT = true;
 
-inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 inline int key_bits(int64_t N) {
     int bits = 1;
     while (bits < 32 && ((int64_t)1 << bits) < N) ++bits;
@@ -57,73 +57,12 @@ __device__ inline u32x4 load16_coherent(const T* p) {
 
 // Stable counting sort, in LDS, of the n <= CAP (key & 255, position) pairs at [cbeg, cbeg + n): s_perm gets the positions
 // grouped by key in their original order, s_rowptr[0..256] the group boundaries. Returns the size of group `threadIdx.x`.
-// Ranking as in sort_engine_impl.h: a wave owns consecutive rows of 64 pairs; eight ballots give every lane the mask of
-// its equal-key lanes; the lowest of them does ONE returning LDS add for the group. The caller must have passed a
-// barrier since the last readers of the LDS arrays; s_perm / s_rowptr are valid after the caller's next barrier.
+// The chunk sort of lds_sort.h (barrier contract there), histograms zeroed inside.
 __device__ inline uint32_t sort_chunk(const uint32_t* __restrict__ keys, const uint32_t* __restrict__ vals, int32_t cbeg, int n,
                                       int32_t* s_perm, uint32_t* s_whist, int32_t* s_rowptr, uint32_t* s_tmp) {
-    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-    const uint64_t lanes_below = (lane == 0) ? 0ull : (~0ull >> (64 - lane));
-    uint32_t* whist = s_whist + wave * 256;
-    for (int i = tid; i < WAVES * 256; i += THREADS) s_whist[i] = 0;
-    __syncthreads();
-    const int rounds_n = (n + THREADS - 1) / THREADS;   // rows of 64 per wave
-    const int wave_base = wave * rounds_n * 64;
-    uint32_t dg[ROUNDS], vv[ROUNDS], rk[ROUNDS];
-    uint32_t is_leader = 0;
-#pragma unroll
-    for (int r = 0; r < ROUNDS; ++r) {
-        dg[r] = 0; vv[r] = 0; rk[r] = 0;
-        if (r < rounds_n) {
-            const int i = wave_base + r * 64 + lane;
-            const bool valid = i < n;
-            if (valid) {
-                dg[r] = keys[cbeg + i] & (BROWS - 1);
-                vv[r] = vals[cbeg + i];
-            }
-            const uint32_t d = dg[r];
-            const uint64_t m = match_digit8(d, __ballot(valid));   // valid lanes with my key
-            const uint32_t below = __popcll(m & lanes_below);
-            if (valid && below == 0) {
-                rk[r] = atomicAdd(&whist[d], (uint32_t)__popcll(m));  // rank of the group inside this wave
-                is_leader |= 1u << r;
-            } else {
-                rk[r] = below | ((uint32_t)(__ffsll((unsigned long long)m) - 1) << 16);
-            }
-        }
-    }
-#pragma unroll
-    for (int r = 0; r < ROUNDS; ++r) {
-        if (r < rounds_n) {
-            const bool lead = (is_leader >> r) & 1u;
-            const int from = lead ? lane : (int)((rk[r] >> 16) & 63u);
-            const uint32_t p = __shfl(rk[r], from);
-            rk[r] = lead ? p : p + (rk[r] & 0xffffu);
-        }
-    }
-    __syncthreads();
-    // key offsets: exclusive over waves, then over keys (thread d owns key d)
-    uint32_t tot = 0;
-#pragma unroll
-    for (int w = 0; w < WAVES; ++w) {
-        const uint32_t c = s_whist[w * 256 + tid];
-        s_whist[w * 256 + tid] = tot;
-        tot += c;
-    }
-    const uint32_t start = block_excl_scan_u32<WAVES>(tot, s_tmp, nullptr);
-#pragma unroll
-    for (int w = 0; w < WAVES; ++w) s_whist[w * 256 + tid] += start;
-    s_rowptr[tid] = (int32_t)start;
-    if (tid == BROWS - 1) s_rowptr[BROWS] = (int32_t)(start + tot);
-    __syncthreads();
-#pragma unroll
-    for (int r = 0; r < ROUNDS; ++r) {
-        if (r < rounds_n) {
-            const int i = wave_base + r * 64 + lane;
-            if (i < n) s_perm[whist[dg[r]] + rk[r]] = (int32_t)vv[r];
-        }
-    }
-    return tot;
+    return ldssort::sort_chunk<THREADS, ROUNDS, false>(
+        n, [&](int i) { return ldssort::Item{keys[cbeg + i] & (BROWS - 1), vals[cbeg + i]}; },
+        reinterpret_cast<uint32_t*>(s_perm), s_whist, s_rowptr, s_tmp);
 }
 
 // Hub detection for a large bucket (cold path, kept out of line so that its registers do not add to the row walk's):
@@ -441,13 +380,13 @@ inline Layout layout(int64_t E, int64_t N) {
     Layout l{};
     const size_t tiles = (size_t)gnnops_cdiv(E > 0 ? E : 1, sortengine::TILE);
     size_t o = 0;
-    l.keys_a = o; o += align_up((size_t)E * 4, 256);
-    l.keys_b = o; o += align_up((size_t)E * 4, 256);
-    l.vals_a = o; o += align_up((size_t)E * 4, 256);
-    l.vals_b = o; o += align_up((size_t)E * 4, 256);
-    l.tile_hist = o; o += align_up(256 * tiles * 4, 256);
+    l.keys_a = o; o += gnnops_align_up((size_t)E * 4, 256);
+    l.keys_b = o; o += gnnops_align_up((size_t)E * 4, 256);
+    l.vals_a = o; o += gnnops_align_up((size_t)E * 4, 256);
+    l.vals_b = o; o += gnnops_align_up((size_t)E * 4, 256);
+    l.tile_hist = o; o += gnnops_align_up(256 * tiles * 4, 256);
     l.digit_total = o; o += 256 * 4;
-    l.bptr = o; o += align_up(((size_t)gnnops_cdiv(N, BROWS) + 1) * 4, 256);
+    l.bptr = o; o += gnnops_align_up(((size_t)gnnops_cdiv(N, BROWS) + 1) * 4, 256);
     l.total = o;
     return l;
 }

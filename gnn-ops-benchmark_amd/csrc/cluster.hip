@@ -109,11 +109,6 @@ __global__ __launch_bounds__(256) void knn_kernel(const T* __restrict__ x, const
 // about k (1 + ln(n / k)) insertions, so a query costs n / 64 distance evaluations per lane instead of k n / 64: the k rounds of
 // knn_kernel above compute every distance k times. Keys are strictly ordered (distance image, then index), so the result is
 // the brute-force one: nearest first, ties to the smaller index, NaN distances never chosen.
-__device__ inline uint32_t knn_order(float v) {
-    uint32_t u = __float_as_uint(v);
-    if (u == 0x80000000u) u = 0u;
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
 // lane `src` (the same in every lane) of a 64-bit value: two v_readlane, no trip through the LDS crossbar
 __device__ inline uint64_t shfl_u64(uint64_t v, int src) {
     const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)v, src);
@@ -143,7 +138,7 @@ __global__ __launch_bounds__(256) void knn_topk_kernel(const T* __restrict__ x, 
             uint64_t key = NONE;
             if (i < xe) {
                 const float d = COSINE ? cos_dist<T>(x + i * D, yq, D) : dist2<T>(x + i * D, yq, D);
-                if (d == d) key = ((uint64_t)knn_order(d) << 32) | (uint32_t)(i - xb);
+                if (d == d) key = ((uint64_t)f32_order(d) << 32) | (uint32_t)(i - xb);
             }
             uint64_t todo = __ballot(key < kth);
             while (todo) {
@@ -175,7 +170,7 @@ struct KnnGrid {
 };
 
 __global__ void knn_bbox_kernel(const float* __restrict__ x, int64_t n, int D, unsigned* __restrict__ box) {
-    // box[0..2] = min image, box[3..5] = max image per axis (knn_order images: unsigned order == float order); non-finite skipped
+    // box[0..2] = min image, box[3..5] = max image per axis (f32_order images: unsigned order == float order); non-finite skipped
     float lo[3] = {__builtin_huge_valf(), __builtin_huge_valf(), __builtin_huge_valf()};
     float hi[3] = {-__builtin_huge_valf(), -__builtin_huge_valf(), -__builtin_huge_valf()};
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
@@ -192,21 +187,20 @@ __global__ void knn_bbox_kernel(const float* __restrict__ x, int64_t n, int D, u
         }
         if ((threadIdx.x & 63) == 0) {
             if (lo[d] <= hi[d]) {
-                atomicMin(box + d, knn_order(lo[d]));
-                atomicMax(box + 3 + d, knn_order(hi[d]));
+                atomicMin(box + d, f32_order(lo[d]));
+                atomicMax(box + 3 + d, f32_order(hi[d]));
             }
         }
     }
 }
 
-__device__ inline float knn_unorder(uint32_t img) { return __uint_as_float((img & 0x80000000u) ? (img & 0x7fffffffu) : ~img); }
 
 __device__ inline KnnGrid knn_grid_of(const unsigned* __restrict__ box, int D, int G) {
     KnnGrid g;
     for (int d = 0; d < 3; ++d) {
         g.lo[d] = 0.f; g.h[d] = 0.f; g.g[d] = 1;
         if (d < D) {
-            const float lo = knn_unorder(box[d]), hi = knn_unorder(box[3 + d]);
+            const float lo = f32_unorder(box[d]), hi = f32_unorder(box[3 + d]);
             if (lo <= hi) {       // at least one finite coordinate on this axis
                 g.lo[d] = lo;
                 g.h[d] = (hi - lo) / (float)G;
@@ -261,7 +255,7 @@ __global__ __launch_bounds__(256) void knn_grid_kernel(const float* __restrict__
                     const int i = perm[p];
                     const float d = dist2<float>(x + (int64_t)i * D, yq, D);
                     if constexpr (RADIUS) { if (d < r2) key = (uint64_t)(uint32_t)i; }
-                    else if (d == d) key = ((uint64_t)knn_order(d) << 32) | (uint32_t)i;
+                    else if (d == d) key = ((uint64_t)f32_order(d) << 32) | (uint32_t)i;
                 }
                 uint64_t todo = __ballot(key < kth);
                 while (todo) {
@@ -314,7 +308,7 @@ __global__ __launch_bounds__(256) void knn_grid_kernel(const float* __restrict__
             }
             if (whole) break;
             if constexpr (RADIUS) { if (bound > 0.f && bound * bound >= r2) break; }
-            else if (kth != NONE && bound > 0.f && knn_unorder((uint32_t)(kth >> 32)) < bound * bound) break;
+            else if (kth != NONE && bound > 0.f && f32_unorder((uint32_t)(kth >> 32)) < bound * bound) break;
         }
         if (lane < k) col[qy * k + lane] = mine == NONE ? (int64_t)-1 : (int64_t)(uint32_t)mine;
     }
@@ -370,7 +364,7 @@ __device__ inline uint64_t wave_max_u64(uint64_t v) {
 }
 // (distance, index) -> a key whose maximum is the farthest point, the smaller index among equals (rel = index - segment start);
 // 0 = "no point" loses to every key
-__device__ inline uint64_t fps_key(float d, uint32_t rel) { return ((uint64_t)knn_order(d) << 32) | (0xffffffffu - rel); }
+__device__ inline uint64_t fps_key(float d, uint32_t rel) { return ((uint64_t)f32_order(d) << 32) | (0xffffffffu - rel); }
 
 // ---- fps: one workgroup per batch segment; dist[] = squared distance to the nearest chosen point so far ----
 template <typename T, int DD>

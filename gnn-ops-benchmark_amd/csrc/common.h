@@ -22,6 +22,7 @@ int gnnops_check_launch(const char* what);
     } while (0)
 
 static inline int64_t gnnops_cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
+static inline size_t gnnops_align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
 // Memory-bound launches: enough workgroups to fill 256 CUs several times over, grid-stride the rest
 // (cdna_hip_programming.md Guideline 11).
@@ -161,6 +162,25 @@ template <> struct Red<GNNOPS_MAX> {
 };
 
 __device__ static inline int lane_id() { return threadIdx.x & 63; }
+
+// ---- order images of fp32: unsigned order of the image == float order of the value ----
+// -0.0 is folded onto +0.0 (they compare equal); NaNs land outside [-inf, +inf] on the side of their sign, so whoever must
+// not let a NaN win excludes it before. f32_unorder inverts the image (of a folded zero: +0.0).
+__host__ __device__ inline uint32_t f32_order_bits(uint32_t u) {   // of the value with bits u
+    if (u == 0x80000000u) u = 0u;
+    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+__host__ __device__ inline uint32_t f32_order(float v) { return f32_order_bits(__builtin_bit_cast(uint32_t, v)); }
+__host__ __device__ inline float f32_unorder(uint32_t o) {
+    return __builtin_bit_cast(float, (o & 0x80000000u) ? (o & 0x7fffffffu) : ~o);
+}
+// the sort key (sort.hip, sort_rows.hip): the image, with every NaN at 0xffffffff — behind +inf, like torch.sort
+__host__ __device__ inline uint32_t f32_key(float x) {
+    uint32_t u = __builtin_bit_cast(uint32_t, x);
+    if (u == 0x80000000u) u = 0u;
+    if ((u & 0x7fffffffu) > 0x7f800000u) return 0xffffffffu;
+    return f32_order_bits(u);
+}
 
 // ---- launch order -> work item, XCD-aware ----
 // Consecutive block ids go round-robin to the 8 XCDs (each with its own L2; MI355X_MICROARCH.md "Workgroup dispatch"), so

@@ -141,13 +141,6 @@ __global__ __launch_bounds__(256) void select_elems_kernel(const U* __restrict__
 constexpr int GL_THREADS = 1024;
 constexpr size_t GL_BUDGET = 160 * 1024 - 512;
 
-// Consecutive block ids go round-robin to the 8 XCDs; give each XCD a contiguous run of work items so that neighbouring
-// column strips (which share the 64/128-B lines of every input / index row) stream through the same L2.
-__device__ inline int64_t gl_xcd_contiguous(int64_t bid, int64_t total) {
-    const int64_t q = total / 8, r = total % 8, x = bid % 8;
-    return x * q + (x < r ? x : r) + bid / 8;
-}
-
 template <typename U, bool FULL_INDEX>
 __global__ __launch_bounds__(GL_THREADS) void gather_lds_kernel(const U* __restrict__ in, const int64_t* __restrict__ index,
                                                                 U* __restrict__ out, int64_t B, int64_t N, int64_t K,
@@ -156,7 +149,8 @@ __global__ __launch_bounds__(GL_THREADS) void gather_lds_kernel(const U* __restr
     U* tile = reinterpret_cast<U*>(gl_raw);
     constexpr int UNR = 8;  // loads in flight per thread (unconditional, on clamped rows: a load under a branch is
                             // waited for inside the branch)
-    const int64_t item = gl_xcd_contiguous(blockIdx.x, gridDim.x);
+    // neighbouring column strips share the 64/128-B lines of every input / index row: one XCD's L2 streams them
+    const int64_t item = xcd_contiguous(blockIdx.x, gridDim.x);
     const int64_t b = item / strips;
     const int64_t k0 = (int64_t)(item % strips) * TC;
     const int tc = (int)((K - k0 < TC) ? (K - k0) : TC);

@@ -1283,7 +1283,6 @@ __global__ void pad_tail_kernel(const uint16_t* __restrict__ A, const uint16_t* 
     }
 }
 
-inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 inline int64_t round_up(int64_t v, int64_t m) { return (v + m - 1) / m * m; }
 
 // How a 16-bit problem is run. The LDS-DMA kernels take any M and N (filler rows / columns, guarded epilogue) but whole
@@ -1339,10 +1338,10 @@ inline GemmPlan gemm_plan(int64_t M, int64_t N, int64_t K) {
         g.tail_a = need && !g.copy_a;
         g.tail_b = need && !g.copy_b;
         g.Kmain = (g.tail_a || g.tail_b) ? (K % 64 ? K - K % 64 : K - 64) : g.Kp;
-        g.a_bytes = g.copy_a ? align_up((size_t)M * g.lda * 2, 256) : 0;
-        g.b_bytes = g.copy_b ? align_up((size_t)g.Kp * g.ldb * 2, 256) : 0;
-        g.at_bytes = g.tail_a ? align_up((size_t)M * 64 * 2, 256) : 0;
-        g.bt_bytes = g.tail_b ? align_up(((size_t)64 * N + 8) * 2, 256) : 0;
+        g.a_bytes = g.copy_a ? gnnops_align_up((size_t)M * g.lda * 2, 256) : 0;
+        g.b_bytes = g.copy_b ? gnnops_align_up((size_t)g.Kp * g.ldb * 2, 256) : 0;
+        g.at_bytes = g.tail_a ? gnnops_align_up((size_t)M * 64 * 2, 256) : 0;
+        g.bt_bytes = g.tail_b ? gnnops_align_up(((size_t)64 * N + 8) * 2, 256) : 0;
         if (g.path == 2) {
             g.sk_split = sk_split_of(gnnops_cdiv(M, BM2) * gnnops_cdiv(N, BN2), cu_count());
             g.sk_bytes = g.sk_split > 1 ? sk_workspace_bytes(cu_count()) : 0;

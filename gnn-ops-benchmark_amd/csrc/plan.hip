@@ -187,7 +187,6 @@ __global__ __launch_bounds__(SMALL_THREADS) void plan_small_kernel(const int64_t
     }
 }
 
-inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
 int key_bits_for(int64_t N) {
     int bits = 1;
@@ -218,11 +217,11 @@ extern "C" size_t gnnops_plan_workspace_bytes(int64_t E, int64_t N) {
     if (E < 0 || N < 0) return 0;
     size_t tiles = (size_t)gnnops_cdiv(E > 0 ? E : 1, sortengine::TILE);
     size_t b = 0;
-    b += 3 * align_up((size_t)E * 4, 256);
-    b += align_up(256 * tiles * 4, 256);
+    b += 3 * gnnops_align_up((size_t)E * 4, 256);
+    b += gnnops_align_up(256 * tiles * 4, 256);
     b += 256 * 4;
     b += 256;
-    b += align_up(3 * ((size_t)N / GAP_INLINE + 2) * 4, 256);
+    b += gnnops_align_up(3 * ((size_t)N / GAP_INLINE + 2) * 4, 256);
     return b;
 }
 
@@ -246,10 +245,10 @@ extern "C" int gnnops_plan_build(const int64_t* index, int64_t E, int64_t N, int
 
     const size_t tiles = (size_t)gnnops_cdiv(E, sortengine::TILE);
     char* w = (char*)workspace;
-    uint32_t* keys_a = (uint32_t*)w; w += align_up((size_t)E * 4, 256);
-    uint32_t* keys_b = (uint32_t*)w; w += align_up((size_t)E * 4, 256);
-    uint32_t* vals_x = (uint32_t*)w; w += align_up((size_t)E * 4, 256);
-    uint32_t* tile_hist = (uint32_t*)w; w += align_up(256 * tiles * 4, 256);
+    uint32_t* keys_a = (uint32_t*)w; w += gnnops_align_up((size_t)E * 4, 256);
+    uint32_t* keys_b = (uint32_t*)w; w += gnnops_align_up((size_t)E * 4, 256);
+    uint32_t* vals_x = (uint32_t*)w; w += gnnops_align_up((size_t)E * 4, 256);
+    uint32_t* tile_hist = (uint32_t*)w; w += gnnops_align_up(256 * tiles * 4, 256);
     uint32_t* digit_total = (uint32_t*)w; w += 256 * 4;
     unsigned int* gap_count = (unsigned int*)w; w += 256;
     int32_t* gap_list = (int32_t*)w;
@@ -314,7 +313,7 @@ extern "C" int gnnops_plan_build_small(const int64_t* index, const int64_t* comp
 // rowptr of an already sorted int64 index (torch_scatter.segment_coo's input contract; also CSR <- sorted COO rows).
 extern "C" size_t gnnops_rowptr_workspace_bytes(int64_t N) {
     if (N < 0) return 0;
-    return 256 + align_up(3 * ((size_t)N / GAP_INLINE + 2) * 4, 256);
+    return 256 + gnnops_align_up(3 * ((size_t)N / GAP_INLINE + 2) * 4, 256);
 }
 
 extern "C" int gnnops_rowptr_from_sorted(const int64_t* sorted_index, int64_t E, int64_t N, int32_t* rowptr,

@@ -23,12 +23,13 @@
 // Sums / means / products (gnnops_scatter1d_sum) keep the sequential order of the oracle — LDS float atomics would not —
 // so there the sort goes one pass further, to buckets of 256 destinations (bits 8 and up: three passes at 31 bits), and a
 // 256-thread workgroup finishes a bucket as bucket.hip does for rows: a stable counting sort of its (destination & 255, value)
-// pairs in LDS (ballot ranking, chunks of 4096 in source order), then thread d adds destination d's values one after the
+// pairs in LDS (the chunk sort of lds_sort.h, chunks of 1024 in source order), then thread d adds destination d's values one after the
 // other, in source position order: bit-identical to the sequential loop. No position travels (means count their lists).
 //
 // HBM-bound, and no random access anywhere: per element ~100 B of streamed traffic (first pass 12 + 12 read, 12 written;
 // second 8 + 12 read, 12 written; reduce 12 + 12 read) + 12 B written per destination.
 #include "common.h"
+#include "lds_sort.h"
 #include "sort_engine.h"
 
 namespace {
@@ -36,7 +37,6 @@ namespace {
 constexpr int LOW = 15, BUCKET = 1 << LOW;     // destinations per bucket = LDS table entries (4 B each: 128 KiB)
 constexpr int RTHREADS = 1024;
 
-inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 inline int bits_of(int64_t v) {   // smallest b with (1 << b) > v
     int b = 0;
     while (b < 40 && ((int64_t)1 << b) <= v) ++b;
@@ -51,13 +51,13 @@ inline Layout1d layout1d(int64_t E, int64_t N) {
     Layout1d l{};
     const size_t tiles = (size_t)gnnops_cdiv(E > 0 ? E : 1, sortengine::TILE);
     size_t o = 0;
-    l.keys_a = o; o += align_up((size_t)E * 8, 256);
-    l.keys_b = o; o += align_up((size_t)E * 8, 256);
-    l.vals_a = o; o += align_up((size_t)E * 4, 256);
-    l.vals_b = o; o += align_up((size_t)E * 4, 256);
-    l.tile_hist = o; o += align_up(256 * tiles * 4, 256);
+    l.keys_a = o; o += gnnops_align_up((size_t)E * 8, 256);
+    l.keys_b = o; o += gnnops_align_up((size_t)E * 8, 256);
+    l.vals_a = o; o += gnnops_align_up((size_t)E * 4, 256);
+    l.vals_b = o; o += gnnops_align_up((size_t)E * 4, 256);
+    l.tile_hist = o; o += gnnops_align_up(256 * tiles * 4, 256);
     l.digit_total = o; o += 256 * 4;
-    l.bptr = o; o += align_up(((size_t)gnnops_cdiv(N > 0 ? N : 1, 256) + 2) * 8, 256);   // sized for the finer (256-row) buckets of the sums
+    l.bptr = o; o += gnnops_align_up(((size_t)gnnops_cdiv(N > 0 ? N : 1, 256) + 2) * 8, 256);   // sized for the finer (256-row) buckets of the sums
     l.desc = o; o += 256;
     l.total = o;
     return l;
@@ -84,15 +84,6 @@ __global__ void bounds1d_kernel(const uint64_t* __restrict__ keys, int64_t E, in
     bptr[b] = lo;
 }
 
-// order-preserving u32 image of a float, -0.0 folded onto +0.0
-__device__ inline uint32_t ordered_of(uint32_t u) {
-    if (u == 0x80000000u) u = 0u;
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ inline float float_of_ordered(uint32_t o) {
-    return __uint_as_float((o & 0x80000000u) ? (o & 0x7fffffffu) : ~o);
-}
-
 // HOLD keys per thread stay in REGISTERS between the value phase and the position phase (24 x 1024 = 24576 pairs — more spills: the 128 registers a lane of a 1024-thread workgroup has hold 48 for the keys — of the mean
 // 32768-pair bucket of the reference's shape, E = N; what a bucket holds beyond that is streamed in both phases), so a bucket's keys are read from HBM once; the
 // positions are read in the second phase only.
@@ -112,7 +103,7 @@ __global__ __launch_bounds__(RTHREADS) void minmax1d_kernel(const uint64_t* __re
         const uint32_t bits = (uint32_t)k;
         if (skip(bits)) return;
         const uint32_t d = (uint32_t)(k >> 32) & (BUCKET - 1);
-        if (IS_MIN) atomicMin(&tab[d], ordered_of(bits)); else atomicMax(&tab[d], ordered_of(bits));
+        if (IS_MIN) atomicMin(&tab[d], f32_order_bits(bits)); else atomicMax(&tab[d], f32_order_bits(bits));
     };
     for (int64_t b = blockIdx.x; b < NB; b += gridDim.x) {
         const int64_t beg = bptr[b], end = bptr[b + 1];
@@ -160,7 +151,7 @@ __global__ __launch_bounds__(RTHREADS) void minmax1d_kernel(const uint64_t* __re
         // b. store the values; c. the table turns into positions
         for (int d = tid; d < BUCKET; d += RTHREADS) {
             const uint32_t o = tab[d];
-            if (d < nd) Elem<T>::store(out + d0 + d, o == EMPTY ? 0.f : float_of_ordered(o));
+            if (d < nd) Elem<T>::store(out + d0 + d, o == EMPTY ? 0.f : f32_unorder(o));
         }
         __syncthreads();   // orders the stores above before this workgroup's loads of them below
         for (int d = tid; d < BUCKET; d += RTHREADS) tab[d] = 0xffffffffu;
@@ -211,82 +202,6 @@ constexpr int STHREADS = 256, SWAVES = STHREADS / 64, SROUNDS = 4, SCAP = STHREA
 // reference shape holds ~256; four rounds keep the kernel at 64 registers, i.e. EIGHT workgroups per CU — the finish is a chain of
 // barriers and dependent LDS steps per bucket (5.75 M buckets), and what hides that latency is other buckets in flight
 
-// Stable counting sort, in LDS, of the n <= SCAP pairs at keys[cbeg .. cbeg + n) by (destination & 255): s_val gets the VALUE
-// bits grouped by destination in their original order, s_rowptr[0..256] the group boundaries (bucket.hip's sort_chunk with
-// the value instead of a position as payload). Ranking as in sort_engine_impl.h: per row of 64 pairs, eight ballots give every
-// lane its equal-key lanes; the lowest of them does ONE returning LDS add. Returns the size of group `threadIdx.x`.
-__device__ inline uint32_t sort_chunk64(const uint64_t* __restrict__ keys, int64_t cbeg, int n, uint32_t* s_val, uint32_t* s_whist,
-                                        int32_t* s_rowptr, uint32_t* s_tmp) {
-    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-    const uint64_t lanes_below = (lane == 0) ? 0ull : (~0ull >> (64 - lane));
-    uint32_t* whist = s_whist + wave * 256;   // zeroed by the caller behind a barrier (sum1d_kernel: one barrier fewer per chunk)
-    const int rounds_n = (n + STHREADS - 1) / STHREADS;   // rows of 64 per wave
-    const int wave_base = wave * rounds_n * 64;
-    uint32_t dg[SROUNDS], vv[SROUNDS], rk[SROUNDS];
-    uint32_t is_leader = 0;
-#pragma unroll
-    for (int r = 0; r < SROUNDS; ++r) {
-        dg[r] = 0; vv[r] = 0; rk[r] = 0;
-        if (r < rounds_n) {
-            const int i = wave_base + r * 64 + lane;
-            const bool valid = i < n;
-            if (valid) {
-                const uint64_t k = keys[cbeg + i];
-                dg[r] = (uint32_t)(k >> 32) & (SROWS - 1);
-                vv[r] = (uint32_t)k;
-            }
-            const uint32_t d = dg[r];
-            const uint64_t m = match_digit8(d, __ballot(valid));   // valid lanes with my key
-            const uint32_t below = __popcll(m & lanes_below);
-            if (valid && below == 0) {
-                rk[r] = atomicAdd(&whist[d], (uint32_t)__popcll(m));  // rank of the group inside this wave
-                is_leader |= 1u << r;
-            } else {
-                rk[r] = below | ((uint32_t)(__ffsll((unsigned long long)m) - 1) << 16);
-            }
-        }
-    }
-#pragma unroll
-    for (int r = 0; r < SROUNDS; ++r) {
-        if (r < rounds_n) {
-            const bool lead = (is_leader >> r) & 1u;
-            const int from = lead ? lane : (int)((rk[r] >> 16) & 63u);
-            const uint32_t p = __shfl(rk[r], from);
-            rk[r] = lead ? p : p + (rk[r] & 0xffffu);
-        }
-    }
-    __syncthreads();
-    uint32_t tot = 0;   // key offsets: exclusive over waves, then over keys (thread d owns key d)
-#pragma unroll
-    for (int w = 0; w < SWAVES; ++w) {
-        const uint32_t c = s_whist[w * 256 + tid];
-        s_whist[w * 256 + tid] = tot;
-        tot += c;
-    }
-    // exclusive scan of `tot` over the 256 threads: wave scan, wave totals through s_tmp — ONE barrier (s_tmp is next written
-    // a chunk later, behind the caller's barriers)
-    const uint32_t incl = wave_incl_scan_u32(tot);
-    if (lane == 63) s_tmp[wave] = incl;
-    __syncthreads();
-    uint32_t start = incl - tot;
-#pragma unroll
-    for (int w = 0; w < SWAVES; ++w)
-        if (w < wave) start += s_tmp[w];
-#pragma unroll
-    for (int w = 0; w < SWAVES; ++w) s_whist[w * 256 + tid] += start;
-    s_rowptr[tid] = (int32_t)start;
-    if (tid == SROWS - 1) s_rowptr[SROWS] = (int32_t)(start + tot);
-    __syncthreads();
-#pragma unroll
-    for (int r = 0; r < SROUNDS; ++r) {
-        if (r < rounds_n) {
-            const int i = wave_base + r * 64 + lane;
-            if (i < n) s_val[whist[dg[r]] + rk[r]] = vv[r];
-        }
-    }
-    return tot;
-}
-
 // R: GNNOPS_SUM or GNNOPS_MUL; is_mean divides the sum by max(count, 1).
 template <typename T, int R>
 __global__ __launch_bounds__(STHREADS, 8) void sum1d_kernel(const uint64_t* __restrict__ keys, const int64_t* __restrict__ bptr,
@@ -304,7 +219,10 @@ __global__ __launch_bounds__(STHREADS, 8) void sum1d_kernel(const uint64_t* __re
         for (int64_t cbeg = beg; cbeg < end; cbeg += SCAP) {
             const int n = (int)((end - cbeg < SCAP) ? (end - cbeg) : SCAP);
             __syncthreads();   // the previous chunk's / bucket's readers are done with s_val, s_rowptr; s_whist is zero
-            cnt += sort_chunk64(keys, cbeg, n, s_val, s_whist, s_rowptr, s_tmp);
+            // stable, by (destination & 255), the VALUE bits as payload: lds_sort.h, histograms zeroed here (one barrier fewer per chunk)
+            cnt += ldssort::sort_chunk<STHREADS, SROUNDS, true>(
+                n, [&](int i) { const uint64_t k = keys[cbeg + i]; return ldssort::Item{(uint32_t)(k >> 32) & (SROWS - 1), (uint32_t)k}; },
+                s_val, s_whist, s_rowptr, s_tmp);
             __syncthreads();   // everyone has placed its values (the last readers of s_whist)
             for (int i = tid; i < SWAVES * 256; i += STHREADS) s_whist[i] = 0;   // for the next chunk, ordered by its leading barrier
             const int32_t jb = s_rowptr[tid], je = s_rowptr[tid + 1];

@@ -370,11 +370,6 @@ __global__ __launch_bounds__(LDS_THREADS) void scatter_lds_kernel(const T* __res
 // the extremum AND its arg in one sweep (the two-pass form above streams src / index twice and spins on a float CAS).
 // -0.0 and +0.0 get the same image (they compare equal: the earlier position wins, like the sequential loop), NaNs never
 // win; the stored value is re-read from src at the winning position, so its bits are exact.
-__device__ inline uint32_t f32_order(float v) {
-    uint32_t u = __float_as_uint(v);
-    if (u == 0x80000000u) u = 0u;
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
 // 16-bit inputs whose positions fit 16 bits (E < 65535: every reference shape) pack into a 32-bit cell — half the LDS per
 // destination, so strips twice as wide. fp16 and bf16 share sign-magnitude order; both widen to fp32 exactly, so the top
 // 16 bits of the fp32 image order bf16 exactly and fp16 after the exact widening (f32_order >> 16 would lose fp16 bits:
@@ -593,7 +588,6 @@ inline LdsGeom lds_geometry(int64_t N, int64_t K, int cell_bytes, int64_t B) {
     return LdsGeom{(int)tc, rows, (int)nchunks};
 }
 
-inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 inline int grid_for(int64_t n) { return gnnops_grid_cap(gnnops_cdiv(n, 256), 256 * 16); }
 
 // The whole dispatch of a call with B * N * K > 0: which form takes it and with what launch geometry. run() and launch_lds()
@@ -710,7 +704,7 @@ int run(const void* src_, const void* index_, int index_bytes, void* out_, int64
             acc = (float*)out;
         } else {
             acc = (float*)w;
-            w += align_up((size_t)nout * 4, 256);
+            w += gnnops_align_up((size_t)nout * 4, 256);
         }
         if (init_from_out) {
             if (!IS_F32) hipLaunchKernelGGL((widen_kernel<T>), dim3(go), dim3(256), 0, stream, out, acc, nout);
@@ -770,8 +764,8 @@ extern "C" size_t gnnops_scatter_elementwise_workspace_bytes(int64_t B, int64_t 
     const size_t nout = (size_t)(B * N * K);
     size_t b = 0;
     if ((reduce == GNNOPS_SUM || reduce == GNNOPS_MEAN || reduce == GNNOPS_MUL) && dtype != GNNOPS_F32)
-        b += align_up(nout * 4, 256);
-    if (reduce == GNNOPS_MEAN) b += align_up(nout * 4, 256);
+        b += gnnops_align_up(nout * 4, 256);
+    if (reduce == GNNOPS_MEAN) b += gnnops_align_up(nout * 4, 256);
     return b;
 }
 

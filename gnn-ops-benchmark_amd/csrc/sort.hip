@@ -19,16 +19,6 @@ namespace {
 
 enum { ST_F32 = 0, ST_F16 = 1, ST_BF16 = 2, ST_I32 = 3, ST_I64 = 4, ST_F64 = 5 };
 
-__device__ inline uint32_t f32_key(float x) {
-    uint32_t u = __float_as_uint(x);
-    if (u == 0x80000000u) u = 0u;
-    if ((u & 0x7fffffffu) > 0x7f800000u) return 0xffffffffu;
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ inline float key_f32(uint32_t k) {
-    const uint32_t u = (k & 0x80000000u) ? (k ^ 0x80000000u) : ~k;
-    return __uint_as_float(u);
-}
 __device__ inline uint64_t f64_key(double x) {
     uint64_t u = (uint64_t)__double_as_longlong(x);
     if (u == 0x8000000000000000ull) u = 0ull;
@@ -42,13 +32,13 @@ __device__ inline double key_f64(uint64_t k) {
 
 template <int ST> struct SortType;
 template <> struct SortType<ST_F32> { using T = float; using Key = uint32_t;
-    __device__ static Key key(T x) { return f32_key(x); } __device__ static T val(Key k) { return key_f32(k); }
+    __device__ static Key key(T x) { return f32_key(x); } __device__ static T val(Key k) { return f32_unorder(k); }
     __device__ static bool special(Key k) { return k == 0x80000000u || k == 0xffffffffu; } };
 template <> struct SortType<ST_F16> { using T = __half; using Key = uint32_t;
-    __device__ static Key key(T x) { return f32_key(__half2float(x)); } __device__ static T val(Key k) { return __float2half(key_f32(k)); }
+    __device__ static Key key(T x) { return f32_key(__half2float(x)); } __device__ static T val(Key k) { return __float2half(f32_unorder(k)); }
     __device__ static bool special(Key k) { return k == 0x80000000u || k == 0xffffffffu; } };
 template <> struct SortType<ST_BF16> { using T = __hip_bfloat16; using Key = uint32_t;
-    __device__ static Key key(T x) { return f32_key(__bfloat162float(x)); } __device__ static T val(Key k) { return __float2bfloat16(key_f32(k)); }
+    __device__ static Key key(T x) { return f32_key(__bfloat162float(x)); } __device__ static T val(Key k) { return __float2bfloat16(f32_unorder(k)); }
     __device__ static bool special(Key k) { return k == 0x80000000u || k == 0xffffffffu; } };
 template <> struct SortType<ST_I32> { using T = int32_t; using Key = uint32_t;
     __device__ static Key key(T x) { return (uint32_t)x ^ 0x80000000u; } __device__ static T val(Key k) { return (int32_t)(k ^ 0x80000000u); }
@@ -116,7 +106,6 @@ __global__ void finish_seg_kernel(const uint64_t* __restrict__ keys, const uint3
     }
 }
 
-inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 inline int grid_for(int64_t n) { return gnnops_grid_cap(gnnops_cdiv(n, 256), 256 * 16); }
 
 struct Work {
@@ -229,7 +218,7 @@ extern "C" size_t gnnops_sort_workspace_bytes(int64_t B, int64_t E, int64_t K, i
     const size_t n = (size_t)(B * E * K);
     const size_t tiles = (size_t)gnnops_cdiv(n > 0 ? (int64_t)n : 1, sortengine::TILE);
     const size_t keyb = key_bytes(sort_dtype, B * K == 1);
-    return 2 * align_up(n * keyb, 256) + 2 * align_up(n * 4, 256) + align_up(256 * tiles * 4, 256) + 1024;
+    return 2 * gnnops_align_up(n * keyb, 256) + 2 * gnnops_align_up(n * 4, 256) + gnnops_align_up(256 * tiles * 4, 256) + 1024;
 }
 
 extern "C" int gnnops_sort(const void* input, void* values, int64_t* indices, int64_t B, int64_t E, int64_t K,
@@ -247,11 +236,11 @@ extern "C" int gnnops_sort(const void* input, void* values, int64_t* indices, in
     Work w;
     w.tiles = (int)gnnops_cdiv(n, sortengine::TILE);
     char* p = (char*)workspace;
-    w.keys_a = p; p += align_up((size_t)n * keyb, 256);
-    w.keys_b = p; p += align_up((size_t)n * keyb, 256);
-    w.vals_a = (uint32_t*)p; p += align_up((size_t)n * 4, 256);
-    w.vals_b = (uint32_t*)p; p += align_up((size_t)n * 4, 256);
-    w.tile_hist = (uint32_t*)p; p += align_up((size_t)256 * w.tiles * 4, 256);
+    w.keys_a = p; p += gnnops_align_up((size_t)n * keyb, 256);
+    w.keys_b = p; p += gnnops_align_up((size_t)n * keyb, 256);
+    w.vals_a = (uint32_t*)p; p += gnnops_align_up((size_t)n * 4, 256);
+    w.vals_b = (uint32_t*)p; p += gnnops_align_up((size_t)n * 4, 256);
+    w.tile_hist = (uint32_t*)p; p += gnnops_align_up((size_t)256 * w.tiles * 4, 256);
     w.digit_total = (uint32_t*)p;
     switch (sort_dtype) {
         case ST_F32: return sort_typed<ST_F32>(input, values, indices, B, E, K, descending, w, stream);

@@ -17,6 +17,7 @@
 #pragma once
 #include "common.h"
 #include "sort_engine.h"
+#include "lds_sort.h"
 
 namespace sortengine {
 
@@ -194,7 +195,7 @@ __global__ __launch_bounds__(THREADS, (sizeof(typename KA::Carry) == 4 ? 4 : 2))
     const int tile = (int)xcd_contiguous(blockIdx.x, gridDim.x);
     const int64_t base = (int64_t)tile * TILE;
     const int64_t wave_base = base + (int64_t)wave * ROUNDS * 64;
-    const uint64_t lanes_below = (lane == 0) ? 0ull : (~0ull >> (64 - lane));
+    const uint64_t lanes_below = ldssort::lanes_below(lane);
     uint32_t* whist = &s_whist[wave][0];
 
     Carry key[ROUNDS];
@@ -216,31 +217,21 @@ __global__ __launch_bounds__(THREADS, (sizeof(typename KA::Carry) == 4 ? 4 : 2))
         }
     }
 
-    // Phase 1: stable rank of each key among equal digits of its wave (rows of 64 keys in memory order).
-    // x[r] holds, in a group's lowest lane, the base returned by the LDS add; in the other lanes
-    // `below | leader_lane << 8`. is_leader has bit r set where this lane is row r's group leader.
+    // Phase 1: stable rank of each key among equal digits of its wave (rows of 64 keys in memory order): lds_sort.h.
+    // x[r] holds the row's vote word; is_leader has bit r set where this lane is row r's group leader.
     uint32_t x[ROUNDS];
     uint32_t is_leader = 0;
 #pragma unroll
     for (int r = 0; r < ROUNDS; ++r) {
         const int64_t i = wave_base + r * 64 + lane;
         const bool valid = i < n;
-        const uint32_t d = KA::digit(key[r], shift);
-        // peers = lanes whose digit equals mine: AND over the 8 digit bits of (ballot(bit) XNOR my bit)
-        const uint64_t m = match_digit8(d, __ballot(valid));
-        const uint32_t below = __popcll(m & lanes_below);
-        if (valid && below == 0) {
-            x[r] = atomicAdd(&whist[d], (uint32_t)__popcll(m));
-            is_leader |= 1u << r;
-        } else {
-            x[r] = below | ((uint32_t)(__ffsll((unsigned long long)m) - 1) << 8);
-        }
+        x[r] = ldssort::rank_vote(KA::digit(key[r], shift), valid, whist, lanes_below, is_leader, r);
         __builtin_amdgcn_sched_barrier(0);  // keep rows from being interleaved (register pressure)
     }
     uint32_t rank[ROUNDS];
 #pragma unroll
-    for (int r = 0; r < ROUNDS; ++r) {
-        const bool lead = (is_leader >> r) & 1u;
+    for (int r = 0; r < ROUNDS; ++r) {  // ldssort::rank_resolve, spelled out: through the call one instantiation
+        const bool lead = (is_leader >> r) & 1u;  // (KeyU32, explicit values, keys written) took 6 more SGPRs
         const int from = lead ? lane : (int)((x[r] >> 8) & 63u);
         const uint32_t p = __shfl(x[r], from);
         rank[r] = lead ? p : p + (x[r] & 255u);

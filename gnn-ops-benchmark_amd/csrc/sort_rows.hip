@@ -4,24 +4,14 @@
 // The generic path (sort.hip) sorts (segment << 32 | key) with six or more passes over HBM. Here a row is read once
 // (4 B/element) and written once (4 B value + 8 B index); the four 8-bit LSD passes run between registers and LDS:
 //   rank   each wave owns consecutive rows of 64 keys; eight ballots give every lane its equal-digit peers, the lowest
-//          peer does one returning LDS add per distinct digit (same scheme as sort_engine_impl.h, stable)
+//          peer does one returning LDS add per distinct digit (the scheme of lds_sort.h, spelled out here; stable)
 //   place  per-digit offsets across waves and digits, then (key, 16-bit position) go to their sorted slot in LDS
 //   reload every wave reads its slice of the sorted image back for the next pass
 // Stable; -0.0 / NaN conventions as in sort.hip. fp32 keys; positions fit 16 bits (E < 65536).
 #include "common.h"
+#include "lds_sort.h"
 
 namespace {
-
-__device__ inline uint32_t f32_key(float x) {
-    uint32_t u = __float_as_uint(x);
-    if (u == 0x80000000u) u = 0u;
-    if ((u & 0x7fffffffu) > 0x7f800000u) return 0xffffffffu;
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ inline float key_f32(uint32_t k) {
-    const uint32_t u = (k & 0x80000000u) ? (k ^ 0x80000000u) : ~k;
-    return __uint_as_float(u);
-}
 
 constexpr int RADIX = 256;
 
@@ -43,7 +33,7 @@ __global__ __launch_bounds__(THREADS) void sort_rows_kernel(const float* __restr
     uint32_t* s_tmp = s_whist + WAVES * RADIX;                                     // [WAVES]
 
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-    const uint64_t lanes_below = (lane == 0) ? 0ull : (~0ull >> (64 - lane));
+    const uint64_t lanes_below = ldssort::lanes_below(lane);
     const int wave_base = wave * ROUNDS * 64;
     uint32_t* whist = s_whist + wave * RADIX;
 
@@ -81,6 +71,8 @@ __global__ __launch_bounds__(THREADS) void sort_rows_kernel(const float* __restr
             for (int r = 0; r < ROUNDS; ++r) {
                 const int i = wave_base + r * 64 + lane;
                 const bool valid = i < E;
+                // ldssort::rank_vote and, below, rank_resolve, spelled out: through the calls the (800, 800, 800) sort
+                // (THREADS 256, ROUNDS 4) measured 0.45 % slower, outside the parent's run-to-run range
                 const uint32_t d = (key[r] >> shift) & 255u;
                 const uint64_t m = match_digit8(d, __ballot(valid));
                 const uint32_t below = __popcll(m & lanes_below);
@@ -156,7 +148,7 @@ __global__ __launch_bounds__(THREADS) void sort_rows_kernel(const float* __restr
                 const uint32_t e = px[r] >> 16;
                 // a zero or a NaN: the key does not fix the bits (-0.0 keyed as +0.0, one key for all NaNs) — re-read the
                 // element (the row was just streamed: an L2 hit), so values == input.gather(indices) bit for bit
-                vdst[i] = (k == 0x80000000u || k == 0xffffffffu) ? src[e] : key_f32(k);
+                vdst[i] = (k == 0x80000000u || k == 0xffffffffu) ? src[e] : f32_unorder(k);
                 idst[i] = (I)(e + (uint32_t)off);
             }
         }

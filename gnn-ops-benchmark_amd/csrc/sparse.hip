@@ -335,7 +335,6 @@ __global__ __launch_bounds__(256) void transpose_narrow_kernel(const int64_t* __
     }
 }
 
-inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 inline int grid_for(int64_t n) { return gnnops_grid_cap(gnnops_cdiv(n, 256), 256 * 16); }
 
 inline int bits_of(int64_t count) {  // bits that hold 0 .. count-1 (at least 1)
@@ -392,8 +391,8 @@ extern "C" size_t gnnops_coalesce_workspace_bytes(int64_t nnz) {
     const size_t n = (size_t)nnz;
     const size_t tiles = (size_t)gnnops_cdiv(nnz > 0 ? nnz : 1, sortengine::TILE);
     const size_t nb = (size_t)gnnops_cdiv(nnz > 0 ? nnz : 1, SCAN_TILE);
-    return 2 * align_up(n * 8, 256) + 2 * align_up(n * 4, 256) + align_up(256 * tiles * 4, 256) + 1024 +
-           align_up(nb * 4, 256) + align_up(n * 4, 256);
+    return 2 * gnnops_align_up(n * 8, 256) + 2 * gnnops_align_up(n * 4, 256) + gnnops_align_up(256 * tiles * 4, 256) + 1024 +
+           gnnops_align_up(nb * 4, 256) + gnnops_align_up(n * 4, 256);
 }
 
 extern "C" int gnnops_coalesce(const int64_t* row, const int64_t* col, const void* value, int64_t nnz, int64_t m,
@@ -414,13 +413,13 @@ extern "C" int gnnops_coalesce(const int64_t* row, const int64_t* col, const voi
     const int tiles = (int)gnnops_cdiv(nnz, sortengine::TILE);
     const int nb = (int)gnnops_cdiv(nnz, SCAN_TILE);
     char* w = (char*)workspace;
-    uint64_t* keys_a = (uint64_t*)w; w += align_up((size_t)nnz * 8, 256);
-    uint64_t* keys_b = (uint64_t*)w; w += align_up((size_t)nnz * 8, 256);
-    uint32_t* vals_a = (uint32_t*)w; w += align_up((size_t)nnz * 4, 256);
-    uint32_t* vals_b = (uint32_t*)w; w += align_up((size_t)nnz * 4, 256);
-    uint32_t* tile_hist = (uint32_t*)w; w += align_up((size_t)256 * tiles * 4, 256);
+    uint64_t* keys_a = (uint64_t*)w; w += gnnops_align_up((size_t)nnz * 8, 256);
+    uint64_t* keys_b = (uint64_t*)w; w += gnnops_align_up((size_t)nnz * 8, 256);
+    uint32_t* vals_a = (uint32_t*)w; w += gnnops_align_up((size_t)nnz * 4, 256);
+    uint32_t* vals_b = (uint32_t*)w; w += gnnops_align_up((size_t)nnz * 4, 256);
+    uint32_t* tile_hist = (uint32_t*)w; w += gnnops_align_up((size_t)256 * tiles * 4, 256);
     uint32_t* digit_total = (uint32_t*)w; w += 1024;
-    uint32_t* block_sums = (uint32_t*)w; w += align_up((size_t)nb * 4, 256);
+    uint32_t* block_sums = (uint32_t*)w; w += gnnops_align_up((size_t)nb * 4, 256);
     uint32_t* seg_start = (uint32_t*)w;
 
     const int cbits = bits_of(n), rbits = bits_of(m);

@@ -90,13 +90,12 @@ __global__ __launch_bounds__(T) void expand_kernel(const int64_t* __restrict__ r
     }
 }
 
-inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
 }  // namespace
 
 extern "C" size_t gnnops_spspmm_workspace_bytes(int64_t nnzA) {
     if (nnzA < 0) return 0;
-    return align_up((size_t)gnnops_cdiv(nnzA > 0 ? nnzA : 1, T) * 4, 256) + 256;
+    return gnnops_align_up((size_t)gnnops_cdiv(nnzA > 0 ? nnzA : 1, T) * 4, 256) + 256;
 }
 
 // Phase 1: *d_total = number of products; block offsets are left in `workspace` for phase 2.
