@@ -27,6 +27,14 @@
 // Backward (destination-ordered too, no atomics): s is recomputed from the same rows, a = exp(s - lse); one [E, H * C] tensor gq
 // is written (d q = its segment sum over the source plan), d p is summed in registers and stored once per destination, d att is
 // summed per wave in fp32 and the [waves, H * C] partials are added in a fixed order by a second small kernel.
+//
+// The second member of the family (gnnops.conv.edge_attention_v1: GATConv, the original GAT, and AttentiveFP's GATEConv) scores
+// an edge from a per-edge scalar and a per-destination scalar, and may take a per-edge row u and a per-edge, per-head scale k
+// (the attention dropout mask, in the weighted sum only):
+//   t[e,h,:] = q[j,h,:] + u[e,h,:]      r = t, or leaky_relu(t, row_slope)      s[e,h] = leaky_relu(att[h,:] . r[e,h,:] + d[i,h], slope)
+//   out[i,h,:] = sum_{e into i} exp(s[e,h] - lse[i,h]) * k[e,h] * r[e,h,:]
+// gate_fwd_kernel / gate_bwd_kernel below: the same layout, group sums, id hand-out, online softmax and d att partials; u and k
+// are read through perm (row = original edge id, int64 offsets). With u a step holds two raw rows per edge, so its unroll halves.
 #include <initializer_list>
 #include <utility>
 #include "common.h"
@@ -117,6 +125,14 @@ struct Place {
         h = hb * (64 >> a.gshift) + (lane >> a.gshift);
         C = a.C;
         head_ok = h < a.H;
+    }
+    __device__ inline Place(int gshift, int H, int C_, int hb) {
+        lane = threadIdx.x & 63;
+        G = 1 << gshift;
+        gl = lane & (G - 1);
+        h = hb * (64 >> gshift) + (lane >> gshift);
+        C = C_;
+        head_ok = h < H;
     }
     template <int VEC> __device__ inline bool live(int k) const { return k * G * VEC < C; }   // wave-uniform: some lane has piece k
     template <int VEC> __device__ inline bool ok(int k) const { return head_ok && (k * G + gl) * VEC < C; }
@@ -399,6 +415,333 @@ __global__ __launch_bounds__(256) void attention_datt_kernel(const float* __rest
     Elem<T>::store(datt + c, s);
 }
 
+// ---- GATConv (v1) / GATEConv ---------------------------------------------------------------------------------------------------
+struct GateArgs {
+    const void *q, *d, *att, *u, *ks, *g, *o;   // u [E, H * C], ks [E, H] (edge_scale): rows = ORIGINAL edge ids, either may be null
+    const int32_t *rowptr, *perm;
+    const int64_t* col;
+    void *out, *dd, *gq;
+    float *lse, *partial;
+    int64_t N, ldq, ldd, ldo, ldg;
+    int H, C, gshift, hblocks, nwaves;
+    float slope, row_slope;   // row_slope = 1 where the row is taken as it is: t * 1 = t and the derivative is 1, exactly
+};
+
+// edges per step: every raw row of a step is in flight before the first is consumed, and with u there are two per edge
+template <int NCH, bool HASU> struct GateUnroll {
+    static constexpr int FW = HASU ? (NCH == 1 ? 4 : NCH == 2 ? 2 : 1) : Unroll<NCH>::U;
+    static constexpr int BW = HASU ? (NCH == 1 ? 2 : 1) : (NCH == 1 ? 4 : NCH == 2 ? 2 : 1);
+};
+
+template <typename T> __device__ inline float gate_scalar(const T* p) {
+    float f[1];
+    att_unpack<T, 1>(att_load_raw<T, 1>(p), f);
+    return f[0];
+}
+
+// t = q[j] + u[e] of one piece
+template <typename T, int VEC, bool HASU>
+__device__ inline void gate_row(const u32x4& qr, const u32x4& ur, float* t) {
+    att_unpack<T, VEC>(qr, t);
+    if constexpr (HASU) {
+        float uv[VEC];
+        att_unpack<T, VEC>(ur, uv);
+#pragma unroll
+        for (int v = 0; v < VEC; ++v) t[v] = t[v] + uv[v];
+    }
+}
+
+template <typename T, int VEC, int NCH, bool HASU>
+__global__ __launch_bounds__(256) void gate_fwd_kernel(const GateArgs a) {
+    constexpr int U = GateUnroll<NCH, HASU>::FW;
+    constexpr bool HOLD = NCH <= 4;   // att pieces stay in registers
+    const T* __restrict__ q = (const T*)a.q;
+    const T* __restrict__ d = (const T*)a.d;
+    const T* __restrict__ att = (const T*)a.att;
+    const T* __restrict__ ue = (const T*)a.u;
+    const T* __restrict__ ks = (const T*)a.ks;
+    const int64_t* __restrict__ col = a.col;
+    const int32_t* __restrict__ perm = a.perm;
+    const int wave = __builtin_amdgcn_readfirstlane((int)(((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6));
+    const int64_t items = a.N * a.hblocks;
+    const int ldq = (int)a.ldq;
+    const int HC = a.H * a.C;
+    const float slope = a.slope, rs = a.row_slope;
+    const bool by_edge = HASU || ks != nullptr;   // something is read by original edge id
+    const float NEG_INF = -__builtin_huge_valf();
+    for (int64_t it = wave; it < items; it += a.nwaves) {
+        const int i = __builtin_amdgcn_readfirstlane((int)(it / a.hblocks));
+        const int hb = __builtin_amdgcn_readfirstlane((int)(it % a.hblocks));
+        const Place pl(a.gshift, a.H, a.C, hb);
+        const int lane = pl.lane;
+        const int hk = pl.head_ok ? pl.h : 0;
+        const int32_t jb = __builtin_amdgcn_readfirstlane(a.rowptr[i]), je = __builtin_amdgcn_readfirstlane(a.rowptr[i + 1]);
+        float av[HOLD ? NCH : 1][VEC];
+        if constexpr (HOLD) {
+#pragma unroll
+            for (int k = 0; k < NCH; ++k) att_unpack<T, VEC>(att_load_raw<T, VEC>(att + pl.off<VEC>(k)), av[k]);
+        }
+        const float dv = gate_scalar<T>(d + (int64_t)i * a.ldd + hk);
+        float acc[NCH][VEC];
+#pragma unroll
+        for (int k = 0; k < NCH; ++k)
+#pragma unroll
+            for (int v = 0; v < VEC; ++v) acc[k][v] = 0.f;
+        float m = NEG_INF, l = 0.f;
+        for (int32_t jrun = jb; jrun < je; jrun += 64) {
+            const int32_t jrun_end = min(jrun + 64, je);
+            int cl = 0, el = 0;
+            if (jrun + lane < je) {
+                cl = (int)col[jrun + lane];   // one coalesced load: lane l holds id l of the run
+                if (by_edge) el = perm ? perm[jrun + lane] : jrun + lane;
+            }
+            for (int32_t j = jrun; j < jrun_end; j += U) {
+                int64_t qrow[U], erow[HASU ? U : 1], krow[U];
+#pragma unroll
+                for (int u = 0; u < U; ++u) {
+                    qrow[u] = (int64_t)__builtin_amdgcn_readlane(cl, (j - jrun + u) & 63) * ldq;
+                    asm volatile("" : "+s"(qrow[u]));   // the row bases are computed HERE, ahead of every row load
+                    krow[u] = 0;
+                    if (by_edge) {                      // pure GAT without a mask: no per-edge base at all
+                        const int64_t e = __builtin_amdgcn_readlane(el, (j - jrun + u) & 63);
+                        krow[u] = e * a.H;
+                        if constexpr (HASU) {
+                            erow[u] = e * HC;
+                            asm volatile("" : "+s"(erow[u]));
+                        }
+                    }
+                }
+                u32x4 qr[U][NCH], ur[HASU ? U : 1][HASU ? NCH : 1];
+                float kv[U];
+#pragma unroll
+                for (int u = 0; u < U; ++u) {           // every row load of the step in flight before the first is consumed
+                    kv[u] = 1.f;
+                    if (j + u < jrun_end) {
+#pragma unroll
+                        for (int k = 0; k < NCH; ++k) {
+                            if (!pl.live<VEC>(k)) continue;
+                            qr[u][k] = att_load_raw<T, VEC>(q + qrow[u] + pl.off<VEC>(k));
+                            if constexpr (HASU) ur[u][k] = att_load_raw<T, VEC>(ue + erow[HASU ? u : 0] + pl.off<VEC>(k));
+                        }
+                        if (ks) kv[u] = gate_scalar<T>(ks + krow[u] + hk);
+                    }
+                }
+                float s[U];
+#pragma unroll
+                for (int u = 0; u < U; ++u) {
+                    s[u] = 0.f;
+                    if (j + u < jrun_end) {
+                        float part = 0.f;
+#pragma unroll
+                        for (int k = 0; k < NCH; ++k) {
+                            if (!pl.live<VEC>(k)) continue;
+                            float t[VEC], ak[VEC];
+                            gate_row<T, VEC, HASU>(qr[u][k], ur[HASU ? u : 0][HASU ? k : 0], t);
+                            if constexpr (!HOLD) att_unpack<T, VEC>(att_load_raw<T, VEC>(att + pl.off<VEC>(k)), ak);
+                            float sub = 0.f;
+#pragma unroll
+                            for (int v = 0; v < VEC; ++v) sub += (HOLD ? av[k][v] : ak[v]) * (t[v] > 0.f ? t[v] : t[v] * rs);
+                            part += pl.ok<VEC>(k) ? sub : 0.f;
+                        }
+                        const float pre = group_sum(part, a.gshift, lane) + dv;
+                        s[u] = pre > 0.f ? pre : pre * slope;
+                    }
+                }
+                float mn = m;
+#pragma unroll
+                for (int u = 0; u < U; ++u)
+                    if (j + u < jrun_end) mn = fmaxf(mn, s[u]);
+                const float scale = expf(m - mn);   // 0 on the first step (m = -inf): nothing to rescale yet
+                m = mn;
+                l = l * scale;
+#pragma unroll
+                for (int k = 0; k < NCH; ++k)
+#pragma unroll
+                    for (int v = 0; v < VEC; ++v) acc[k][v] = acc[k][v] * scale;
+#pragma unroll
+                for (int u = 0; u < U; ++u) {
+                    if (j + u < jrun_end) {
+                        const float w = expf(s[u] - mn);
+                        l = l + w;                      // the denominator never sees the scale: dropout comes after the softmax
+                        const float wk = w * kv[u];
+#pragma unroll
+                        for (int k = 0; k < NCH; ++k) {
+                            if (!pl.live<VEC>(k)) continue;
+                            float t[VEC];
+                            gate_row<T, VEC, HASU>(qr[u][k], ur[HASU ? u : 0][HASU ? k : 0], t);
+#pragma unroll
+                            for (int v = 0; v < VEC; ++v) acc[k][v] = acc[k][v] + wk * (t[v] > 0.f ? t[v] : t[v] * rs);
+                        }
+                    }
+                }
+            }
+        }
+        const bool any = je > jb;
+#pragma unroll
+        for (int k = 0; k < NCH; ++k) {
+            if (!pl.live<VEC>(k)) continue;
+            float o[VEC];
+#pragma unroll
+            for (int v = 0; v < VEC; ++v) o[v] = any ? acc[k][v] / l : 0.f;
+            if (pl.ok<VEC>(k)) att_store<T, VEC>((T*)a.out + (int64_t)i * a.ldo + pl.off<VEC>(k), o);
+        }
+        if (pl.head_ok && pl.gl == 0) a.lse[(int64_t)i * a.H + pl.h] = any ? m + logf(l) : NEG_INF;
+    }
+}
+
+// Backward: as attention_bwd_kernel (one head block per wave, d att in registers across its destinations); d d[i, h] is the sum
+// of dpre over the edges of i, in a register, stored once.
+template <typename T, int VEC, int NCH, bool HASU>
+__global__ __launch_bounds__(256) void gate_bwd_kernel(const GateArgs a) {
+    constexpr int U = GateUnroll<NCH, HASU>::BW;
+    constexpr bool HOLD = NCH <= 4;
+    const T* __restrict__ q = (const T*)a.q;
+    const T* __restrict__ d = (const T*)a.d;
+    const T* __restrict__ att = (const T*)a.att;
+    const T* __restrict__ ue = (const T*)a.u;
+    const T* __restrict__ ks = (const T*)a.ks;
+    const T* __restrict__ g = (const T*)a.g;
+    const T* __restrict__ o = (const T*)a.o;
+    const int64_t* __restrict__ col = a.col;
+    const int32_t* __restrict__ perm = a.perm;
+    const int wave = __builtin_amdgcn_readfirstlane((int)(((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6));
+    if (wave >= a.nwaves) return;
+    const int64_t items = a.N * a.hblocks;
+    const int ldq = (int)a.ldq;
+    const int HC = a.H * a.C;
+    const float slope = a.slope, rs = a.row_slope;
+    const int hb = __builtin_amdgcn_readfirstlane(wave % a.hblocks);
+    const Place pl(a.gshift, a.H, a.C, hb);
+    const int lane = pl.lane;
+    const int hk = pl.head_ok ? pl.h : 0;
+    float datt[NCH][VEC];
+#pragma unroll
+    for (int k = 0; k < NCH; ++k)
+#pragma unroll
+        for (int v = 0; v < VEC; ++v) datt[k][v] = 0.f;
+    float av[HOLD ? NCH : 1][VEC];
+    if constexpr (HOLD) {
+#pragma unroll
+        for (int k = 0; k < NCH; ++k) att_unpack<T, VEC>(att_load_raw<T, VEC>(att + pl.off<VEC>(k)), av[k]);
+    }
+    for (int64_t it = wave; it < items; it += a.nwaves) {
+        const int i = __builtin_amdgcn_readfirstlane((int)(it / a.hblocks));
+        const int32_t jb = __builtin_amdgcn_readfirstlane(a.rowptr[i]), je = __builtin_amdgcn_readfirstlane(a.rowptr[i + 1]);
+        float gv[HOLD ? NCH : 1][VEC];
+        float dpart = 0.f;
+#pragma unroll
+        for (int k = 0; k < NCH; ++k) {
+            if (!pl.live<VEC>(k)) continue;
+            float gk[VEC], ok_[VEC];
+            att_unpack<T, VEC>(att_load_raw<T, VEC>(g + (int64_t)i * a.ldg + pl.off<VEC>(k)), gk);
+            att_unpack<T, VEC>(att_load_raw<T, VEC>(o + (int64_t)i * a.ldo + pl.off<VEC>(k)), ok_);
+            float sub = 0.f;
+#pragma unroll
+            for (int v = 0; v < VEC; ++v) sub += gk[v] * ok_[v];
+            dpart += pl.ok<VEC>(k) ? sub : 0.f;
+            if constexpr (HOLD) {
+#pragma unroll
+                for (int v = 0; v < VEC; ++v) gv[k][v] = gk[v];
+            }
+        }
+        const float delta = group_sum(dpart, a.gshift, lane);                    // sum_c g * out of this head
+        const float lse = pl.head_ok ? a.lse[(int64_t)i * a.H + pl.h] : 0.f;
+        const float dv = gate_scalar<T>(d + (int64_t)i * a.ldd + hk);
+        float dd = 0.f;
+        for (int32_t jrun = jb; jrun < je; jrun += 64) {
+            const int32_t jrun_end = min(jrun + 64, je);
+            int cl = 0, el = 0;
+            if (jrun + lane < je) {
+                cl = (int)col[jrun + lane];
+                el = perm ? perm[jrun + lane] : jrun + lane;
+            }
+            for (int32_t j = jrun; j < jrun_end; j += U) {
+                int64_t qrow[U], erow[U], krow[U];
+#pragma unroll
+                for (int u = 0; u < U; ++u) {
+                    qrow[u] = (int64_t)__builtin_amdgcn_readlane(cl, (j - jrun + u) & 63) * ldq;
+                    const int64_t e = __builtin_amdgcn_readlane(el, (j - jrun + u) & 63);
+                    erow[u] = e * HC;                   // always: the row of gq
+                    krow[u] = ks ? e * a.H : 0;
+                    asm volatile("" : "+s"(qrow[u]));
+                    asm volatile("" : "+s"(erow[u]));
+                }
+                u32x4 qr[U][NCH], ur[HASU ? U : 1][HASU ? NCH : 1];
+                float kv[U];
+#pragma unroll
+                for (int u = 0; u < U; ++u) {
+                    kv[u] = 1.f;
+                    if (j + u < jrun_end) {
+#pragma unroll
+                        for (int k = 0; k < NCH; ++k) {
+                            if (!pl.live<VEC>(k)) continue;
+                            qr[u][k] = att_load_raw<T, VEC>(q + qrow[u] + pl.off<VEC>(k));
+                            if constexpr (HASU) ur[u][k] = att_load_raw<T, VEC>(ue + erow[u] + pl.off<VEC>(k));
+                        }
+                        if (ks) kv[u] = gate_scalar<T>(ks + krow[u] + hk);
+                    }
+                }
+#pragma unroll
+                for (int u = 0; u < U; ++u) {
+                    if (j + u >= jrun_end) continue;
+                    float spart = 0.f, dapart = 0.f;
+#pragma unroll
+                    for (int k = 0; k < NCH; ++k) {
+                        if (!pl.live<VEC>(k)) continue;
+                        float t[VEC], ak[VEC], gk[VEC];
+                        gate_row<T, VEC, HASU>(qr[u][k], ur[HASU ? u : 0][HASU ? k : 0], t);
+                        if constexpr (!HOLD) {
+                            att_unpack<T, VEC>(att_load_raw<T, VEC>(att + pl.off<VEC>(k)), ak);
+                            att_unpack<T, VEC>(att_load_raw<T, VEC>(g + (int64_t)i * a.ldg + pl.off<VEC>(k)), gk);
+                        }
+                        float s1 = 0.f, s2 = 0.f;
+#pragma unroll
+                        for (int v = 0; v < VEC; ++v) {
+                            const float r = t[v] > 0.f ? t[v] : t[v] * rs;
+                            s1 += (HOLD ? av[k][v] : ak[v]) * r;
+                            s2 += (HOLD ? gv[k][v] : gk[v]) * r;
+                        }
+                        const bool ok = pl.ok<VEC>(k);
+                        spart += ok ? s1 : 0.f;
+                        dapart += ok ? s2 : 0.f;
+                    }
+                    const float pre = group_sum(spart, a.gshift, lane) + dv;
+                    const float da = kv[u] * group_sum(dapart, a.gshift, lane);
+                    const float w = expf((pre > 0.f ? pre : pre * slope) - lse);
+                    const float ds = w * (da - delta);
+                    const float dpre = ds * (pre > 0.f ? 1.f : slope);
+                    const float wk = w * kv[u];
+                    dd = dd + dpre;
+#pragma unroll
+                    for (int k = 0; k < NCH; ++k) {
+                        if (!pl.live<VEC>(k)) continue;
+                        float t[VEC], ak[VEC], gk[VEC], row[VEC];
+                        gate_row<T, VEC, HASU>(qr[u][k], ur[HASU ? u : 0][HASU ? k : 0], t);
+                        if constexpr (!HOLD) {
+                            att_unpack<T, VEC>(att_load_raw<T, VEC>(att + pl.off<VEC>(k)), ak);
+                            att_unpack<T, VEC>(att_load_raw<T, VEC>(g + (int64_t)i * a.ldg + pl.off<VEC>(k)), gk);
+                        }
+#pragma unroll
+                        for (int v = 0; v < VEC; ++v) {
+                            datt[k][v] = datt[k][v] + dpre * (t[v] > 0.f ? t[v] : t[v] * rs);
+                            row[v] = (wk * (HOLD ? gv[k][v] : gk[v]) + dpre * (HOLD ? av[k][v] : ak[v])) * (t[v] > 0.f ? 1.f : rs);
+                        }
+                        if (pl.ok<VEC>(k)) att_store<T, VEC>((T*)a.gq + erow[u] + pl.off<VEC>(k), row);
+                    }
+                }
+            }
+        }
+        if (pl.head_ok && pl.gl == 0) att_store<T, 1>((T*)a.dd + (int64_t)i * a.H + pl.h, &dd);
+    }
+    float* prow = a.partial + (int64_t)(wave / a.hblocks) * HC;
+#pragma unroll
+    for (int k = 0; k < NCH; ++k) {
+        if (!pl.live<VEC>(k) || !pl.ok<VEC>(k)) continue;
+#pragma unroll
+        for (int v = 0; v < VEC; ++v) prow[pl.off<VEC>(k) + v] = datt[k][v];
+    }
+}
+
 struct Geometry { int vec, nch, gshift, hblocks; };
 
 // widest piece the operands allow, narrowed while the heads of a row leave half the wave idle; NCH pieces per lane
@@ -472,6 +815,40 @@ int check_sizes(const char* what, int64_t N, int64_t E, int64_t H, int64_t C, in
         default: gnnops_set_error("%s: unknown dtype %d", what, dtype); return GNNOPS_EINVAL;
     }
     return GNNOPS_OK;
+}
+
+template <typename T, bool BW, bool HASU, int VEC, int NCH>
+void gate_launch_kernel(const GateArgs& a, int grid, hipStream_t stream) {
+    if constexpr (BW) hipLaunchKernelGGL((gate_bwd_kernel<T, VEC, NCH, HASU>), dim3(grid), dim3(256), 0, stream, a);
+    else hipLaunchKernelGGL((gate_fwd_kernel<T, VEC, NCH, HASU>), dim3(grid), dim3(256), 0, stream, a);
+}
+
+template <typename T, bool BW, bool HASU, int VEC>
+void gate_launch_nch(const GateArgs& a, int nch, int grid, hipStream_t stream) {
+    if (nch == 1) gate_launch_kernel<T, BW, HASU, VEC, 1>(a, grid, stream);
+    else if (nch == 2) gate_launch_kernel<T, BW, HASU, VEC, 2>(a, grid, stream);
+    else gate_launch_kernel<T, BW, HASU, VEC, 4>(a, grid, stream);
+}
+
+template <typename T, bool BW, bool HASU>
+void gate_launch_vec(const GateArgs& a, const Geometry& geo, int grid, hipStream_t stream) {
+    if (geo.nch == 128) return gate_launch_kernel<T, BW, HASU, 1, 128>(a, grid, stream);
+    if constexpr (Elem<T>::VEC == 8) {
+        if (geo.vec == 8) return gate_launch_nch<T, BW, HASU, 8>(a, geo.nch, grid, stream);
+    }
+    if (geo.vec == 4) return gate_launch_nch<T, BW, HASU, 4>(a, geo.nch, grid, stream);
+    if (geo.vec == 2) return gate_launch_nch<T, BW, HASU, 2>(a, geo.nch, grid, stream);
+    return gate_launch_nch<T, BW, HASU, 1>(a, geo.nch, grid, stream);
+}
+
+template <bool BW>
+void gate_launch(const GateArgs& a, const Geometry& geo, int grid, int dtype, hipStream_t stream) {
+    const bool has_u = a.u != nullptr;
+    switch (dtype) {
+        case GNNOPS_F32: has_u ? gate_launch_vec<float, BW, true>(a, geo, grid, stream) : gate_launch_vec<float, BW, false>(a, geo, grid, stream); break;
+        case GNNOPS_F16: has_u ? gate_launch_vec<__half, BW, true>(a, geo, grid, stream) : gate_launch_vec<__half, BW, false>(a, geo, grid, stream); break;
+        default: has_u ? gate_launch_vec<__hip_bfloat16, BW, true>(a, geo, grid, stream) : gate_launch_vec<__hip_bfloat16, BW, false>(a, geo, grid, stream); break;
+    }
 }
 
 }  // namespace
@@ -548,4 +925,74 @@ extern "C" int gnnops_edge_attention_backward(const void* q, int64_t ldq, const 
         default: hipLaunchKernelGGL(attention_datt_kernel<__hip_bfloat16>, dgrid, dim3(256), 0, stream, a.partial, rows, HC, (__hip_bfloat16*)grad_att); break;
     }
     return gnnops_check_launch("edge_attention_backward");
+}
+
+extern "C" int gnnops_edge_attention_v1(const void* q, int64_t ldq, const void* d, int64_t ldd, const void* att, const void* u,
+                                        const void* edge_scale, const int32_t* rowptr, const int32_t* perm, const int64_t* col,
+                                        void* out, int64_t ldo, float* lse, int64_t N, int64_t E, int64_t H, int64_t C,
+                                        int has_row_slope, float row_slope, float negative_slope, int dtype, gnnops_stream_t s) {
+    int es = 0;
+    const int rc = check_sizes("edge_attention_v1", N, E, H, C, ldq, H * C, dtype, &es);
+    if (rc != GNNOPS_OK) return rc;
+    GNNOPS_REQUIRE(ldo >= H * C && ldd >= H, GNNOPS_EINVAL, "edge_attention_v1: a row pitch is shorter than the row");
+    if (N == 0) return GNNOPS_OK;
+    GNNOPS_REQUIRE(rowptr && out && lse && d && att && (E == 0 || (q && col)), GNNOPS_EINVAL, "edge_attention_v1: null pointer");
+    const int max_vec = max_vec_of(es, {{q, ldq}, {att, 0}, {u, H * C}, {out, ldo}});
+    const Geometry geo = geometry((int)H, (int)C, max_vec, es);
+    GateArgs a{};
+    a.q = q; a.d = d; a.att = att; a.u = E ? u : nullptr; a.ks = E ? edge_scale : nullptr; a.rowptr = rowptr; a.perm = perm; a.col = col;
+    a.out = out; a.lse = lse;
+    a.N = N; a.ldq = ldq; a.ldd = ldd; a.ldo = ldo; a.H = (int)H; a.C = (int)C;
+    a.slope = negative_slope; a.row_slope = has_row_slope ? row_slope : 1.f;
+    a.gshift = geo.gshift; a.hblocks = geo.hblocks;
+    const int grid = gnnops_grid_cap(gnnops_cdiv(N * geo.hblocks, 4), 256 * 32);
+    a.nwaves = grid * 4;
+    gate_launch<false>(a, geo, grid, dtype, (hipStream_t)s);
+    return gnnops_check_launch("edge_attention_v1");
+}
+
+extern "C" size_t gnnops_edge_attention_v1_backward_workspace_bytes(int64_t N, int64_t H, int64_t C) {
+    return gnnops_edge_attention_backward_workspace_bytes(N, H, C);
+}
+
+extern "C" int gnnops_edge_attention_v1_backward(const void* q, int64_t ldq, const void* d, int64_t ldd, const void* att, const void* u,
+                                                 const void* edge_scale, const void* out, int64_t ldo, const float* lse,
+                                                 const void* grad_out, int64_t ldg, const int32_t* rowptr, const int32_t* perm,
+                                                 const int64_t* col, void* grad_d, void* gq, void* grad_att, int64_t N, int64_t E,
+                                                 int64_t H, int64_t C, int has_row_slope, float row_slope, float negative_slope,
+                                                 int dtype, void* workspace, size_t workspace_bytes, gnnops_stream_t s) {
+    int es = 0;
+    const int rc = check_sizes("edge_attention_v1_backward", N, E, H, C, ldq, H * C, dtype, &es);
+    if (rc != GNNOPS_OK) return rc;
+    GNNOPS_REQUIRE(ldo >= H * C && ldd >= H && (ldg >= H * C || ldg == 0), GNNOPS_EINVAL,
+                   "edge_attention_v1_backward: a row pitch is shorter than the row");
+    GNNOPS_REQUIRE(grad_att, GNNOPS_EINVAL, "edge_attention_v1_backward: null pointer");
+    hipStream_t stream = (hipStream_t)s;
+    const int HC = (int)(H * C);
+    if (N == 0) return GNNOPS_OK;   // no destination: nothing is written
+    GNNOPS_REQUIRE(rowptr && out && lse && d && att && grad_out && grad_d && (E == 0 || (q && col && gq)), GNNOPS_EINVAL,
+                   "edge_attention_v1_backward: null pointer");
+    const size_t need = gnnops_edge_attention_v1_backward_workspace_bytes(N, H, C);
+    GNNOPS_REQUIRE(workspace && workspace_bytes >= need && (uintptr_t)workspace % 16 == 0, GNNOPS_EWORKSPACE,
+                   "edge_attention_v1_backward: workspace %zu < %zu", workspace_bytes, need);
+    const int max_vec = max_vec_of(es, {{q, ldq}, {att, 0}, {u, HC}, {out, ldo}, {grad_out, ldg}, {gq, HC}});
+    const Geometry geo = geometry((int)H, (int)C, max_vec, es);
+    const int rows = rows_of_partials(N, (int)H, (int)C);
+    GateArgs a{};
+    a.q = q; a.d = d; a.att = att; a.u = E ? u : nullptr; a.ks = E ? edge_scale : nullptr; a.g = grad_out; a.o = out;
+    a.rowptr = rowptr; a.perm = perm; a.col = col;
+    a.dd = grad_d; a.gq = gq; a.lse = const_cast<float*>(lse); a.partial = (float*)workspace;
+    a.N = N; a.ldq = ldq; a.ldd = ldd; a.ldo = ldo; a.ldg = ldg; a.H = (int)H; a.C = (int)C;
+    a.slope = negative_slope; a.row_slope = has_row_slope ? row_slope : 1.f;
+    a.gshift = geo.gshift; a.hblocks = geo.hblocks;
+    a.nwaves = rows * geo.hblocks;
+    const int grid = (int)gnnops_cdiv(a.nwaves, 4);
+    gate_launch<true>(a, geo, grid, dtype, stream);
+    const dim3 dgrid((unsigned)gnnops_cdiv(HC, 256));
+    switch (dtype) {
+        case GNNOPS_F32: hipLaunchKernelGGL(attention_datt_kernel<float>, dgrid, dim3(256), 0, stream, a.partial, rows, HC, (float*)grad_att); break;
+        case GNNOPS_F16: hipLaunchKernelGGL(attention_datt_kernel<__half>, dgrid, dim3(256), 0, stream, a.partial, rows, HC, (__half*)grad_att); break;
+        default: hipLaunchKernelGGL(attention_datt_kernel<__hip_bfloat16>, dgrid, dim3(256), 0, stream, a.partial, rows, HC, (__hip_bfloat16*)grad_att); break;
+    }
+    return gnnops_check_launch("edge_attention_v1_backward");
 }

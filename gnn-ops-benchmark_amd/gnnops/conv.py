@@ -21,6 +21,8 @@ fused multi-aggregator pass has no backward, so in a graph that needs gradients 
 
 Attention: `GATv2Conv` (the reference's model zoo, graph_benchmark/models/ptg_models.py:208-236) is one dense product and one
 attention pass, `edge_attention` (csrc/attention.hip: online softmax per destination and head, trainable) — SURVEY.md §8(f) rank 1.
+`GATConv` (the original GAT), `GATEConv` and the `AttentiveFP` model on them (the reference's AttentiveFPREG, ptg_models.py:91-120) run
+on the second member of that family, `edge_attention_v1`: per-edge rows, a leaky ReLU on the row, attention dropout after the softmax.
 """
 import ctypes
 
@@ -197,7 +199,8 @@ class _Packed:
         self.key = self.weight = self.bias = self._alive = None
 
     def get(self, params, blocks, stack=False):
-        """params: the Parameters the blocks are cut from; blocks: [(weight or a column slice of it [out, in], bias or None)]."""
+        """params: the Parameters the blocks are cut from; blocks: [(weight or a column slice of it [out, in], bias or None)], or a
+        callable that returns that list."""
         # Module.to() / .half() swap a parameter's data without touching its version counter: the pointer and dtype are in the key
         # tensors created under torch.inference_mode() have no version counter: nothing derived from them is cached
         if _wants_grad(*params):     # training: the packed operand is part of the graph (cat / t are differentiable) and never cached
@@ -213,6 +216,8 @@ class _Packed:
 
     @staticmethod
     def _pack(blocks, stack):
+        if callable(blocks):     # blocks that cost weight-sized work to cut (a fold, a pad) are made only when the cache misses
+            blocks = blocks()
         if stack:
             weight = torch.cat([wt.t() for wt, _ in blocks], dim=0).contiguous()
             biases = [b for _, b in blocks if b is not None]
@@ -764,3 +769,296 @@ class GATv2Conv(_Layer):
         if not self.concat:
             out = out.view(n_dst, H, C).mean(dim=1)
         return out if self.bias is None else out + self.bias
+
+
+# ---- attention: GAT (v1), GATEConv and AttentiveFP (csrc/attention.hip, gate_fwd_kernel / gate_bwd_kernel) ------------------
+def _v1_operands(q, d, att, edge_index, num_dst, heads, u, edge_scale):
+    op = "edge_attention_v1"
+    _require_gpu(q, d, att, edge_index, u, edge_scale)
+    HC = att.numel()
+    if heads < 1 or HC == 0 or HC % heads:
+        raise RuntimeError(f"{op}: heads = {heads} does not divide the row width {HC} (att has one entry per head and channel)")
+    if HC > 8192:
+        raise RuntimeError(f"{op}: heads * channels = {HC} exceeds the row limit of 8192")
+    if any(t is not None and t.dtype != q.dtype for t in (d, att, u, edge_scale)):
+        raise RuntimeError(f"{op}: operands must have the same dtype")
+    q, ldq = _rows(q, "q", 1, HC, op=op)
+    d, ldd = _rows(d, "d", 1, heads, op=op)
+    if d.size(0) != num_dst:
+        raise RuntimeError(f"{op}: d has one row per destination and one column per head")
+    if q.size(0) >= 2 ** 31:
+        raise NotImplementedError(f"{op}: 2^31 or more source rows")
+    edge_index, src_rows, dst_rows = _coo_rows_cols(edge_index, op)
+    E = edge_index.size(1)
+    if u is not None:
+        if u.dim() != 2 or tuple(u.shape) != (E, HC):
+            raise RuntimeError(f"{op}: u must be [E, heads * channels] = [{E}, {HC}], in the order of edge_index")
+        u = u.contiguous()
+    if edge_scale is not None:
+        if edge_scale.dim() != 2 or tuple(edge_scale.shape) != (E, heads):
+            raise RuntimeError(f"{op}: edge_scale must be [E, heads] = [{E}, {heads}], in the order of edge_index")
+        edge_scale = edge_scale.detach().contiguous()
+    plan = get_plan(dst_rows, num_dst, owner=edge_index, tag=1, companion=src_rows)   # the plans of edge_attention: nothing new on a warm call
+    if plan.col is not None or E == 0:
+        col = plan.col if E else src_rows
+    else:
+        col, _ = _csr_arrays(plan, src_rows, None, owner=edge_index, tag=0)
+    return q, ldq, d, ldd, att.contiguous().view(-1), u, edge_scale, edge_index, src_rows, plan, col, E, HC
+
+
+def _v1_forward(q, d, att, edge_index, num_dst, heads, u, row_slope, negative_slope, edge_scale):
+    """(out [num_dst, H * C], lse fp32 [num_dst, H]) of one launch of gnnops_edge_attention_v1."""
+    q, ldq, d, ldd, att, u, ks, edge_index, _, plan, col, E, HC = _v1_operands(q, d, att, edge_index, num_dst, heads, u, edge_scale)
+    out = torch.empty((num_dst, HC), dtype=q.dtype, device=q.device)
+    lse = torch.empty((num_dst, heads), dtype=torch.float32, device=q.device)
+    ptr = lambda t: t.data_ptr() if t is not None else None   # noqa: E731
+    with _on(q.device):
+        check(_lib.load().gnnops_edge_attention_v1(q.data_ptr(), ldq, d.data_ptr(), ldd, att.data_ptr(), ptr(u), ptr(ks), plan.rowptr.data_ptr(),
+                                                   plan.perm.data_ptr(), col.data_ptr(), out.data_ptr(), HC, lse.data_ptr(), num_dst, E, heads,
+                                                   HC // heads, int(row_slope is not None), float(row_slope or 0.0), float(negative_slope),
+                                                   _dtype_code(q, "edge_attention_v1"), _stream()), "edge_attention_v1")
+    return out, lse
+
+
+def edge_attention_v1(q, d, att, edge_index, num_dst, heads, u=None, row_slope=None, negative_slope=0.2, edge_scale=None):
+    """out[i, h, :] = sum over the edges e = (j -> i) of softmax_e(s[e, h]) * edge_scale[e, h] * r[e, h, :], with
+    r = q[j, h] + u[e, h] (through leaky_relu(., row_slope) when row_slope is given) and s[e, h] = leaky_relu(att[h] . r[e, h] + d[i, h],
+    negative_slope): the message and aggregation of GATConv (u, row_slope absent) and of AttentiveFP's GATEConv in one pass with an
+    online softmax (csrc/attention.hip). q [N_src, H * C] and d [num_dst, H] may be column blocks of one product; att holds H * C
+    entries; u [E, H * C] and edge_scale [E, H] follow the order of edge_index. edge_scale (the attention dropout mask divided by
+    1 - p) multiplies the weighted sum only, never the softmax denominator, and is not differentiated. A destination without edges
+    gets a zero row. Differentiable in q, d, att and u."""
+    if _wants_grad(q, d, att, u):
+        return _EdgeAttentionV1.apply(q, d, att, u, edge_scale, edge_index, num_dst, heads, row_slope, float(negative_slope))
+    return _v1_forward(q, d, att, edge_index, num_dst, heads, u, row_slope, negative_slope, edge_scale)[0]
+
+
+class _EdgeAttentionV1(torch.autograd.Function):
+    """backward (gnnops_edge_attention_v1_backward, destination-ordered like the forward): d d and d att from the kernel, and one
+    per-edge tensor gq [E, H * C] in edge order: d u is gq itself, d q its segment sum over the plan of the source ids."""
+
+    @staticmethod
+    def forward(ctx, q, d, att, u, edge_scale, edge_index, num_dst, heads, row_slope, negative_slope):
+        out, lse = _v1_forward(q, d, att, edge_index, num_dst, heads, u, row_slope, negative_slope, edge_scale)
+        ctx.meta = (num_dst, heads, row_slope, negative_slope, u is not None, edge_scale is not None)
+        ctx.save_for_backward(q, d, att, edge_index, out, lse, *(t for t in (u, edge_scale) if t is not None))
+        return out
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        q0, d0, att0, edge_index, out, lse, *rest = ctx.saved_tensors
+        num_dst, heads, row_slope, slope, has_u, has_ks = ctx.meta
+        u0 = rest.pop(0) if has_u else None
+        ks0 = rest.pop(0) if has_ks else None
+        q, ldq, d, ldd, att, u, ks, edge_index, src_rows, plan, col, E, HC = _v1_operands(q0, d0, att0, edge_index, num_dst, heads, u0, ks0)
+        need_q, need_d, need_att, need_u = ctx.needs_input_grad[:4]
+        tail = (None,) * 6
+        if E == 0 or num_dst == 0:
+            return (torch.zeros_like(q0) if need_q else None, torch.zeros_like(d0) if need_d else None,
+                    torch.zeros_like(att0) if need_att else None, torch.zeros_like(u0) if has_u and need_u else None) + tail
+        # the layouts autograd hands over, as _EdgeAttention.backward takes them
+        g = grad_out if grad_out.dim() == 2 and (grad_out.stride(1) == 1 or grad_out.size(1) == 1) else grad_out.contiguous()
+        g, ldg = _rows(g, "the output gradient", 1, HC, op="edge_attention_v1")
+        if g.size(0) > 1 and g.stride(0) == 0:
+            ldg = 0
+        d_d = torch.empty((num_dst, heads), dtype=q.dtype, device=q.device)
+        gq = torch.empty((E, HC), dtype=q.dtype, device=q.device)
+        d_att = torch.empty(HC, dtype=q.dtype, device=q.device)
+        L = _lib.load()
+        ws_bytes = L.gnnops_edge_attention_v1_backward_workspace_bytes(num_dst, heads, HC // heads)
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=q.device)
+        ptr = lambda t: t.data_ptr() if t is not None else None   # noqa: E731
+        with _on(q.device):
+            check(L.gnnops_edge_attention_v1_backward(q.data_ptr(), ldq, d.data_ptr(), ldd, att.data_ptr(), ptr(u), ptr(ks), out.data_ptr(), HC,
+                                                      lse.data_ptr(), g.data_ptr(), ldg, plan.rowptr.data_ptr(), plan.perm.data_ptr(),
+                                                      col.data_ptr(), d_d.data_ptr(), gq.data_ptr(), d_att.data_ptr(), num_dst, E, heads,
+                                                      HC // heads, int(row_slope is not None), float(row_slope or 0.0), slope,
+                                                      _dtype_code(q, "edge_attention_v1"), ws.data_ptr(), ws_bytes, _stream()),
+                  "edge_attention_v1_backward")
+        d_q = None
+        if need_q:
+            plan_src = get_plan(src_rows, q.size(0), owner=edge_index, tag=0)
+            d_q = ops.scatter(gq, plan_src, 0, None, None, "sum")
+            if q0.size(1) != HC:         # q was a column block wider than the H * C the pass reads
+                d_q = torch.nn.functional.pad(d_q, (0, q0.size(1) - HC))
+        if need_d and d0.size(1) != heads:
+            d_d = torch.nn.functional.pad(d_d, (0, d0.size(1) - heads))
+        return (d_q, d_d if need_d else None, d_att.view(att0.shape) if need_att else None, gq if has_u and need_u else None) + tail
+
+
+def _dropout_scale(E, heads, p, dtype, device):
+    """The attention dropout mask of one call, [E, H]: Bernoulli(1 - p) drawn with torch, already divided by 1 - p."""
+    keep = torch.rand((E, heads), device=device) >= p
+    return (keep.to(torch.float32) / (1.0 - p)).to(dtype)
+
+
+def _fold(att, weight, heads):
+    """[H, in]: row h = att[h, :] @ weight[h * C:(h + 1) * C, :], so that x @ row^T = att[h] . (x W^T)[h] — the per-node score term
+    as H more columns of the layer's one product."""
+    return torch.einsum("hc,hci->hi", att.view(heads, -1), weight.view(heads, att.numel() // heads, weight.size(1)))
+
+
+def _pad8(blocks, like):
+    """Zero columns up to a multiple of 8, so that every row of the product starts on a 16-byte boundary in every type."""
+    width = sum(w.size(0) for w, _ in blocks)
+    if width % 8:
+        blocks = blocks + [(like.new_zeros((8 - width % 8, like.size(1))), None)]
+    return blocks
+
+
+class GATConv(_Layer):
+    """x'_i = sum_j alpha_ij W x_j (+ bias),  alpha_ij = softmax_j(leaky_relu(att_src . W x_j + att_dst . W x_i))  per head
+    (torch_geometric 2.0.x GATConv, Velickovic et al. 2018; AttentiveFP's atom layers after the first and its read-out). One product
+    x @ [W^T | fold(att_dst, W_dst)^T]: the per-destination score term d comes out of it as H more columns (att_dst folded into the
+    weight, `_fold`), then one attention pass (`edge_attention_v1`), the mean over heads (concat=False) and the bias. Parameter names
+    follow PyG 2.0.x (lin_src, lin_dst, att_src, att_dst, bias); parity unpinned. Self loops and the bipartite pair as GATv2Conv.
+    Attention dropout: a Bernoulli mask [E, H] drawn with torch, scaled by 1 / (1 - p), applied after the softmax (edge_scale)."""
+
+    def __init__(self, in_channels, out_channels, heads=1, concat=True, negative_slope=0.2, dropout=0.0, add_self_loops=True, bias=True):
+        super().__init__()
+        self.in_channels, self.out_channels, self.heads, self.concat = in_channels, out_channels, heads, concat
+        self.negative_slope, self.dropout, self.add_self_loops = negative_slope, dropout, add_self_loops
+        if isinstance(in_channels, int):
+            self.lin_src = torch.nn.Linear(in_channels, heads * out_channels, bias=False)
+            self.lin_dst = self.lin_src
+        else:
+            self.lin_src = torch.nn.Linear(in_channels[0], heads * out_channels, bias=False)
+            self.lin_dst = torch.nn.Linear(in_channels[1], heads * out_channels, bias=False)
+        self.att_src = torch.nn.Parameter(torch.empty(1, heads, out_channels))
+        self.att_dst = torch.nn.Parameter(torch.empty(1, heads, out_channels))
+        self.bias = torch.nn.Parameter(torch.zeros(heads * out_channels if concat else out_channels)) if bias else None
+        for w in (self.lin_src.weight, self.lin_dst.weight, self.att_src, self.att_dst):      # glorot, as PyG
+            torch.nn.init.xavier_uniform_(w)
+        self._pk_both, self._pk_src, self._pk_dst = _Packed(), _Packed(), _Packed()
+        self._looped = None
+
+    _with_self_loops = GATv2Conv._with_self_loops
+
+    def forward(self, x, edge_index, size=None):
+        H, C = self.heads, self.out_channels
+        HC = H * C
+        ws, wd = self.lin_src.weight, self.lin_dst.weight
+        if isinstance(x, (tuple, list)):
+            if self.add_self_loops:
+                raise RuntimeError("GATConv: a bipartite pair needs add_self_loops=False")
+            x_src, x_dst = x
+            _require_gpu(x_src, x_dst, edge_index)
+            q = _dense(x_src.contiguous(), self._pk_src.get([ws], [(ws, None)]))
+            d = _dense(x_dst.contiguous(), self._pk_dst.get([wd, self.att_dst], lambda: _pad8([(_fold(self.att_dst, wd, H), None)], wd)))[:, :H]
+            n_dst = x_dst.size(0) if size is None else size[1]
+        else:
+            _require_gpu(x, edge_index)
+            n_dst = x.size(0)
+            qd = _dense(x.contiguous(), self._pk_both.get([ws, wd, self.att_dst], lambda: _pad8([(ws, None), (_fold(self.att_dst, wd, H), None)], ws)))
+            q, d = qd[:, :HC], qd[:, HC:HC + H]
+            if self.add_self_loops:
+                edge_index = self._with_self_loops(edge_index, n_dst)
+        scale = None
+        if self.dropout > 0.0 and self.training:
+            scale = _dropout_scale(edge_index.size(1), H, self.dropout, q.dtype, q.device)
+        out = edge_attention_v1(q, d, self.att_src, edge_index, n_dst, H, negative_slope=self.negative_slope, edge_scale=scale)
+        if not self.concat:
+            out = out.view(n_dst, H, C).mean(dim=1)
+        return out if self.bias is None else out + self.bias
+
+
+class _EdgeLinear(torch.autograd.Function):
+    """u = edge_attr @ weight_t for [E, edge_dim] edge features, edge_dim tiny. The backward of gnnops.autograd.matmul copies the
+    transpose of its left operand, and that copy stops at 64 * 65535 rows; the transpose of ONE column is the same memory, so for
+    edge_dim = 1 (the reference's config) d weight_t = edge_attr.view(1, E) @ g needs no copy and no limit."""
+
+    @staticmethod
+    def forward(ctx, edge_attr, weight_t):
+        ctx.save_for_backward(edge_attr, weight_t)
+        return ops.matmul(edge_attr, weight_t)
+
+    @staticmethod
+    def backward(ctx, g):
+        from .sparse import transpose_contiguous
+
+        edge_attr, weight_t = ctx.saved_tensors
+        g = g.contiguous()
+        d_e = d_w = None
+        if ctx.needs_input_grad[0]:
+            d_e = ops.matmul(g, transpose_contiguous(weight_t))
+        if ctx.needs_input_grad[1]:
+            e_t = edge_attr.view(1, -1) if edge_attr.size(1) == 1 else transpose_contiguous(edge_attr)
+            d_w = ops.matmul(e_t, g)
+        return d_e, d_w
+
+
+class GATEConv(_Layer):
+    """AttentiveFP's first atom layer (torch_geometric.nn.models.attentive_fp.GATEConv, one head):
+    x_j' = leaky_relu(lin1([x_j, e_ji])),  alpha_ji = softmax_j(leaky_relu(att_l . x_j' + att_r . x_i)),  x'_i = lin2(sum_j alpha_ji x_j') + bias
+    (both slopes 0.01). lin1 splits into its node and its edge columns: one product x @ [W1x^T | att_r^T] gives q and d, one product
+    edge_attr @ W1e^T gives the per-edge rows u, one attention pass (`edge_attention_v1` with u and row_slope), and lin2 — linear —
+    is applied once to the aggregate instead of once per edge. No self loops. Attention dropout as GATConv. Training with
+    edge_dim > 1 on more than 64 * 65535 edges meets the row limit of the package's transpose copy (`_EdgeLinear`); edge_dim = 1 does not."""
+
+    def __init__(self, in_channels, out_channels, edge_dim, dropout=0.0):
+        super().__init__()
+        self.in_channels, self.out_channels, self.edge_dim, self.dropout = in_channels, out_channels, edge_dim, dropout
+        self.att_l = torch.nn.Parameter(torch.empty(1, out_channels))
+        self.att_r = torch.nn.Parameter(torch.empty(1, in_channels))
+        self.lin1 = torch.nn.Linear(in_channels + edge_dim, out_channels, bias=False)
+        self.lin2 = torch.nn.Linear(out_channels, out_channels, bias=False)
+        self.bias = torch.nn.Parameter(torch.zeros(out_channels))
+        for w in (self.att_l, self.att_r, self.lin1.weight, self.lin2.weight):
+            torch.nn.init.xavier_uniform_(w)
+        self._pk_x, self._pk_e, self._pk_2 = _Packed(), _Packed(), _Packed()
+
+    def forward(self, x, edge_index, edge_attr):
+        _require_gpu(x, edge_index, edge_attr)
+        cin, cout = self.in_channels, self.out_channels
+        w1 = self.lin1.weight
+        qd = _dense(x.contiguous(), self._pk_x.get([w1, self.att_r], lambda: _pad8([(w1[:, :cin], None), (self.att_r, None)], self.att_r)))
+        q, d = qd[:, :cout], qd[:, cout:cout + 1]
+        w1e_t = self._pk_e.get([w1], lambda: [(w1[:, cin:], None)])[0]
+        u = _EdgeLinear.apply(edge_attr.contiguous(), w1e_t) if _wants_grad(edge_attr, w1e_t) else ops.matmul(edge_attr.contiguous(), w1e_t)
+        scale = None
+        if self.dropout > 0.0 and self.training:
+            scale = _dropout_scale(edge_index.size(1), 1, self.dropout, q.dtype, q.device)
+        agg = edge_attention_v1(q, d, self.att_l, edge_index, x.size(0), 1, u=u, row_slope=0.01, negative_slope=0.01, edge_scale=scale)
+        return _dense(agg, self._pk_2.get([self.lin2.weight, self.bias], [(self.lin2.weight, self.bias)]))
+
+
+class AttentiveFP(torch.nn.Module):
+    """The molecule regressor of Xiong et al. 2020 as torch_geometric.nn.models.AttentiveFP builds it (submodule names lin1,
+    atom_convs, atom_grus, mol_conv, mol_gru, lin2; the reference's AttentiveFPREG, graph_benchmark/models/ptg_models.py): atom
+    layers of GATEConv / GATConv each followed by a GRU cell, a read-out of num_timesteps rounds of GATConv over the bipartite
+    (atom -> molecule) graph with a GRU cell, and a Linear. The attention layers are this package's fused ones, the sum over a
+    molecule's atoms its scatter; GRUCell, elu and the feature dropout are torch's."""
+
+    def __init__(self, in_channels, hidden_channels, out_channels, edge_dim, num_layers, num_timesteps, dropout=0.0):
+        super().__init__()
+        self.num_layers, self.num_timesteps, self.dropout = num_layers, num_timesteps, dropout
+        self.lin1 = torch.nn.Linear(in_channels, hidden_channels)
+        self.atom_convs = torch.nn.ModuleList([GATEConv(hidden_channels, hidden_channels, edge_dim, dropout)])
+        self.atom_grus = torch.nn.ModuleList([torch.nn.GRUCell(hidden_channels, hidden_channels)])
+        for _ in range(num_layers - 1):
+            self.atom_convs.append(GATConv(hidden_channels, hidden_channels, dropout=dropout, add_self_loops=False, negative_slope=0.01))
+            self.atom_grus.append(torch.nn.GRUCell(hidden_channels, hidden_channels))
+        self.mol_conv = GATConv(hidden_channels, hidden_channels, dropout=dropout, add_self_loops=False, negative_slope=0.01)
+        self.mol_gru = torch.nn.GRUCell(hidden_channels, hidden_channels)
+        self.lin2 = torch.nn.Linear(hidden_channels, out_channels)
+
+    def forward(self, x, edge_index, edge_attr, batch, num_graphs=None):
+        """batch int64 [N]: the molecule of each atom; num_graphs spares the read of batch.max() from the device."""
+        from . import autograd
+        F = torch.nn.functional
+        _require_gpu(x, edge_index, edge_attr, batch)
+        x = F.leaky_relu(self.lin1(x))
+        for k, (conv, gru) in enumerate(zip(self.atom_convs, self.atom_grus)):
+            h = F.elu(conv(x, edge_index, edge_attr) if k == 0 else conv(x, edge_index))
+            h = F.dropout(h, p=self.dropout, training=self.training)
+            x = gru(h, x).relu()
+        n = x.size(0)
+        G = int(batch.max()) + 1 if num_graphs is None else num_graphs
+        out = autograd.scatter(x, batch, 0, None, G, "sum").relu()
+        to_mol = torch.stack([torch.arange(n, dtype=batch.dtype, device=batch.device), batch])   # one object: its plans serve every round
+        for _ in range(self.num_timesteps):
+            h = F.elu(self.mol_conv((x, out), to_mol, size=(n, G)))
+            h = F.dropout(h, p=self.dropout, training=self.training)
+            out = self.mol_gru(h, out).relu()
+        out = F.dropout(out, p=self.dropout, training=self.training)
+        return self.lin2(out)

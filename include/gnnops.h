@@ -562,6 +562,32 @@ int gnnops_edge_attention_backward(const void* q, int64_t ldq, const void* p, in
                                    int64_t E, int64_t H, int64_t C, float negative_slope, int dtype, void* workspace,
                                    size_t workspace_bytes, gnnops_stream_t stream);
 
+/* The second member of the family (GATConv, the original GAT, and AttentiveFP's GATEConv): the score is a per-edge scalar plus
+ * a per-destination scalar, the row may carry a per-edge part u and a leaky ReLU of its own, and a per-edge, per-head scale
+ * (the attention dropout mask divided by 1 - p) enters the weighted sum only, never the denominator.
+ *   t[e,h,:] = q[j,h,:] + u[e,h,:]            r = has_row_slope ? leaky_relu(t, row_slope) : t              edge e = (j -> i)
+ *   s[e,h] = leaky_relu(att[h,:] . r[e,h,:] + d[i,h], negative_slope)       lse[i,h] = log sum_{e into i} exp(s[e,h])
+ *   out[i,h,:] = sum_{e into i} exp(s[e,h] - lse[i,h]) * edge_scale[e,h] * r[e,h,:]
+ * q [N_src, >= H*C] (pitch ldq), d [N, >= H] (pitch ldd), att [H*C], out [N, H*C] (pitch ldo) in `dtype`; lse fp32 [N, H].
+ * u [E, H*C] and edge_scale [E, H] are dense, in `dtype`, their rows the ORIGINAL edge ids (read through perm, offsets in
+ * 64 bits); NULL = absent (u = 0, edge_scale = 1). row_slope is read only when has_row_slope != 0. Limits, the plan operands
+ * and the empty destination as gnnops_edge_attention. One launch, no allocation, no synchronisation.
+ * Backward: grad_d [N, H] dense (summed in fp32, stored once per destination); gq [E, H*C] dense, row = original edge id,
+ *   = d u, and d q = its segment sum over the plan of the source ids; grad_att [H*C] through the workspace of
+ *   gnnops_edge_attention_v1_backward_workspace_bytes(N, H, C) bytes (host-only; fixed-order sum, the same bits every run).
+ *   edge_scale is not differentiated. N == 0: nothing is written. */
+int gnnops_edge_attention_v1(const void* q, int64_t ldq, const void* d, int64_t ldd, const void* att, const void* u,
+                             const void* edge_scale, const int32_t* rowptr, const int32_t* perm, const int64_t* col, void* out,
+                             int64_t ldo, float* lse, int64_t N, int64_t E, int64_t H, int64_t C, int has_row_slope,
+                             float row_slope, float negative_slope, int dtype, gnnops_stream_t stream);
+size_t gnnops_edge_attention_v1_backward_workspace_bytes(int64_t N, int64_t H, int64_t C);
+int gnnops_edge_attention_v1_backward(const void* q, int64_t ldq, const void* d, int64_t ldd, const void* att, const void* u,
+                                      const void* edge_scale, const void* out, int64_t ldo, const float* lse,
+                                      const void* grad_out, int64_t ldg, const int32_t* rowptr, const int32_t* perm,
+                                      const int64_t* col, void* grad_d, void* gq, void* grad_att, int64_t N, int64_t E,
+                                      int64_t H, int64_t C, int has_row_slope, float row_slope, float negative_slope, int dtype,
+                                      void* workspace, size_t workspace_bytes, gnnops_stream_t stream);
+
 /* ---------------------------------------------------------------------------------------------
  * The remaining ops of the reference's list (ops.txt:17-19, 29-41) - SURVEY.md 8(f) rank 4. Neither package is in the
  * reference tree (torch-spline-conv 1.2.1, torch-cluster 1.5.9: requirements.txt:214, :210) and the reference has no
