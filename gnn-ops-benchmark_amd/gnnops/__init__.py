@@ -28,7 +28,9 @@ from .sparse import (SpmmTiles, coalesce, coalesce_sparse_tensor, sddmm, sort, s
 from .segment import (expand_rowptr, gather_coo, gather_csr, rowptr_from_sorted, scatter_log_softmax, scatter_logsumexp, scatter_softmax,
                       scatter_std, segment_coo, segment_csr)
 from . import autograd, layers
-from .conv import AttentiveFP, GATConv, GATEConv, GATv2Conv, edge_attention, edge_attention_v1
+from .conv import AttentiveFP, GATConv, GATEConv, GATv2Conv, GCNConv, GraphUNet, TopKPooling, edge_attention, edge_attention_v1, gcn_propagate
+from .pool import filter_adj, remove_self_loops, topk
+from . import pool
 from .aten import install, uninstall, installed
 
 __all__ = [
@@ -38,4 +40,5 @@ __all__ = [
     "set_plan_cache", "install", "uninstall", "installed", "coalesce", "coalesce_sparse_tensor", "sort", "sparse_mm",
     "spmm", "spmm_csr", "spmm_tiles", "SpmmTiles", "spmm_t", "sddmm", "expand_rowptr", "spspmm", "transpose", "transpose_contiguous", "addmm", "matmul", "index_add_select_sum", "segment_csr", "segment_coo", "gather_csr", "gather_coo",
     "rowptr_from_sorted", "scatter_softmax", "scatter_log_softmax", "scatter_logsumexp", "scatter_std", "autograd", "layers", "GATv2Conv", "edge_attention", "GATConv", "GATEConv", "AttentiveFP", "edge_attention_v1",
+    "GCNConv", "TopKPooling", "GraphUNet", "gcn_propagate", "pool", "topk", "filter_adj", "remove_self_loops",
 ]

@@ -123,6 +123,16 @@ SIGNATURES = {
     "gnnops_addmm_ld": (_ci, [_vp, _i64, _vp, _vp, _vp, _i64, _i64, _i64, _ci, _vp, _sz, _vp]),
     "gnnops_fused_index_add_select_sum_workspace_bytes": (_sz, [_i64, _i64]),
     "gnnops_fused_index_add_select_sum": (_ci, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _ci, _vp, _sz, _vp]),
+    "gnnops_segment_topk_max_len": (_i64, []),
+    "gnnops_segment_topk_counts": (_ci, [_vp, _i64, ctypes.c_float, _i64, _vp, _vp, _vp]),
+    "gnnops_segment_topk_workspace_bytes": (_sz, [_i64, _i64, _ci]),
+    "gnnops_segment_topk": (_ci, [_vp, _vp, _vp, _vp, _i64, _i64, _i64, _ci, _ci, _vp, _sz, _vp]),
+    "gnnops_node_map": (_ci, [_vp, _i64, _i64, _vp, _vp]),
+    "gnnops_filter_edges_tile": (_i64, []),
+    "gnnops_filter_edges_workspace_bytes": (_sz, [_i64]),
+    "gnnops_filter_edges": (_ci, [_vp, _vp, _vp, _i64, _vp, _i64, _ci, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "gnnops_gcn_degree": (_ci, [_vp, _vp, _vp, _vp, _i64, _i64, ctypes.c_float, _vp, _vp, _vp]),
+    "gnnops_gcn_propagate": (_ci, [_vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _ci, _vp]),
 }
 
 _lib = None

@@ -23,6 +23,9 @@ Attention: `GATv2Conv` (the reference's model zoo, graph_benchmark/models/ptg_mo
 attention pass, `edge_attention` (csrc/attention.hip: online softmax per destination and head, trainable) — SURVEY.md §8(f) rank 1.
 `GATConv` (the original GAT), `GATEConv` and the `AttentiveFP` model on them (the reference's AttentiveFPREG, ptg_models.py:91-120) run
 on the second member of that family, `edge_attention_v1`: per-edge rows, a leaky ReLU on the row, attention dropout after the softmax.
+
+GraphUNet's layers (the reference's GraphUNetREG): `GCNConv` is one product and `gcn_propagate` (csrc/gcn.hip: symmetric normalisation
+with edge weights, trainable), `TopKPooling` selects with `gnnops.pool.topk` / `filter_adj` (csrc/pool.hip), `GraphUNet` is the model.
 """
 import ctypes
 
@@ -1062,3 +1065,225 @@ class AttentiveFP(torch.nn.Module):
             out = self.mol_gru(h, out).relu()
         out = F.dropout(out, p=self.dropout, training=self.training)
         return self.lin2(out)
+
+
+# ---- GCNConv, TopKPooling and GraphUNet (csrc/gcn.hip, csrc/pool.hip) -------------------------------------------------------
+def _gcn_plan(edge_index, num_nodes, flip):
+    """(plan, plan-ordered column ids, E) of the destination plan (``flip``: of the source ids) — the plans of `edge_reduce`."""
+    edge_index, src_rows, dst_rows = _coo_rows_cols(edge_index, "gcn_propagate")
+    if flip:
+        src_rows, dst_rows = dst_rows, src_rows
+    E = edge_index.size(1)
+    plan = get_plan(dst_rows, num_nodes, owner=edge_index, tag=0 if flip else 1, companion=src_rows)
+    if plan.col is not None or E == 0:
+        col = plan.col if E else src_rows
+    else:
+        col, _ = _csr_arrays(plan, src_rows, None, owner=edge_index, tag=1 if flip else 0)
+    return plan, col, E
+
+
+def _gcn_degree(edge_index, w, num_nodes, fill_value):
+    """(dis, lw) fp32 [num_nodes] of gnnops_gcn_degree: D^-1/2 and the self-loop weight of every node."""
+    plan, col, E = _gcn_plan(edge_index, num_nodes, False)
+    dev = edge_index.device
+    dis = torch.empty(num_nodes, dtype=torch.float32, device=dev)
+    lw = torch.empty(num_nodes, dtype=torch.float32, device=dev)
+    with _on(dev):
+        check(_lib.load().gnnops_gcn_degree(plan.rowptr.data_ptr(), plan.perm.data_ptr(), col.data_ptr() if E else None,
+                                            w.data_ptr() if w is not None else None, num_nodes, E, float(fill_value),
+                                            dis.data_ptr(), lw.data_ptr(), _stream()), "gcn_degree")
+    return dis, lw
+
+
+def _gcn_launch(h, edge_index, w, dis, lw, bias, num_nodes, flip):
+    plan, col, E = _gcn_plan(edge_index, num_nodes, flip)
+    K = h.size(1)
+    h, ldh = _rows(h, "h", 1, K, op="gcn_propagate")
+    if h.size(0) > 1 and h.stride(0) == 0:
+        ldh = 0
+    out = torch.empty((num_nodes, K), dtype=h.dtype, device=h.device)
+    with _on(h.device):
+        check(_lib.load().gnnops_gcn_propagate(h.data_ptr(), ldh, plan.rowptr.data_ptr(), plan.perm.data_ptr(),
+                                               col.data_ptr() if E else None, w.data_ptr() if w is not None else None,
+                                               dis.data_ptr(), lw.data_ptr(), bias.data_ptr() if bias is not None else None,
+                                               out.data_ptr(), K, num_nodes, E, K, _dtype_code(h, "gcn_propagate"), _stream()),
+              "gcn_propagate")
+    return out
+
+
+class _GCNPropagate(torch.autograd.Function):
+    """The normalised edge pass is a symmetric operator in h: d h is the same kernel over the plan of the source ids (tag 0 of the
+    same edge_index object) with the forward's dis / lw; d bias is the column sum of the output gradient."""
+
+    @staticmethod
+    def forward(ctx, h, bias, edge_index, w, num_nodes, fill_value):
+        dis, lw = _gcn_degree(edge_index, w, num_nodes, fill_value)
+        out = _gcn_launch(h, edge_index, w, dis, lw, bias, num_nodes, False)
+        ctx.num_nodes = num_nodes
+        ctx.save_for_backward(edge_index, dis, lw, *((w,) if w is not None else ()))
+        return out
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        edge_index, dis, lw, *rest = ctx.saved_tensors
+        w = rest[0] if rest else None
+        need_h, need_bias = ctx.needs_input_grad[:2]
+        # as _EdgeAttention.backward: rows of unit column stride are read in place (pitch 0 = one row for all), the rest is copied
+        g = grad_out if grad_out.dim() == 2 and (grad_out.stride(1) == 1 or grad_out.size(1) == 1) else grad_out.contiguous()
+        d_h = _gcn_launch(g, edge_index, w, dis, lw, None, ctx.num_nodes, True) if need_h else None
+        d_bias = grad_out.sum(dim=0) if need_bias else None
+        return d_h, d_bias, None, None, None, None
+
+
+def gcn_propagate(h, edge_index, edge_weight, num_nodes, fill_value=1.0, bias=None):
+    """out = D^-1/2 (A + L) D^-1/2 h (+ bias): GCNConv's normalised aggregation (torch_geometric's add_remaining_self_loops +
+    gcn_norm + propagate) in two launches, without rewriting the edge list. L is diagonal: the weight of a node's last self loop
+    in edge order, ``fill_value`` for a node without one; A holds the other edges (j -> i) = (edge_index[0], edge_index[1]) with
+    ``edge_weight`` [E] (``None``: ones); D is the row sum of A + L, D^-1/2 = 0 where that is not positive. h [num_nodes, K] may be a
+    column block. Differentiable in h and bias; an ``edge_weight`` that requires grad raises."""
+    _require_gpu(h, edge_index, edge_weight, bias)
+    if edge_weight is not None and torch.is_grad_enabled() and edge_weight.requires_grad:
+        raise NotImplementedError("gnnops.conv.gcn_propagate: edge_weight requires grad, but the normalised edge pass has no backward "
+                                  "for its weights (differentiable in h and bias only); detach edge_weight")
+    if h.dim() != 2 or h.size(0) != num_nodes:
+        raise RuntimeError("gcn_propagate: h must be [num_nodes, K]")
+    if bias is not None and (bias.dtype != h.dtype or bias.numel() != h.size(1)):
+        raise RuntimeError("gcn_propagate: bias must hold K entries of h's dtype")
+    _dtype_code(h, "gcn_propagate")
+    w = None
+    if edge_weight is not None:
+        if edge_weight.numel() != edge_index.size(1):
+            raise RuntimeError("gcn_propagate: edge_weight has one entry per edge")
+        w = edge_weight.detach().reshape(-1).to(torch.float32).contiguous()
+    bias_c = bias.contiguous() if bias is not None else None
+    if _wants_grad(h, bias):
+        return _GCNPropagate.apply(h, bias_c, edge_index, w, num_nodes, float(fill_value))
+    dis, lw = _gcn_degree(edge_index, w, num_nodes, fill_value)
+    return _gcn_launch(h, edge_index, w, dis, lw, bias_c, num_nodes, False)
+
+
+class GCNConv(_Layer):
+    """x' = D^-1/2 (A + fill I) D^-1/2 x W^T + bias (Kipf & Welling 2017; torch_geometric 2.0.2 GCNConv — the layer the reference's
+    GraphUNetREG is built from, graph_benchmark/models/ptg_models.py): one dense product and `gcn_propagate`. ``improved=True`` makes
+    the self-loop weight 2. Parameter names and shapes follow PyG (``lin.weight`` [out, in], ``bias`` [out]; glorot / zeros) so a
+    state_dict moves across; torch_geometric is not available to compare against: parity unpinned. ``cached=True``,
+    ``normalize=False`` and ``add_self_loops=False`` are not implemented."""
+
+    def __init__(self, in_channels, out_channels, improved=False, cached=False, add_self_loops=True, normalize=True, bias=True):
+        super().__init__()
+        if cached or not add_self_loops or not normalize:
+            raise NotImplementedError("gnnops.conv.GCNConv: cached=True, add_self_loops=False and normalize=False are not implemented")
+        self.in_channels, self.out_channels, self.improved = in_channels, out_channels, improved
+        self.lin = torch.nn.Linear(in_channels, out_channels, bias=False)
+        self.bias = torch.nn.Parameter(torch.zeros(out_channels)) if bias else None
+        torch.nn.init.xavier_uniform_(self.lin.weight)
+        self._pk = _Packed()
+
+    def forward(self, x, edge_index, edge_weight=None):
+        _require_gpu(x, edge_index, edge_weight)
+        h = _dense(x.contiguous(), self._pk.get([self.lin.weight], [(self.lin.weight, None)]))
+        return gcn_propagate(h, edge_index, edge_weight, x.size(0), 2.0 if self.improved else 1.0, self.bias)
+
+
+class TopKPooling(torch.nn.Module):
+    """torch_geometric 2.0.2 TopKPooling (Gao & Ji 2019) without ``min_score``: score = nonlinearity(x . weight / |weight|), the
+    ceil(ratio * n) best nodes of every graph are kept (`gnnops.pool.topk`), x = x[perm] * score[perm] * multiplier, and the
+    edge list is cut down to the kept nodes and relabelled (`gnnops.pool.filter_adj`). ``weight`` [1, in_channels] as in PyG;
+    parity unpinned. The score is formed in float32 whatever x's dtype, so the selection does not hang on 16-bit rounding; the
+    gather is the package's differentiable index_select, so gradients reach x and weight. Two host reads (the two result sizes)."""
+
+    def __init__(self, in_channels, ratio=0.5, min_score=None, multiplier=1.0, nonlinearity=torch.tanh):
+        super().__init__()
+        if min_score is not None:
+            raise NotImplementedError("gnnops.conv.TopKPooling: min_score is not supported")
+        self.in_channels, self.ratio, self.multiplier, self.nonlinearity = in_channels, ratio, multiplier, nonlinearity
+        self.weight = torch.nn.Parameter(torch.empty(1, in_channels))
+        bound = 1.0 / (in_channels ** 0.5)
+        torch.nn.init.uniform_(self.weight, -bound, bound)
+
+    def forward(self, x, edge_index, edge_attr=None, batch=None, num_graphs=None):
+        from . import autograd, pool
+
+        _require_gpu(x, edge_index, edge_attr, batch)
+        n = x.size(0)
+        w = self.weight.float()
+        score = self.nonlinearity((x.float() * w).sum(dim=-1) / w.norm(p=2, dim=-1))
+        perm = pool.topk(score, self.ratio, batch, num_graphs)
+        kept = autograd.index_select(score.to(x.dtype).view(-1, 1), 0, perm)
+        out = autograd.index_select(x, 0, perm) * kept
+        if self.multiplier != 1:
+            out = self.multiplier * out
+        if batch is None:
+            batch = edge_index.new_zeros(n)
+        edge_index, edge_attr = pool.filter_adj(edge_index, edge_attr, perm, num_nodes=n)
+        return out, edge_index, edge_attr, batch[perm], perm, kept.view(-1)
+
+
+class GraphUNet(torch.nn.Module):
+    """torch_geometric.nn.models.GraphUNet (2.0.2; Gao & Ji 2019 — the reference's GraphUNetREG, graph_benchmark/models/ptg_models.py):
+    ``depth`` levels of GCNConv(improved=True) + TopKPooling on the squared adjacency going down, unpooling with a residual (sum, or
+    concatenation with ``sum_res=False``) going up. Submodule names ``down_convs``, ``pools``, ``up_convs`` and the forward order are
+    PyG's, so a state_dict moves across; torch_geometric is not available to compare against: parity unpinned. `augment_adj` is
+    remove_self_loops, one unit self loop per node, `gnnops.spspmm` of the matrix with itself (its result is coalesced row-major, which
+    is what sort_edge_index + spspmm give upstream) and remove_self_loops again; unpooling ``up[perm] = x`` is the package's
+    differentiable scatter. Edge weights are float32 at every level, whatever x's dtype. The pooled levels' edge lists are new
+    tensors on every forward, so only level 0's plans are cached across calls; inside one call a level's plans serve its down conv,
+    its up conv and their backward. ``num_graphs`` spares the host read of ``batch.max()``."""
+
+    def __init__(self, in_channels, hidden_channels, out_channels, depth, pool_ratios=0.5, sum_res=True, act=torch.relu):
+        super().__init__()
+        if depth < 1:
+            raise ValueError("GraphUNet: depth >= 1")
+        self.in_channels, self.hidden_channels, self.out_channels, self.depth = in_channels, hidden_channels, out_channels, depth
+        self.pool_ratios = list(pool_ratios) if isinstance(pool_ratios, (list, tuple)) else [pool_ratios] * depth
+        self.act, self.sum_res = act, sum_res
+        channels = hidden_channels
+        self.down_convs = torch.nn.ModuleList([GCNConv(in_channels, channels, improved=True)])
+        self.pools = torch.nn.ModuleList()
+        for i in range(depth):
+            self.pools.append(TopKPooling(channels, self.pool_ratios[i]))
+            self.down_convs.append(GCNConv(channels, channels, improved=True))
+        up_in = channels if sum_res else 2 * channels
+        self.up_convs = torch.nn.ModuleList([GCNConv(up_in, channels, improved=True) for _ in range(depth - 1)])
+        self.up_convs.append(GCNConv(up_in, out_channels, improved=True))
+
+    @staticmethod
+    def augment_adj(edge_index, edge_weight, num_nodes):
+        from . import pool
+        from .sparse import spspmm
+
+        edge_index, edge_weight = pool.remove_self_loops(edge_index, edge_weight)
+        loops = torch.arange(num_nodes, dtype=edge_index.dtype, device=edge_index.device)
+        edge_index = torch.cat([edge_index, torch.stack([loops, loops])], dim=1)
+        edge_weight = torch.cat([edge_weight, edge_weight.new_ones(num_nodes)])
+        edge_index, edge_weight = spspmm(edge_index, edge_weight, edge_index, edge_weight, num_nodes, num_nodes, num_nodes)
+        return pool.remove_self_loops(edge_index, edge_weight)
+
+    def forward(self, x, edge_index, batch=None, num_graphs=None, return_perms=False):
+        from . import autograd
+
+        _require_gpu(x, edge_index, batch)
+        if batch is None:
+            batch, num_graphs = edge_index.new_zeros(x.size(0)), 1
+        edge_weight = torch.ones(edge_index.size(1), dtype=torch.float32, device=x.device)
+        x = self.act(self.down_convs[0](x, edge_index, edge_weight))
+        xs, edge_indices, edge_weights, perms = [x], [edge_index], [edge_weight], []
+        for i in range(1, self.depth + 1):
+            edge_index, edge_weight = self.augment_adj(edge_index, edge_weight, x.size(0))
+            x, edge_index, edge_weight, batch, perm, _ = self.pools[i - 1](x, edge_index, edge_weight, batch, num_graphs)
+            edge_index, edge_weight = edge_index.contiguous(), edge_weight.contiguous()   # one object per level: its plans are built once
+            x = self.act(self.down_convs[i](x, edge_index, edge_weight))
+            if i < self.depth:
+                xs.append(x)
+                edge_indices.append(edge_index)
+                edge_weights.append(edge_weight)
+            perms.append(perm)
+        for i in range(self.depth):
+            j = self.depth - 1 - i
+            res, perm = xs[j], perms[j]
+            up = autograd.scatter(x, perm, 0, None, res.size(0), "sum")   # up[perm] = x: perm holds distinct ids
+            x = res + up if self.sum_res else torch.cat((res, up), dim=-1)
+            x = self.up_convs[i](x, edge_indices[j], edge_weights[j])
+            if i < self.depth - 1:
+                x = self.act(x)
+        return (x, perms) if return_perms else x

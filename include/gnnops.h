@@ -669,6 +669,65 @@ int gnnops_random_walk_node2vec(const int64_t* rowptr, const int64_t* col, const
 int gnnops_graclus_rounds(const int64_t* rowptr, const int64_t* col, const void* weight, int64_t N, uint64_t seed, int rounds,
                           int64_t* cluster, int64_t* proposal, int* d_active, int finish, int dtype, gnnops_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * GraphUNet's pieces (the reference's GraphUNetREG, graph_benchmark/models/ptg_models.py; torch_geometric 2.0.2 TopKPooling,
+ * filter_adj, GCNConv — the packages' published definitions, parity unpinned): csrc/pool.hip, csrc/gcn.hip.
+ *
+ * Per-graph top-k of a score vector. graph_ptr int32 [G+1]: the nodes of one graph are contiguous (a sorted `batch`).
+ *   gnnops_segment_topk_counts  k_g = min(k, n_g) for an integer k >= 1; with k < 1, k_g = ceil(ratio * float32(n_g)) in
+ *       float32 for a ratio in (0, 1], as (ratio * num_nodes.to(torch.float)).ceil(). out_ptr int32 [G+1] = exclusive scan
+ *       of k_g; d_info (device int64 [2]) = { sum of k_g, the longest graph } — the one host read the caller needs: the
+ *       first sizes perm, the second picks the route. One workgroup.
+ *   gnnops_segment_topk  perm int64 [out_ptr[G]]: global node ids, graph after graph, each graph's in descending score.
+ *       Ties go to the lower node id, -0.0 orders as +0.0, a NaN ranks above every number (gnnops_sort, descending).
+ *       score [N] in `dtype`. max_graph_len: at least the longest graph (d_info[1]).
+ *       route 0: on-chip when max_graph_len <= gnnops_segment_topk_max_len(), else long; 1: on-chip (GNNOPS_EINVAL if a
+ *       graph cannot fit); 2: long. On-chip: one wave per graph of up to 64 nodes, one workgroup per longer one, the graph
+ *       read once, only its k ids written. Long: one gnnops_sort of int64 keys (graph id << 32 | score image) and a select
+ *       pass, in `workspace` of gnnops_segment_topk_workspace_bytes(N, max_graph_len, route) bytes (host-only; 0 on-chip).
+ *       Both routes give the same perm. G, N below 2^31. No allocation, no synchronisation.
+ * ------------------------------------------------------------------------------------------- */
+int64_t gnnops_segment_topk_max_len(void);
+int gnnops_segment_topk_counts(const int32_t* graph_ptr, int64_t G, float ratio, int64_t k, int32_t* out_ptr, int64_t* d_info,
+                               gnnops_stream_t stream);
+size_t gnnops_segment_topk_workspace_bytes(int64_t N, int64_t max_graph_len, int route);
+int gnnops_segment_topk(const void* score, const int32_t* graph_ptr, const int32_t* out_ptr, int64_t* perm, int64_t G, int64_t N,
+                        int64_t max_graph_len, int dtype, int route, void* workspace, size_t workspace_bytes,
+                        gnnops_stream_t stream);
+
+/* node_map int32 [N] = -1 everywhere, then node_map[perm[i]] = i for i < k: the `mask[perm] = arange(k)` of filter_adj.
+ * perm: distinct ids in [0, N). */
+int gnnops_node_map(const int64_t* perm, int64_t k, int64_t N, int32_t* node_map, gnnops_stream_t stream);
+
+/* Stable compaction of a COO edge list. row, col int64 [E]; node_map (optional) int32 [>= every id + 1], -1 = node gone;
+ * value (optional) [E] rows of value_row_bytes bytes each (an even number). An edge survives if both mapped endpoints are
+ * >= 0 and, with drop_self_loops, they differ. Survivors keep their order; out_row / out_col (int64, room for E) get the
+ * mapped ids, out_value the rows, *d_count (device int64) their number. Count per tile of gnnops_filter_edges_tile()
+ * edges, scan of the tile counts, write: two passes over the edges. workspace = gnnops_filter_edges_workspace_bytes(E)
+ * bytes (host-only). E below 2^32 - tile. */
+int64_t gnnops_filter_edges_tile(void);
+size_t gnnops_filter_edges_workspace_bytes(int64_t E);
+int gnnops_filter_edges(const int64_t* row, const int64_t* col, const void* value, int64_t value_row_bytes,
+                        const int32_t* node_map, int64_t E, int drop_self_loops, int64_t* out_row, int64_t* out_col,
+                        void* out_value, int64_t* d_count, void* workspace, size_t workspace_bytes, gnnops_stream_t stream);
+
+/* GCNConv's edge pass over the destination plan of gnnops_edge_reduce (rowptr int32 [N+1], perm int32 [E] = original edge id
+ * of a sorted position, NULL = identity; col int64 [E] = source row of a sorted position). w fp32 [E] in EDGE order (read
+ * through perm), NULL = every weight 1.
+ *   gnnops_gcn_degree     lw[i] = the weight of the last self loop of i in edge order, fill_value without one;
+ *                         deg[i] = lw[i] + sum of w_e over the non-loop edges into i; dis[i] = deg[i] > 0 ? rsqrt(deg[i]) : 0.
+ *                         dis, lw fp32 [N]. (add_remaining_self_loops + gcn_norm; the edge list is not rewritten.)
+ *   gnnops_gcn_propagate  out[i] = dis[i] * (sum over the non-loop edges (j -> i) of w_e * dis[j] * h[j] + lw[i] * dis[i] * h[i])
+ *                         (+ bias [K]). h [N_src, >= K] (pitch ldh; 0 = one row for all), out [N, >= K] (pitch ldo), bias in
+ *                         `dtype`; fp32 arithmetic, one rounding on store, no atomics, the same bits every run. The operator
+ *                         is symmetric: the backward is this call over the plan of the SOURCE ids with the same dis / lw.
+ * A destination of any in-degree is reduced by its own lane group. N, E below 2^31. One launch each. */
+int gnnops_gcn_degree(const int32_t* rowptr, const int32_t* perm, const int64_t* col, const float* w, int64_t N, int64_t E,
+                      float fill_value, float* dis, float* lw, gnnops_stream_t stream);
+int gnnops_gcn_propagate(const void* h, int64_t ldh, const int32_t* rowptr, const int32_t* perm, const int64_t* col,
+                         const float* w, const float* dis, const float* lw, const void* bias, void* out, int64_t ldo,
+                         int64_t N, int64_t E, int64_t K, int dtype, gnnops_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
