@@ -1224,7 +1224,7 @@ class GraphUNet(torch.nn.Module):
     ``depth`` levels of GCNConv(improved=True) + TopKPooling on the squared adjacency going down, unpooling with a residual (sum, or
     concatenation with ``sum_res=False``) going up. Submodule names ``down_convs``, ``pools``, ``up_convs`` and the forward order are
     PyG's, so a state_dict moves across; torch_geometric is not available to compare against: parity unpinned. `augment_adj` is
-    remove_self_loops, one unit self loop per node, `gnnops.spspmm` of the matrix with itself (its result is coalesced row-major, which
+    remove_self_loops, one unit self loop per node, `gnnops.spspmm(..., method="auto")` of the matrix with itself (coalesced row-major, which
     is what sort_edge_index + spspmm give upstream) and remove_self_loops again; unpooling ``up[perm] = x`` is the package's
     differentiable scatter. Edge weights are float32 at every level, whatever x's dtype. The pooled levels' edge lists are new
     tensors on every forward, so only level 0's plans are cached across calls; inside one call a level's plans serve its down conv,
@@ -1248,7 +1248,7 @@ class GraphUNet(torch.nn.Module):
         self.up_convs.append(GCNConv(up_in, out_channels, improved=True))
 
     @staticmethod
-    def augment_adj(edge_index, edge_weight, num_nodes):
+    def augment_adj(edge_index, edge_weight, num_nodes, method="auto"):
         from . import pool
         from .sparse import spspmm
 
@@ -1256,7 +1256,10 @@ class GraphUNet(torch.nn.Module):
         loops = torch.arange(num_nodes, dtype=edge_index.dtype, device=edge_index.device)
         edge_index = torch.cat([edge_index, torch.stack([loops, loops])], dim=1)
         edge_weight = torch.cat([edge_weight, edge_weight.new_ones(num_nodes)])
-        edge_index, edge_weight = spspmm(edge_index, edge_weight, edge_index, edge_weight, num_nodes, num_nodes, num_nodes)
+        # "auto": row-wise with on-chip accumulators when no entry is stored twice and the graphs fit the window (the pooled
+        # levels always are repeat-free: a coalesced product, filtered), expand - sort - compress otherwise; same bits either way
+        edge_index, edge_weight = spspmm(edge_index, edge_weight, edge_index, edge_weight, num_nodes, num_nodes, num_nodes,
+                                         method=method)
         return pool.remove_self_loops(edge_index, edge_weight)
 
     def forward(self, x, edge_index, batch=None, num_graphs=None, return_perms=False):

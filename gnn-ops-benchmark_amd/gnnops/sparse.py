@@ -297,9 +297,25 @@ def sparse_mm(mat_a, mat_b):
     return spmm(mat_a._indices(), mat_a._values(), m, n, mat_b)
 
 
-def spspmm(indexA, valueA, indexB, valueB, m, k, n, coalesced=False):
+_SPSPMM_METHODS = ("esc", "rowwise", "auto")
+
+
+def spgemm_max_span():
+    """Widest column window of an output row that ``spspmm(..., method="rowwise")`` accumulates on chip."""
+    return int(_lib.load().gnnops_spgemm_max_span())
+
+
+def spspmm(indexA, valueA, indexB, valueB, m, k, n, coalesced=False, method="esc"):
     """torch_sparse.spspmm(indexA, valueA, indexB, valueB, m, k, n): (m x k) @ (k x n), coalesced COO result.
-    Two host round trips size the expansion and the result (the upstream op synchronises for the same reason)."""
+
+    ``method="esc"`` (default): expand - sort - compress; two host round trips size the expansion and the result (the upstream op
+    synchronises for the same reason). ``"rowwise"``: row by row with the output row's accumulator in LDS (csrc/spgemm.hip), no
+    partial product reaches memory, one host read, no limit on the number of products. It takes operand pairs in which no row of B
+    stores a column twice and the columns of every output row lie within :func:`spgemm_max_span` columns (block-diagonal batches of
+    small graphs), and raises NotImplementedError otherwise. ``"auto"``: row-wise when eligible, else ``"esc"`` on the same
+    operands. Wherever both run, the index, the values and the count are the same bit for bit."""
+    if method not in _SPSPMM_METHODS:
+        raise ValueError(f"spspmm: method must be one of {_SPSPMM_METHODS}, got {method!r}")
     _require_gpu(indexA, valueA, indexB, valueB)
     indexA, rowA, colA = _coo_rows_cols(indexA, "spspmm")
     indexB, rowB, colB = _coo_rows_cols(indexB, "spspmm")
@@ -307,10 +323,16 @@ def spspmm(indexA, valueA, indexB, valueB, m, k, n, coalesced=False):
     if valueB.dtype != valueA.dtype:
         raise RuntimeError("spspmm: valueA and valueB must have the same dtype")
     valueA, valueB = valueA.contiguous(), valueB.contiguous()
+    planB = None
+    if method != "esc":
+        out, planB = _spspmm_rowwise(indexA, rowA, colA, valueA, indexB, rowB, colB, valueB, m, k, dt, fall_back=method == "auto")
+        if out is not None:
+            return out
     nnzA = indexA.size(1)
     dev = indexA.device
     L = _lib.load()
-    planB = get_plan(rowB, k)
+    if planB is None:   # "auto" falling back hands over the plan it built
+        planB = get_plan(rowB, k)
     ws_bytes = L.gnnops_spspmm_workspace_bytes(nnzA)
     ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
     total = torch.empty(1, dtype=torch.int64, device=dev)
@@ -328,6 +350,46 @@ def spspmm(indexA, valueA, indexB, valueB, m, k, n, coalesced=False):
                                          ex_index[1].data_ptr(), ex_value.data_ptr(), dt, ws.data_ptr(), _stream()),
                   "spspmm_expand")
     return coalesce(ex_index, ex_value, m, n)
+
+
+def _spspmm_rowwise(indexA, rowA, colA, valueA, indexB, rowB, colB, valueB, m, k, dt, fall_back):
+    """The row-wise route of spspmm: (result, plan of B's rows). The result is None when the operands are not eligible and
+    ``fall_back`` is set; without ``fall_back`` that raises."""
+    nnzA, nnzB = indexA.size(1), indexB.size(1)
+    dev = indexA.device
+    if nnzA >= 1 << 31 or nnzB >= 1 << 31:
+        if fall_back:
+            return None, None
+        raise NotImplementedError("gnnops.spspmm(method='rowwise'): operands must hold fewer than 2^31 entries")
+    L = _lib.load()
+    planA = get_plan(rowA, m, owner=indexA, tag=0)
+    planB = get_plan(rowB, k, owner=indexB, tag=0)   # A @ A: the plan of A again
+    # B is read once per referencing nonzero of A: stream its columns and values in plan (CSR) order instead of chasing perm
+    colB_csr, valB_csr = _csr_arrays(planB, colB, valueB, indexB, 1) if nnzB else (colB, valueB)
+    ws_bytes = L.gnnops_spgemm_workspace_bytes(m, k)
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+    info = torch.empty(4, dtype=torch.int64, device=dev)
+    with _on(dev):
+        check(L.gnnops_spgemm_row_stats(planB.rowptr.data_ptr(), None, colB_csr.data_ptr(), k, nnzB, info.data_ptr(), ws.data_ptr(),
+                                        ws_bytes, _stream()), "spgemm_row_stats")
+        check(L.gnnops_spgemm_symbolic(planA.rowptr.data_ptr(), planA.perm.data_ptr(), colA.data_ptr(), m, nnzA, planB.rowptr.data_ptr(),
+                                       None, colB_csr.data_ptr(), k, nnzB, info.data_ptr(), ws.data_ptr(), ws_bytes, _stream()),
+              "spgemm_symbolic")
+        nnzC, too_wide, b_repeats, max_span = info.tolist()   # the one host read of the route
+        if too_wide or b_repeats:
+            if fall_back:
+                return None, planB
+            why = (f"an output row spans more than {spgemm_max_span()} columns (too wide for the on-chip accumulator)" if too_wide
+                   else "a row of B stores a column more than once (repeated entries)")
+            raise NotImplementedError(f"gnnops.spspmm(method='rowwise'): {why}; use method='esc' or method='auto'")
+        out_index = torch.empty((2, nnzC), dtype=torch.int64, device=dev)
+        out_value = torch.empty(nnzC, dtype=valueA.dtype, device=dev)
+        if nnzC:
+            check(L.gnnops_spgemm_numeric(planA.rowptr.data_ptr(), planA.perm.data_ptr(), colA.data_ptr(), valueA.data_ptr(), m, nnzA,
+                                          planB.rowptr.data_ptr(), None, colB_csr.data_ptr(), valB_csr.data_ptr(), k, nnzC, max_span,
+                                          out_index[0].data_ptr(), out_index[1].data_ptr(), out_value.data_ptr(), dt, ws.data_ptr(),
+                                          ws_bytes, _stream()), "spgemm_numeric")
+    return (out_index, out_value), planB
 
 
 def coalesce(index, value, m, n, op="add"):

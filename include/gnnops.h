@@ -447,6 +447,30 @@ int gnnops_spspmm_expand(const int64_t* rowA, const int64_t* colA, const void* v
                          const void* workspace, gnnops_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Row-wise (Gustavson) spspmm with the output row's accumulator in LDS (csrc/spgemm.hip): the same C = A @ B,
+ * bit for bit, for operand pairs in which no row of B repeats a column and every output row's columns lie in a
+ * window of at most gnnops_spgemm_max_span() columns. A and B are given as the plans (rowptr, perm) of their row
+ * indices plus col / val; perm may be NULL when col / val are in plan (CSR) order already.
+ *   row_stats  clears d_info (device int64[4]) and fills the per-row statistics of B in `workspace`
+ *   symbolic   windows, sizes and row pointer of C in `workspace`; d_info = {nnz(C), some output row is too
+ *              wide, some row of B repeats a column, largest window}: the caller's one host read
+ *   numeric    only when neither flag is raised: out_row / out_col / out_val [nnz(C)], row-major with
+ *              ascending columns; max_span = d_info[3] as read
+ * One `workspace` of gnnops_spgemm_workspace_bytes(m, k) serves the three phases of a call.
+ * ------------------------------------------------------------------------------------------- */
+int64_t gnnops_spgemm_max_span(void);
+size_t gnnops_spgemm_workspace_bytes(int64_t m, int64_t k);
+int gnnops_spgemm_row_stats(const int32_t* rowptrB, const int32_t* permB, const int64_t* colB, int64_t k, int64_t nnzB,
+                            int64_t* d_info, void* workspace, size_t workspace_bytes, gnnops_stream_t stream);
+int gnnops_spgemm_symbolic(const int32_t* rowptrA, const int32_t* permA, const int64_t* colA, int64_t m, int64_t nnzA,
+                           const int32_t* rowptrB, const int32_t* permB, const int64_t* colB, int64_t k, int64_t nnzB,
+                           int64_t* d_info, void* workspace, size_t workspace_bytes, gnnops_stream_t stream);
+int gnnops_spgemm_numeric(const int32_t* rowptrA, const int32_t* permA, const int64_t* colA, const void* valA, int64_t m,
+                          int64_t nnzA, const int32_t* rowptrB, const int32_t* permB, const int64_t* colB, const void* valB,
+                          int64_t k, int64_t nnzC, int64_t max_span, int64_t* out_row, int64_t* out_col, void* out_val,
+                          int dtype, const void* workspace, size_t workspace_bytes, gnnops_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Widening per SURVEY.md 8(f) rank 1: what PyG layers on the reference's OpProfiler path call.
  *
  * gnnops_segment_reduce with perm == NULL treats rowptr as a CSR pointer over src itself

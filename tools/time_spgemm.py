@@ -1,0 +1,137 @@
+"""spspmm(..., method="rowwise" | "auto") (csrc/spgemm.hip: row by row, accumulators in LDS) against method="esc" (expand - sort -
+compress) in the same process.
+
+  (a) GraphUNet.augment_adj alone on the matrices a GraphUNet(64, hidden, 1, depth=3) forward squares on the molecules shape of
+      tools/time_graph_unet.py (64 graphs x 1000 nodes, 10 in-edges per node): the level-0 adjacency (it holds repeated edges, so
+      "auto" falls back there; a de-duplicated copy shows the row-wise route on that shape), the filtered level-1 product and the
+      filtered level-2 product; and on one graph of N = 100 000 nodes, where "auto" must fall back (rows too wide) at the cost of
+      the statistics + symbolic passes and one host read
+  (b) the reference's own spspmm point: L = 1414 at sparsity 0.995, both operands random
+
+The methods alternate inside one process, every callable is warmed first, a sample is enough calls between two device events to last
+tens of milliseconds; the table gives the median and the spread (tools/time_graph_unet.py's protocol and its `measure`). Results
+are compared bit for bit before they are timed. No pass bar: the record is the deliverable.
+
+  python tools/time_spgemm.py [--samples S] [--out profiles/spgemm_rowwise.txt]
+"""
+import argparse
+import os
+import statistics
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path[:0] = [os.path.join(ROOT, "gnn-ops-benchmark_amd"), os.path.join(ROOT, "tools")]
+import torch  # noqa: E402
+
+import gnnops  # noqa: E402
+from gnnops import conv  # noqa: E402
+from time_graph_unet import measure  # noqa: E402
+
+
+def same_bits(a, b):
+    return a[0].shape == b[0].shape and bool(torch.equal(a[0], b[0])) and bool(torch.equal(a[1].view(torch.int32), b[1].view(torch.int32)))
+
+
+def table(lines, res, names):
+    med = {}
+    for name in names:
+        v, reps = res[name]
+        med[name] = statistics.median(v)
+        lines.append(f"  {name:8s} {med[name]:9.3f} ms  [{min(v):.3f} .. {max(v):.3f}]  ({reps} calls per sample)")
+    base = med[names[0]]
+    lines.append("  " + ", ".join(f"{names[0]} / {n} = {base / med[n]:.2f}" for n in names[1:]))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--samples", type=int, default=7)
+    ap.add_argument("--window-ms", type=float, default=60.0)
+    ap.add_argument("--graphs", type=int, default=64)
+    ap.add_argument("--per", type=int, default=1000)
+    ap.add_argument("--deg", type=int, default=10)
+    ap.add_argument("--nodes", type=int, default=100_000)
+    ap.add_argument("--in-deg", type=int, default=5)
+    ap.add_argument("--hidden", type=int, default=128)
+    ap.add_argument("--out", default=None)
+    args = ap.parse_args()
+    if not torch.cuda.is_available():
+        raise SystemExit("time_spgemm.py needs a GPU: nothing is measured without one")
+    gnnops.load_library()
+    g = torch.Generator(device="cuda").manual_seed(5)
+    lines = [f"spspmm on {torch.cuda.get_device_name(0)}: method=\"rowwise\" / \"auto\" (on-chip accumulators, window of up to "
+             f"{gnnops.spgemm_max_span()} columns) against method=\"esc\" (expand - sort - compress)",
+             f"ms per call: median [min .. max] of {args.samples} samples, each of enough calls for ~{args.window_ms:.0f} ms; the methods "
+             "alternate in one process; results compared bit for bit first", ""]
+
+    def flush():
+        text = "\n".join(lines)
+        if args.out:
+            with open(args.out, "w") as f:
+                f.write(text + "\n")
+        return text
+
+    # ---- (a) the matrices GraphUNet squares ----
+    n1 = args.graphs * args.per
+    dst1 = torch.randint(0, n1, (n1 * args.deg,), generator=g, device="cuda")
+    src1 = torch.randint(0, args.per, (n1 * args.deg,), generator=g, device="cuda") + dst1 // args.per * args.per
+    ei = torch.stack([src1, dst1])
+    batch = torch.arange(args.graphs, device="cuda").repeat_interleave(args.per)
+    torch.manual_seed(0)
+    model = conv.GraphUNet(64, args.hidden, 1, 3).cuda()
+    x = torch.rand(n1, 64, generator=g, device="cuda") - 0.5
+    seen, real = [], conv.GraphUNet.augment_adj
+
+    def recorder(edge_index, edge_weight, num_nodes, *a, **kw):
+        seen.append((edge_index, edge_weight, num_nodes))
+        return real(edge_index, edge_weight, num_nodes, *a, **kw)
+
+    conv.GraphUNet.augment_adj = staticmethod(recorder)
+    try:
+        with torch.no_grad():
+            model(x, ei, batch, args.graphs)
+    finally:
+        conv.GraphUNet.augment_adj = staticmethod(real)
+    del model, x
+    cases = [(f"level {lvl}: {args.graphs} graphs, {n} nodes", e, w, n) for lvl, (e, w, n) in enumerate(seen)]
+    e0, w0, n0 = seen[0]
+    d0 = torch.unique(e0[0] * n0 + e0[1])
+    cases.insert(1, ("level 0 with repeated edges removed", torch.stack([d0 // n0, d0 % n0]), torch.ones(d0.numel(), device="cuda"), n0))
+    big = torch.stack([torch.randint(0, args.nodes, (args.nodes * args.in_deg,), generator=g, device="cuda"),
+                       torch.arange(args.nodes, device="cuda").repeat_interleave(args.in_deg)])
+    cases.append((f"one graph: N = {args.nodes}, {args.in_deg} random in-edges per node", big, torch.ones(big.size(1), device="cuda"), args.nodes))
+    lines.append("(a) GraphUNet.augment_adj alone (remove_self_loops, unit loops, the product, remove_self_loops)")
+    for label, e, w, n in cases:
+        out = {mth: real(e, w, n, method=mth) for mth in ("esc", "auto")}
+        try:
+            real(e, w, n, method="rowwise")
+            route = "row-wise"
+        except NotImplementedError as exc:
+            route = "falls back to esc: " + str(exc).split(": ", 1)[1].split(";")[0]
+        lines.append(f"{label}: nnz(A) = {e.size(1)}, nnz((A+I)^2) - diagonal = {out['esc'][0].size(1)}; \"auto\" {route}; "
+                     f"same bits: {same_bits(out['esc'], out['auto'])}")
+        del out
+        res = measure({mth: (lambda mth=mth: real(e, w, n, method=mth)) for mth in ("esc", "auto")}, args.samples, args.window_ms)
+        table(lines, res, ("esc", "auto"))
+        lines.append("")
+        flush()
+        torch.cuda.empty_cache()
+
+    # ---- (b) the reference's sweep point ----
+    L, sparsity = 1414, 0.995
+    ops = []
+    for _ in range(2):
+        mask = torch.rand(L, L, generator=g, device="cuda") >= sparsity
+        idx = mask.nonzero().t().contiguous()
+        ops += [idx, torch.rand(idx.size(1), generator=g, device="cuda")]
+    run = lambda mth: gnnops.spspmm(ops[0], ops[1], ops[2], ops[3], L, L, L, method=mth)   # noqa: E731
+    out = {mth: run(mth) for mth in ("esc", "rowwise")}
+    lines.append(f"(b) the reference's point: L = {L}, sparsity {sparsity}: nnz(A) = {ops[0].size(1)}, nnz(B) = {ops[2].size(1)}, "
+                 f"nnz(C) = {out['esc'][0].size(1)}; same bits: {same_bits(out['esc'], out['rowwise'])}")
+    res = measure({mth: (lambda mth=mth: run(mth)) for mth in ("esc", "rowwise")}, args.samples, args.window_ms)
+    table(lines, res, ("esc", "rowwise"))
+    lines.append("")
+    print(flush())
+
+
+if __name__ == "__main__":
+    main()
