@@ -23,7 +23,7 @@ from .ops import (
 # the differentiable front ends (they ARE the raw ops when nothing requires grad; gnnops.ops.* are the raw forms)
 from .autograd import (addmm, gather, index_select, matmul, scatter, scatter_add, scatter_max, scatter_mean, scatter_min,
                        scatter_mul, scatter_sum)
-from .sparse import (SpmmTiles, coalesce, coalesce_sparse_tensor, sddmm, sort, sparse_mm, spgemm_max_span, spmm, spmm_csr, spmm_t, spmm_tiles,
+from .sparse import (SpmmTiles, coalesce, coalesce_sparse_tensor, sddmm, sort, sparse_mm, spgemm_hash_max_row, spgemm_max_span, spmm, spmm_csr, spmm_t, spmm_tiles,
                      spspmm, transpose, transpose_contiguous)
 from .segment import (expand_rowptr, gather_coo, gather_csr, rowptr_from_sorted, scatter_log_softmax, scatter_logsumexp, scatter_softmax,
                       scatter_std, segment_coo, segment_csr)
@@ -38,7 +38,7 @@ __all__ = [
     "index_add_", "index_max", "index_select", "index_select_sum", "scatter", "scatter_add", "scatter_add_",
     "scatter_max", "scatter_mean", "scatter_min", "scatter_mul", "scatter_reduce_mul_", "scatter_sum",
     "set_plan_cache", "install", "uninstall", "installed", "coalesce", "coalesce_sparse_tensor", "sort", "sparse_mm",
-    "spmm", "spmm_csr", "spmm_tiles", "SpmmTiles", "spmm_t", "sddmm", "expand_rowptr", "spspmm", "spgemm_max_span", "transpose", "transpose_contiguous", "addmm", "matmul", "index_add_select_sum", "segment_csr", "segment_coo", "gather_csr", "gather_coo",
+    "spmm", "spmm_csr", "spmm_tiles", "SpmmTiles", "spmm_t", "sddmm", "expand_rowptr", "spspmm", "spgemm_max_span", "spgemm_hash_max_row", "transpose", "transpose_contiguous", "addmm", "matmul", "index_add_select_sum", "segment_csr", "segment_coo", "gather_csr", "gather_coo",
     "rowptr_from_sorted", "scatter_softmax", "scatter_log_softmax", "scatter_logsumexp", "scatter_std", "autograd", "layers", "GATv2Conv", "edge_attention", "GATConv", "GATEConv", "AttentiveFP", "edge_attention_v1",
     "GCNConv", "TopKPooling", "GraphUNet", "gcn_propagate", "pool", "topk", "filter_adj", "remove_self_loops",
 ]

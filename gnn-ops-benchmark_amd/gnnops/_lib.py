@@ -84,6 +84,10 @@ SIGNATURES = {
     "gnnops_spgemm_row_stats": (_ci, [_vp, _vp, _vp, _i64, _i64, _vp, _vp, _sz, _vp]),
     "gnnops_spgemm_symbolic": (_ci, [_vp, _vp, _vp, _i64, _i64, _vp, _vp, _vp, _i64, _i64, _vp, _vp, _sz, _vp]),
     "gnnops_spgemm_numeric": (_ci, [_vp, _vp, _vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _vp, _vp, _vp, _ci, _vp, _sz, _vp]),
+    "gnnops_spgemm_hash_max_row": (_i64, []),
+    "gnnops_spgemm_hash_row_stats": (_ci, [_vp, _vp, _vp, _i64, _i64, _vp, _vp, _sz, _vp]),
+    "gnnops_spgemm_hash_symbolic": (_ci, [_vp, _vp, _vp, _i64, _i64, _vp, _vp, _vp, _i64, _i64, _vp, _vp, _sz, _vp]),
+    "gnnops_spgemm_hash_numeric": (_ci, [_vp, _vp, _vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _vp, _vp, _vp, _ci, _vp, _sz, _vp]),
     "gnnops_rowptr_workspace_bytes": (_sz, [_i64]),
     "gnnops_rowptr_from_sorted": (_ci, [_vp, _i64, _i64, _vp, _vp, _sz, _vp]),
     "gnnops_owner_counts": (_ci, [_vp, _i64, _i64, _ci, _vp, _vp]),

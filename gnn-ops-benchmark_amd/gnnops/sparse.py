@@ -297,12 +297,17 @@ def sparse_mm(mat_a, mat_b):
     return spmm(mat_a._indices(), mat_a._values(), m, n, mat_b)
 
 
-_SPSPMM_METHODS = ("esc", "rowwise", "auto")
+_SPSPMM_METHODS = ("esc", "rowwise", "rowhash", "auto")
 
 
 def spgemm_max_span():
     """Widest column window of an output row that ``spspmm(..., method="rowwise")`` accumulates on chip."""
     return int(_lib.load().gnnops_spgemm_max_span())
+
+
+def spgemm_hash_max_row():
+    """Most distinct columns of an output row that ``spspmm(..., method="rowhash")`` accumulates on chip."""
+    return int(_lib.load().gnnops_spgemm_hash_max_row())
 
 
 def spspmm(indexA, valueA, indexB, valueB, m, k, n, coalesced=False, method="esc"):
@@ -312,8 +317,12 @@ def spspmm(indexA, valueA, indexB, valueB, m, k, n, coalesced=False, method="esc
     synchronises for the same reason). ``"rowwise"``: row by row with the output row's accumulator in LDS (csrc/spgemm.hip), no
     partial product reaches memory, one host read, no limit on the number of products. It takes operand pairs in which no row of B
     stores a column twice and the columns of every output row lie within :func:`spgemm_max_span` columns (block-diagonal batches of
-    small graphs), and raises NotImplementedError otherwise. ``"auto"``: row-wise when eligible, else ``"esc"`` on the same
-    operands. Wherever both run, the index, the values and the count are the same bit for bit."""
+    small graphs), and raises NotImplementedError otherwise. ``"rowhash"``: the same scheme with the row's accumulators in an LDS
+    hash table keyed by column, for rows whose columns lie anywhere (within 2^32 - 2 columns of each other): it takes operand pairs
+    in which no row of B stores a column twice and every output row has at most :func:`spgemm_hash_max_row` distinct columns, and
+    raises NotImplementedError otherwise. ``"auto"``: the window when eligible, else ``"esc"`` on the same operands (it does not try
+    the hash table: measured behind "esc" on the largest point of the reference's sweep, profiles/spgemm_rowhash.txt). Wherever
+    several run, the index, the values and the count are the same bit for bit."""
     if method not in _SPSPMM_METHODS:
         raise ValueError(f"spspmm: method must be one of {_SPSPMM_METHODS}, got {method!r}")
     _require_gpu(indexA, valueA, indexB, valueB)
@@ -325,7 +334,8 @@ def spspmm(indexA, valueA, indexB, valueB, m, k, n, coalesced=False, method="esc
     valueA, valueB = valueA.contiguous(), valueB.contiguous()
     planB = None
     if method != "esc":
-        out, planB = _spspmm_rowwise(indexA, rowA, colA, valueA, indexB, rowB, colB, valueB, m, k, dt, fall_back=method == "auto")
+        out, planB = _spspmm_rowwise(indexA, rowA, colA, valueA, indexB, rowB, colB, valueB, m, k, dt, fall_back=method == "auto",
+                                     hashed=method == "rowhash")
         if out is not None:
             return out
     nnzA = indexA.size(1)
@@ -352,16 +362,19 @@ def spspmm(indexA, valueA, indexB, valueB, m, k, n, coalesced=False, method="esc
     return coalesce(ex_index, ex_value, m, n)
 
 
-def _spspmm_rowwise(indexA, rowA, colA, valueA, indexB, rowB, colB, valueB, m, k, dt, fall_back):
-    """The row-wise route of spspmm: (result, plan of B's rows). The result is None when the operands are not eligible and
-    ``fall_back`` is set; without ``fall_back`` that raises."""
+def _spspmm_rowwise(indexA, rowA, colA, valueA, indexB, rowB, colB, valueB, m, k, dt, fall_back, hashed=False):
+    """The row-wise routes of spspmm, ``hashed`` choosing the LDS hash table over the column window: (result, plan of B's rows).
+    The result is None when the operands are not eligible and ``fall_back`` is set; without ``fall_back`` that raises."""
     nnzA, nnzB = indexA.size(1), indexB.size(1)
     dev = indexA.device
+    name = "rowhash" if hashed else "rowwise"
     if nnzA >= 1 << 31 or nnzB >= 1 << 31:
         if fall_back:
             return None, None
-        raise NotImplementedError("gnnops.spspmm(method='rowwise'): operands must hold fewer than 2^31 entries")
+        raise NotImplementedError(f"gnnops.spspmm(method='{name}'): operands must hold fewer than 2^31 entries")
     L = _lib.load()
+    row_stats, symbolic, numeric = ((L.gnnops_spgemm_hash_row_stats, L.gnnops_spgemm_hash_symbolic, L.gnnops_spgemm_hash_numeric) if hashed
+                                    else (L.gnnops_spgemm_row_stats, L.gnnops_spgemm_symbolic, L.gnnops_spgemm_numeric))
     planA = get_plan(rowA, m, owner=indexA, tag=0)
     planB = get_plan(rowB, k, owner=indexB, tag=0)   # A @ A: the plan of A again
     # B is read once per referencing nonzero of A: stream its columns and values in plan (CSR) order instead of chasing perm
@@ -370,25 +383,31 @@ def _spspmm_rowwise(indexA, rowA, colA, valueA, indexB, rowB, colB, valueB, m, k
     ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
     info = torch.empty(4, dtype=torch.int64, device=dev)
     with _on(dev):
-        check(L.gnnops_spgemm_row_stats(planB.rowptr.data_ptr(), None, colB_csr.data_ptr(), k, nnzB, info.data_ptr(), ws.data_ptr(),
-                                        ws_bytes, _stream()), "spgemm_row_stats")
-        check(L.gnnops_spgemm_symbolic(planA.rowptr.data_ptr(), planA.perm.data_ptr(), colA.data_ptr(), m, nnzA, planB.rowptr.data_ptr(),
-                                       None, colB_csr.data_ptr(), k, nnzB, info.data_ptr(), ws.data_ptr(), ws_bytes, _stream()),
-              "spgemm_symbolic")
-        nnzC, too_wide, b_repeats, max_span = info.tolist()   # the one host read of the route
-        if too_wide or b_repeats:
+        check(row_stats(planB.rowptr.data_ptr(), None, colB_csr.data_ptr(), k, nnzB, info.data_ptr(), ws.data_ptr(), ws_bytes, _stream()),
+              f"spgemm_{name}_row_stats")
+        check(symbolic(planA.rowptr.data_ptr(), planA.perm.data_ptr(), colA.data_ptr(), m, nnzA, planB.rowptr.data_ptr(), None,
+                       colB_csr.data_ptr(), k, nnzB, info.data_ptr(), ws.data_ptr(), ws_bytes, _stream()), f"spgemm_{name}_symbolic")
+        nnzC, refused, b_repeats, largest = info.tolist()   # the one host read of the route; largest: span (window) or row count (hash)
+        if refused or b_repeats:
             if fall_back:
                 return None, planB
-            why = (f"an output row spans more than {spgemm_max_span()} columns (too wide for the on-chip accumulator)" if too_wide
-                   else "a row of B stores a column more than once (repeated entries)")
-            raise NotImplementedError(f"gnnops.spspmm(method='rowwise'): {why}; use method='esc' or method='auto'")
+            if b_repeats:
+                why = "a row of B stores a column more than once (repeated entries)"
+            elif not hashed:
+                why = f"an output row spans more than {spgemm_max_span()} columns (too wide for the on-chip accumulator)"
+            elif refused & 1:
+                why = f"an output row has more than {spgemm_hash_max_row()} distinct columns (too many for the on-chip table)"
+            else:
+                why = "an output row spans 2^32 - 1 columns or more (too wide for a 32-bit key)"
+            others = "method='esc' or method='auto'" if hashed else "method='rowhash', method='esc' or method='auto'"
+            raise NotImplementedError(f"gnnops.spspmm(method='{name}'): {why}; use {others}")
         out_index = torch.empty((2, nnzC), dtype=torch.int64, device=dev)
         out_value = torch.empty(nnzC, dtype=valueA.dtype, device=dev)
         if nnzC:
-            check(L.gnnops_spgemm_numeric(planA.rowptr.data_ptr(), planA.perm.data_ptr(), colA.data_ptr(), valueA.data_ptr(), m, nnzA,
-                                          planB.rowptr.data_ptr(), None, colB_csr.data_ptr(), valB_csr.data_ptr(), k, nnzC, max_span,
-                                          out_index[0].data_ptr(), out_index[1].data_ptr(), out_value.data_ptr(), dt, ws.data_ptr(),
-                                          ws_bytes, _stream()), "spgemm_numeric")
+            check(numeric(planA.rowptr.data_ptr(), planA.perm.data_ptr(), colA.data_ptr(), valueA.data_ptr(), m, nnzA,
+                          planB.rowptr.data_ptr(), None, colB_csr.data_ptr(), valB_csr.data_ptr(), k, nnzC, largest,
+                          out_index[0].data_ptr(), out_index[1].data_ptr(), out_value.data_ptr(), dt, ws.data_ptr(), ws_bytes, _stream()),
+                  f"spgemm_{name}_numeric")
     return (out_index, out_value), planB
 
 

@@ -470,6 +470,26 @@ int gnnops_spgemm_numeric(const int32_t* rowptrA, const int32_t* permA, const in
                           int64_t k, int64_t nnzC, int64_t max_span, int64_t* out_row, int64_t* out_col, void* out_val,
                           int dtype, const void* workspace, size_t workspace_bytes, gnnops_stream_t stream);
 
+/* The hashed route of the same product (spspmm(..., method="rowhash")): the output row's accumulator is an
+ * open-addressing hash table in LDS keyed by column - (smallest column of the row) as 32 bits, so the columns of a
+ * row may lie anywhere within 2^32 - 1 columns; an output row may hold at most gnnops_spgemm_hash_max_row() distinct
+ * columns. Same phases, arguments, workspace and bits as gnnops_spgemm_*, except
+ *   row_stats  rows of B of up to hash_max_row entries are checked for repeated columns and marked, the row, not the
+ *              call (longer rows are not checked: the symbolic pass refuses every output row that references one)
+ *   symbolic   d_info = {nnz(C), 1 * some output row has too many distinct columns + 2 * some output row spans too
+ *              many columns for a key, some referenced row of B repeats a column, largest row count}
+ *   numeric    only when d_info[1] and d_info[2] are zero; max_row = d_info[3] as read (it picks the table class) */
+int64_t gnnops_spgemm_hash_max_row(void);
+int gnnops_spgemm_hash_row_stats(const int32_t* rowptrB, const int32_t* permB, const int64_t* colB, int64_t k, int64_t nnzB,
+                                 int64_t* d_info, void* workspace, size_t workspace_bytes, gnnops_stream_t stream);
+int gnnops_spgemm_hash_symbolic(const int32_t* rowptrA, const int32_t* permA, const int64_t* colA, int64_t m, int64_t nnzA,
+                                const int32_t* rowptrB, const int32_t* permB, const int64_t* colB, int64_t k, int64_t nnzB,
+                                int64_t* d_info, void* workspace, size_t workspace_bytes, gnnops_stream_t stream);
+int gnnops_spgemm_hash_numeric(const int32_t* rowptrA, const int32_t* permA, const int64_t* colA, const void* valA, int64_t m,
+                               int64_t nnzA, const int32_t* rowptrB, const int32_t* permB, const int64_t* colB, const void* valB,
+                               int64_t k, int64_t nnzC, int64_t max_row, int64_t* out_row, int64_t* out_col, void* out_val,
+                               int dtype, const void* workspace, size_t workspace_bytes, gnnops_stream_t stream);
+
 /* ---------------------------------------------------------------------------------------------
  * Widening per SURVEY.md 8(f) rank 1: what PyG layers on the reference's OpProfiler path call.
  *

@@ -13,6 +13,13 @@ tens of milliseconds; the table gives the median and the spread (tools/time_grap
 are compared bit for bit before they are timed. No pass bar: the record is the deliverable.
 
   python tools/time_spgemm.py [--samples S] [--out profiles/spgemm_rowwise.txt]
+
+--route rowhash records method="rowhash" (the row's accumulators in an LDS hash table) under the same protocol instead:
+  (c) esc against rowhash on the reference's sweep points L = 1414, 4472 and 7071 (fp32, sparsity 0.995)
+  (d) esc against auto against rowhash on the one-graph augment_adj case, whose rows are too wide for the window
+  (e) rowwise against rowhash on the level-1 and level-2 batches of (a): what the hash and the sort cost where the window works too
+
+  python tools/time_spgemm.py --route rowhash [--samples S] [--out profiles/spgemm_rowhash.txt]
 """
 import argparse
 import os
@@ -53,6 +60,7 @@ def main():
     ap.add_argument("--in-deg", type=int, default=5)
     ap.add_argument("--hidden", type=int, default=128)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--route", choices=("rowwise", "rowhash"), default="rowwise")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("time_spgemm.py needs a GPU: nothing is measured without one")
@@ -99,6 +107,15 @@ def main():
     big = torch.stack([torch.randint(0, args.nodes, (args.nodes * args.in_deg,), generator=g, device="cuda"),
                        torch.arange(args.nodes, device="cuda").repeat_interleave(args.in_deg)])
     cases.append((f"one graph: N = {args.nodes}, {args.in_deg} random in-edges per node", big, torch.ones(big.size(1), device="cuda"), args.nodes))
+    if args.route == "rowhash":
+        del lines[:]
+        lines += [f"spspmm on {torch.cuda.get_device_name(0)}: method=\"rowhash\" (on-chip hash table, up to {gnnops.spgemm_hash_max_row()} distinct "
+                  "columns per output row) against method=\"esc\" (expand - sort - compress), \"rowwise\" (on-chip column window) and \"auto\"",
+                  f"ms per call: median [min .. max] of {args.samples} samples, each of enough calls for ~{args.window_ms:.0f} ms; the methods "
+                  "alternate in one process; results compared bit for bit first", ""]
+        hashed_sections(args, lines, flush, g, real, cases)
+        print(flush())
+        return
     lines.append("(a) GraphUNet.augment_adj alone (remove_self_loops, unit loops, the product, remove_self_loops)")
     for label, e, w, n in cases:
         out = {mth: real(e, w, n, method=mth) for mth in ("esc", "auto")}
@@ -131,6 +148,49 @@ def main():
     table(lines, res, ("esc", "rowwise"))
     lines.append("")
     print(flush())
+
+
+def hashed_sections(args, lines, flush, g, augment_adj, cases):
+    lines.append("(c) the reference's sweep (op_bm_scripts/benchmark_sparse_spspmm.py): square random operands, sparsity 0.995, fp32")
+    for L in (1414, 4472, 7071):
+        ops = []
+        for _ in range(2):
+            idx = (torch.rand(L, L, generator=g, device="cuda") >= 0.995).nonzero().t().contiguous()
+            ops += [idx, torch.rand(idx.size(1), generator=g, device="cuda")]
+        run = lambda mth: gnnops.spspmm(ops[0], ops[1], ops[2], ops[3], L, L, L, method=mth)   # noqa: E731
+        out = {mth: run(mth) for mth in ("esc", "rowhash")}
+        most = int(torch.bincount(out["esc"][0][0], minlength=L).max())
+        lines.append(f"L = {L}: nnz(A) = {ops[0].size(1)}, nnz(B) = {ops[2].size(1)}, nnz(C) = {out['esc'][0].size(1)}, largest output row "
+                     f"{most}; same bits: {same_bits(out['esc'], out['rowhash'])}")
+        del out
+        table(lines, measure({mth: (lambda mth=mth: run(mth)) for mth in ("esc", "rowhash")}, args.samples, args.window_ms), ("esc", "rowhash"))
+        lines.append("")
+        flush()
+        del ops
+        torch.cuda.empty_cache()
+    label, e, w, n = cases[-1]
+    d = torch.unique(e[0] * n + e[1])   # random in-edges repeat now and then: a row of B that repeats a column is for "esc" alone
+    e, w = torch.stack([d // n, d % n]), torch.ones(d.numel(), device="cuda")
+    lines.append("(d) GraphUNet.augment_adj alone on one large graph, repeated edges removed: too wide for the window")
+    out = {mth: augment_adj(e, w, n, method=mth) for mth in ("esc", "auto", "rowhash")}
+    lines.append(f"{label}: nnz(A) = {e.size(1)}, nnz((A+I)^2) - diagonal = {out['esc'][0].size(1)}; same bits: "
+                 f"{same_bits(out['esc'], out['auto']) and same_bits(out['esc'], out['rowhash'])}")
+    del out
+    table(lines, measure({mth: (lambda mth=mth: augment_adj(e, w, n, method=mth)) for mth in ("esc", "auto", "rowhash")}, args.samples,
+                         args.window_ms), ("esc", "auto", "rowhash"))
+    lines.append("")
+    flush()
+    lines.append("(e) GraphUNet.augment_adj alone on the pooled batches, where the window works too")
+    for label, e, w, n in cases[2:4]:
+        out = {mth: augment_adj(e, w, n, method=mth) for mth in ("rowwise", "rowhash")}
+        lines.append(f"{label}: nnz(A) = {e.size(1)}, nnz((A+I)^2) - diagonal = {out['rowwise'][0].size(1)}; same bits: "
+                     f"{same_bits(out['rowwise'], out['rowhash'])}")
+        del out
+        table(lines, measure({mth: (lambda mth=mth: augment_adj(e, w, n, method=mth)) for mth in ("rowwise", "rowhash")}, args.samples,
+                             args.window_ms), ("rowwise", "rowhash"))
+        lines.append("")
+        flush()
+        torch.cuda.empty_cache()
 
 
 if __name__ == "__main__":
