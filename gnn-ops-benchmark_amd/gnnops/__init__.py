@@ -28,8 +28,9 @@ from .sparse import (SpmmTiles, coalesce, coalesce_sparse_tensor, sddmm, sort, s
 from .segment import (expand_rowptr, gather_coo, gather_csr, rowptr_from_sorted, scatter_log_softmax, scatter_logsumexp, scatter_softmax,
                       scatter_std, segment_coo, segment_csr)
 from . import autograd, layers
-from .conv import AttentiveFP, GATConv, GATEConv, GATv2Conv, GCNConv, GraphUNet, TopKPooling, edge_attention, edge_attention_v1, gcn_propagate
-from .pool import filter_adj, remove_self_loops, topk
+from .conv import (AttentiveFP, GATConv, GATEConv, GATv2, GATv2Conv, GCNConv, GraphUNet, TopKPooling, edge_attention, edge_attention_v1, gcn_propagate,
+                   head_act_norm)
+from .pool import filter_adj, global_add_pool, global_max_pool, global_mean_pool, remove_self_loops, topk
 from . import pool
 from .aten import install, uninstall, installed
 
@@ -41,4 +42,5 @@ __all__ = [
     "spmm", "spmm_csr", "spmm_tiles", "SpmmTiles", "spmm_t", "sddmm", "expand_rowptr", "spspmm", "spgemm_max_span", "spgemm_hash_max_row", "transpose", "transpose_contiguous", "addmm", "matmul", "index_add_select_sum", "segment_csr", "segment_coo", "gather_csr", "gather_coo",
     "rowptr_from_sorted", "scatter_softmax", "scatter_log_softmax", "scatter_logsumexp", "scatter_std", "autograd", "layers", "GATv2Conv", "edge_attention", "GATConv", "GATEConv", "AttentiveFP", "edge_attention_v1",
     "GCNConv", "TopKPooling", "GraphUNet", "gcn_propagate", "pool", "topk", "filter_adj", "remove_self_loops",
+    "GATv2", "head_act_norm", "global_add_pool", "global_mean_pool", "global_max_pool",
 ]

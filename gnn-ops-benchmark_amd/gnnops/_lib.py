@@ -142,6 +142,9 @@ SIGNATURES = {
     "gnnops_filter_edges": (_ci, [_vp, _vp, _vp, _i64, _vp, _i64, _ci, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "gnnops_gcn_degree": (_ci, [_vp, _vp, _vp, _vp, _i64, _i64, ctypes.c_float, _vp, _vp, _vp]),
     "gnnops_gcn_propagate": (_ci, [_vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _ci, _vp]),
+    "gnnops_head_act_norm": (_ci, [_vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _ci, ctypes.c_float, _ci, _vp]),
+    "gnnops_head_act_norm_backward_workspace_bytes": (_sz, [_i64, _i64, _i64]),
+    "gnnops_head_act_norm_backward": (_ci, [_vp, _i64, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _ci, _ci, _vp, _sz, _vp]),
 }
 
 _lib = None

@@ -24,6 +24,9 @@ attention pass, `edge_attention` (csrc/attention.hip: online softmax per destina
 `GATConv` (the original GAT), `GATEConv` and the `AttentiveFP` model on them (the reference's AttentiveFPREG, ptg_models.py:91-120) run
 on the second member of that family, `edge_attention_v1`: per-edge rows, a leaky ReLU on the row, attention dropout after the softmax.
 
+The GATv2 MODEL (the reference's GATv2REG) is `GATv2`: per layer the product, the attention pass and ONE `head_act_norm` pass
+(csrc/norm.hip: mean over heads + bias + ReLU + feature-dropout mask + LayerNorm, trainable), then gnnops.pool.global_mean_pool.
+
 GraphUNet's layers (the reference's GraphUNetREG): `GCNConv` is one product and `gcn_propagate` (csrc/gcn.hip: symmetric normalisation
 with edge weights, trainable), `TopKPooling` selects with `gnnops.pool.topk` / `filter_adj` (csrc/pool.hip), `GraphUNet` is the model.
 """
@@ -745,7 +748,8 @@ class GATv2Conv(_Layer):
         self._looped = (weakref.ref(edge_index), edge_index._version, n, looped) if cacheable else None
         return looped
 
-    def forward(self, x, edge_index, size=None):
+    def _attend(self, x, edge_index, size=None):
+        """The attention output [n_dst, H * C] before the head mean / bias of `forward` (`GATv2` fuses those into `head_act_norm`)."""
         if self.dropout > 0.0 and self.training:
             raise NotImplementedError("gnnops.conv.GATv2Conv: attention dropout is not implemented in the fused pass; construct the "
                                       "layer with dropout=0.0 (the reference's default) or call it in eval mode")
@@ -768,10 +772,156 @@ class GATv2Conv(_Layer):
                 q, p = qp[:, :HC], qp[:, HC:]
             if self.add_self_loops:
                 edge_index = self._with_self_loops(edge_index, n_dst)
-        out = edge_attention(q, p, self.att, edge_index, n_dst, H, self.negative_slope)
+        return edge_attention(q, p, self.att, edge_index, n_dst, H, self.negative_slope)
+
+    def forward(self, x, edge_index, size=None):
+        out = self._attend(x, edge_index, size)
         if not self.concat:
-            out = out.view(n_dst, H, C).mean(dim=1)
+            out = out.view(out.size(0), self.heads, self.out_channels).mean(dim=1)
         return out if self.bias is None else out + self.bias
+
+
+# ---- the epilogue between two attention passes (csrc/norm.hip) and the GATv2 model ------------------------------------------------
+def _norm_operands(a, heads, bias, scale, norm_weight, norm_bias):
+    op = "head_act_norm"
+    _require_gpu(a, bias, scale, norm_weight, norm_bias)
+    if a.dim() != 2 or heads < 1 or a.size(1) % heads:
+        raise RuntimeError(f"{op}: a must be 2-D with heads = {heads} dividing its columns")
+    HC = a.size(1)
+    C = HC // heads
+    if HC > 8192:
+        raise RuntimeError(f"{op}: heads * channels = {HC} is past the 8192 the row pass holds")
+    if norm_bias is not None and norm_weight is None:
+        raise RuntimeError(f"{op}: norm_bias without norm_weight")
+    if HC > 1 and a.stride(1) != 1:
+        a = a.contiguous()
+    a, lda = _rows(a, "a", 1, HC, op=op) if HC else (a, 0)
+    vecs = []
+    for t, what in ((bias, "bias"), (norm_weight, "norm_weight"), (norm_bias, "norm_bias")):
+        if t is not None and (t.numel() != C or t.dtype != a.dtype):
+            raise RuntimeError(f"{op}: {what} must hold {C} values of a's dtype")
+        vecs.append(None if t is None else t.contiguous().view(-1))
+    if scale is not None:
+        if tuple(scale.shape) != (a.size(0), C) or scale.dtype != a.dtype:
+            raise RuntimeError(f"{op}: scale must be [{a.size(0)}, {C}] of a's dtype")
+        scale = scale.contiguous()
+    return a, lda, vecs[0], scale, vecs[1], vecs[2], HC, C
+
+
+def _ptr(t):
+    return None if t is None else t.data_ptr()
+
+
+def _norm_forward(a, heads, bias, relu, scale, norm_weight, norm_bias, eps, want_stats):
+    """(out [N, C], stats fp32 [N, 2] or None) of one launch of gnnops_head_act_norm: the raw call, which like every raw entry
+    point refuses operands that require grad (inside `_HeadActNorm` grad mode is off)."""
+    ops._refuse_grad("conv.head_act_norm", a, bias, scale, norm_weight, norm_bias)
+    a, lda, bias, scale, gamma, beta, HC, C = _norm_operands(a, heads, bias, scale, norm_weight, norm_bias)
+    N = a.size(0)
+    out = torch.empty((N, C), dtype=a.dtype, device=a.device)
+    stats = torch.empty((N, 2), dtype=torch.float32, device=a.device) if want_stats and gamma is not None else None
+    if C == 0:
+        return out, stats
+    with _on(a.device):
+        check(_lib.load().gnnops_head_act_norm(a.data_ptr(), lda, _ptr(bias), _ptr(scale), _ptr(gamma), _ptr(beta), out.data_ptr(),
+                                               _ptr(stats), N, heads, C, int(bool(relu)), float(eps), _dtype_code(a, "head_act_norm"),
+                                               _stream()), "head_act_norm")
+    return out, stats
+
+
+def head_act_norm(a, heads, bias=None, relu=True, scale=None, norm_weight=None, norm_bias=None, eps=1e-5):
+    """out[i] = LayerNorm(relu(mean over heads of a[i] + bias) * scale[i]) in one row pass (csrc/norm.hip): what the GATv2 model
+    runs between two attention passes. a [N, heads * C] (a column block of a wider matrix is fine), bias [C], scale [N, C] (the
+    dropout mask already divided by 1 - p; not differentiated), norm_weight / norm_bias [C]; each optional: without norm_weight
+    there is no normalisation. Differentiable in a, bias, norm_weight and norm_bias; the backward recomputes the row from a."""
+    if _wants_grad(scale):
+        raise RuntimeError("head_act_norm: scale (the dropout mask) is not differentiated; detach it")
+    if _wants_grad(a, bias, norm_weight, norm_bias):
+        return _HeadActNorm.apply(a, bias, scale, norm_weight, norm_bias, heads, bool(relu), float(eps))
+    return _norm_forward(a, heads, bias, relu, scale, norm_weight, norm_bias, eps, False)[0]
+
+
+class _HeadActNorm(torch.autograd.Function):
+    """backward (gnnops_head_act_norm_backward): saves the operands and (mu, rstd) only; y, the ReLU gate and xhat are recomputed
+    from a. d bias / d norm_weight / d norm_bias are fp32 partial sums added in a fixed order (no atomics)."""
+
+    @staticmethod
+    def forward(ctx, a, bias, scale, norm_weight, norm_bias, heads, relu, eps):
+        out, stats = _norm_forward(a, heads, bias, relu, scale, norm_weight, norm_bias, eps, True)
+        ctx.meta = (heads, relu)
+        ctx.save_for_backward(a, bias, scale, norm_weight, norm_bias, stats)
+        return out
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        a0, bias0, scale, gamma0, beta0, stats = ctx.saved_tensors
+        heads, relu = ctx.meta
+        a, lda, bias, scale, gamma, _, HC, C = _norm_operands(a0, heads, bias0, scale, gamma0, None)
+        N = a.size(0)
+        need_a, need_bias, _, need_gamma, need_beta = ctx.needs_input_grad[:5]
+        d_a = torch.empty((N, HC), dtype=a.dtype, device=a.device)
+        d_bias = torch.zeros(C, dtype=a.dtype, device=a.device) if need_bias else None
+        d_gamma = torch.zeros(C, dtype=a.dtype, device=a.device) if need_gamma else None
+        d_beta = torch.zeros(C, dtype=a.dtype, device=a.device) if need_beta else None
+        if N and C:
+            # the layouts autograd hands over, as `_EdgeAttention.backward`: unit column stride in place (pitch 0 = one row for
+            # all), anything else copied
+            g = grad_out if grad_out.dim() == 2 and (grad_out.stride(1) == 1 or grad_out.size(1) == 1) else grad_out.contiguous()
+            g, ldg = _rows(g, "the output gradient", 1, C, op="head_act_norm")
+            if g.size(0) > 1 and g.stride(0) == 0:
+                ldg = 0
+            L = _lib.load()
+            ws_bytes = L.gnnops_head_act_norm_backward_workspace_bytes(N, heads, C)
+            ws = torch.empty(ws_bytes, dtype=torch.uint8, device=a.device)
+            with _on(a.device):
+                check(L.gnnops_head_act_norm_backward(a.data_ptr(), lda, _ptr(bias), _ptr(scale), _ptr(gamma), _ptr(stats), g.data_ptr(), ldg,
+                                                      d_a.data_ptr(), _ptr(d_bias), _ptr(d_gamma), _ptr(d_beta), N, heads, C, int(relu),
+                                                      _dtype_code(a, "head_act_norm"), ws.data_ptr(), ws_bytes, _stream()),
+                      "head_act_norm_backward")
+        shaped = lambda d, like: None if d is None else d.view(like.shape)   # noqa: E731
+        return (d_a if need_a else None, shaped(d_bias, bias0) if need_bias else None, None, shaped(d_gamma, gamma0) if need_gamma else None,
+                shaped(d_beta, beta0) if need_beta else None, None, None, None)
+
+
+def _feature_scale(n, channels, p, dtype, device):
+    """The feature dropout mask of one layer of `GATv2`, [N, C]: Bernoulli(1 - p) drawn with torch, already divided by 1 - p."""
+    keep = torch.rand((n, channels), device=device) >= p
+    return (keep.to(torch.float32) / (1.0 - p)).to(dtype)
+
+
+class GATv2(torch.nn.Module):
+    """The graph regressor the reference's zoo builds from GATv2Conv (GATv2REG, graph_benchmark/models/ptg_models.py): `convs` holds
+    num_conv_layers + 1 GATv2Conv(., hidden_dim, heads, concat=False), `lns` num_conv_layers LayerNorm(hidden_dim), `post_mp` one
+    Linear(hidden_dim, 1); the last conv and the last norm are parameters the forward never uses, as there, so a state_dict moves
+    across. A layer is one dense product, one attention pass and ONE `head_act_norm` (mean over heads + bias + ReLU + the feature
+    dropout mask + LayerNorm, the norm left out after the last layer); then the mean over each graph's nodes and `post_mp`."""
+
+    def __init__(self, input_dim, hidden_dim, dropout, num_conv_layers, heads):
+        super().__init__()
+        self.dropout, self.num_layers = dropout, num_conv_layers
+        self.convs = torch.nn.ModuleList([GATv2Conv(input_dim if k == 0 else hidden_dim, hidden_dim, heads=heads, concat=False)
+                                          for k in range(num_conv_layers + 1)])
+        self.lns = torch.nn.ModuleList([torch.nn.LayerNorm(hidden_dim) for _ in range(num_conv_layers)])
+        self.post_mp = torch.nn.Sequential(torch.nn.Linear(hidden_dim, 1))
+
+    def forward(self, x, edge_index=None, batch=None, num_graphs=None):
+        """forward(x, edge_index, batch), or forward(data) with data.x / data.edge_index / data.batch. num_graphs spares the read
+        of batch.max() from the device."""
+        from . import pool
+
+        if edge_index is None:
+            x, edge_index, batch = x.x, x.edge_index, x.batch
+        _require_gpu(x, edge_index, batch)
+        for k in range(self.num_layers):
+            conv = self.convs[k]
+            a = conv._attend(x, edge_index)
+            scale = None
+            if self.training and self.dropout > 0.0:
+                scale = _feature_scale(a.size(0), conv.out_channels, self.dropout, a.dtype, a.device)
+            ln = self.lns[k] if k != self.num_layers - 1 else None
+            x = head_act_norm(a, conv.heads, conv.bias, True, scale, None if ln is None else ln.weight, None if ln is None else ln.bias,
+                              1e-5 if ln is None else ln.eps)
+        return self.post_mp(pool.global_mean_pool(x, batch, num_graphs))
 
 
 # ---- attention: GAT (v1), GATEConv and AttentiveFP (csrc/attention.hip, gate_fwd_kernel / gate_bwd_kernel) ------------------

@@ -3,8 +3,11 @@
 
 `topk` is PyG's per-graph top-k without the dense [G, max_n] pad and sort: one wave per small graph, one workgroup per graph of
 up to `topk_max_len()` nodes, the radix sort engine beyond. `filter_adj` / `remove_self_loops` are one stable compaction kernel.
-Each makes one host read (the size of its result), as the upstream ops do. Nothing here is differentiable: a selection has no
+Each makes one host read (the size of its result), as the upstream ops do. The selections are not differentiable: a selection has no
 gradient (`topk` detaches its score by design), and `filter_adj` refuses an `edge_attr` that requires grad rather than drop it.
+
+`global_add_pool` / `global_mean_pool` / `global_max_pool` are the graph-level read-outs (one row per graph of `batch`) on the
+package's differentiable segment / scatter reductions: no kernel of their own.
 """
 import torch
 
@@ -137,3 +140,41 @@ def filter_adj(edge_index, edge_attr, perm, num_nodes=None):
 def remove_self_loops(edge_index, edge_attr=None):
     """torch_geometric.utils.remove_self_loops: the edges whose endpoints differ, in their original order."""
     return _filter(edge_index, edge_attr, None, True, "remove_self_loops")
+
+
+# ---- graph-level pooling: one row per graph of `batch` ------------------------------------------------------------------------
+def _global_pool(x, batch, size, reduce):
+    from . import autograd
+
+    _require_gpu(x, batch)
+    if batch.dim() != 1 or batch.numel() != x.size(0):
+        raise RuntimeError(f"global_{reduce}_pool: batch holds one graph id per row of x")
+    n = batch.numel()
+    is_sorted = True
+    if n:       # one host read: the order of batch and, without size, its largest id
+        info = torch.stack([(batch[1:] < batch[:-1]).any().to(batch.dtype), batch.max()]).tolist()
+        is_sorted = not info[0]
+        size = info[1] + 1 if size is None else size
+    size = int(size or 0)
+    if is_sorted:
+        out = autograd.segment_csr(x, rowptr_from_sorted(batch, size), reduce)
+    else:
+        out = autograd.scatter(x, batch, 0, None, size, reduce)
+    return out[0] if isinstance(out, tuple) else out
+
+
+def global_add_pool(x, batch, size=None):
+    """out[g] = sum of the rows of x whose batch id is g (torch_geometric.nn.global_add_pool). A sorted batch goes through
+    `rowptr_from_sorted` + `segment_csr`, an unsorted one through `scatter`; a graph without nodes gets a zero row.
+    Differentiable in x."""
+    return _global_pool(x, batch, size, "sum")
+
+
+def global_mean_pool(x, batch, size=None):
+    """As `global_add_pool`, the mean (a graph without nodes gets a zero row)."""
+    return _global_pool(x, batch, size, "mean")
+
+
+def global_max_pool(x, batch, size=None):
+    """As `global_add_pool`, the maximum (a graph without nodes gets a zero row)."""
+    return _global_pool(x, batch, size, "max")

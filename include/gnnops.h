@@ -772,6 +772,33 @@ int gnnops_gcn_propagate(const void* h, int64_t ldh, const int32_t* rowptr, cons
                          const float* w, const float* dis, const float* lw, const void* bias, void* out, int64_t ldo,
                          int64_t N, int64_t E, int64_t K, int dtype, gnnops_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * What the GATv2 model (the reference's GATv2REG, graph_benchmark/models/ptg_models.py) runs between two attention passes, as
+ * one row pass (csrc/norm.hip): the mean over heads, the bias, ReLU, the feature-dropout mask and LayerNorm.
+ *   y[c] = (a[i,0,c] + ... + a[i,H-1,c]) / H (+ bias[c])    r[c] = relu ? max(y[c], 0) : y[c]    d[c] = r[c] * scale[i,c]
+ *   gamma given: mu = mean_c d, var = mean_c (d - mu)^2 (biased, two passes), out[i,c] = (d[c] - mu) * rsqrt(var + eps) * gamma[c] (+ beta[c])
+ *   gamma NULL:  out[i,c] = d[c]
+ * a [N, >= H*C] (pitch lda in elements, so a column block of a wider matrix is fine), bias / gamma / beta [C], scale [N, C]
+ * dense (the mask already divided by 1 - p), out [N, C] dense, all in `dtype`; NULL bias / scale / beta = absent (beta needs
+ * gamma). fp32 arithmetic, heads added in ascending order, one rounding on store. stats (optional, read by the backward):
+ * fp32 [N, 2] = (mu, rstd), written only with gamma. 1 <= H, 1 <= C, H*C <= 8192 (GNNOPS_EINVAL otherwise); N, lda < 2^31.
+ * One launch on `stream`, no allocation, no synchronisation.
+ * Backward, given grad_out [N, >= C] (pitch ldg; 0 = one row for all) and the forward's operands and stats (nothing else is
+ * saved: y, the gate and xhat are recomputed): grad_a [N, H*C] dense (d y / H in every head), and where the pointer is not
+ * NULL grad_bias = sum_i d y, grad_gamma = sum_i grad_out * xhat, grad_beta = sum_i grad_out, each [C] (the last two need
+ * gamma). scale is not differentiated. workspace = gnnops_head_act_norm_backward_workspace_bytes(N, H, C) bytes (host-only)
+ * of fp32 partial column sums, added in a fixed order by a second kernel: no atomics, the same bits every run. N == 0:
+ * nothing is written.
+ * ------------------------------------------------------------------------------------------- */
+int gnnops_head_act_norm(const void* a, int64_t lda, const void* bias, const void* scale, const void* gamma, const void* beta,
+                         void* out, float* stats, int64_t N, int64_t H, int64_t C, int relu, float eps, int dtype,
+                         gnnops_stream_t stream);
+size_t gnnops_head_act_norm_backward_workspace_bytes(int64_t N, int64_t H, int64_t C);
+int gnnops_head_act_norm_backward(const void* a, int64_t lda, const void* bias, const void* scale, const void* gamma,
+                                  const float* stats, const void* grad_out, int64_t ldg, void* grad_a, void* grad_bias,
+                                  void* grad_gamma, void* grad_beta, int64_t N, int64_t H, int64_t C, int relu, int dtype,
+                                  void* workspace, size_t workspace_bytes, gnnops_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
