@@ -267,6 +267,17 @@ __device__ inline void accumulate(const Args& a, int n, int c0, int32_t jb, int3
     }
 }
 
+// PNA's degree scaler s of a row: degc = max(deg, 1), inv_deg = 1 / degc, logd = log(degc + 1)
+__device__ inline float degree_scale(const Args& a, int s, float degc, float inv_deg, float logd) {
+    switch (a.scal[s]) {
+        case S_AMPLIFICATION: return logd * __builtin_amdgcn_rcpf(a.avg_log);
+        case S_ATTENUATION: return a.avg_log * __builtin_amdgcn_rcpf(logd);
+        case S_LINEAR: return degc * __builtin_amdgcn_rcpf(a.avg_lin);
+        case S_INVERSE_LINEAR: return a.avg_lin * inv_deg;
+        default: return 1.f;
+    }
+}
+
 // accumulators of a whole destination -> its output blocks: aggregators x degree scalers (+ the residual row)
 template <typename T, int VEC>
 __device__ inline void finish_row(const Args& a, int n, int c0, int32_t cnt, const float* sum, const float* sq, const float* mn,
@@ -304,14 +315,7 @@ __device__ inline void finish_row(const Args& a, int n, int c0, int32_t cnt, con
         stdv[v] = __builtin_amdgcn_sqrtf(fmaxf(sq[v] * inv_deg - mean[v] * mean[v], 0.f) + 1e-5f);
     }
     for (int s = 0; s < a.n_scal; ++s) {
-        float scale = 1.f;
-        switch (a.scal[s]) {
-            case S_AMPLIFICATION: scale = logd * __builtin_amdgcn_rcpf(a.avg_log); break;
-            case S_ATTENUATION: scale = a.avg_log * __builtin_amdgcn_rcpf(logd); break;
-            case S_LINEAR: scale = degc * __builtin_amdgcn_rcpf(a.avg_lin); break;
-            case S_INVERSE_LINEAR: scale = a.avg_lin * inv_deg; break;
-            default: break;
-        }
+        const float scale = degree_scale(a, s, degc, inv_deg, logd);
         for (int g = 0; g < a.n_aggr; ++g) {
             float o[VEC];
 #pragma unroll
@@ -805,5 +809,293 @@ extern "C" int gnnops_edge_grad(int functor, const void* p, int64_t ldp, const v
         case GNNOPS_F32: return dispatch_edge_grad<float>(functor, p, ldp, q, ldq, w, ldw, g, ldg, src, dst, gp, gq, E, K, v, stream);
         case GNNOPS_F16: return dispatch_edge_grad<__half>(functor, p, ldp, q, ldq, w, ldw, g, ldg, src, dst, gp, gq, E, K, v, stream);
         default: return dispatch_edge_grad<__hip_bfloat16>(functor, p, ldp, q, ldq, w, ldw, g, ldg, src, dst, gp, gq, E, K, v, stream);
+    }
+}
+
+// ---- backward of the MULTI-aggregator pass (PNAConv in a training loop) ----
+// For the messages that are affine in their operands (ADD: m = p[i] + q[j] (+ w[e]); COPY: m = q[j]) the gradient of every
+// operand is the gradient of the message itself, so the backward of the whole pass — any subset of sum / mean / min / max / std
+// times the degree scalers — is ONE per-edge tensor gm [E, K] = d m_e (d w = gm, d q = its segment sum over the plan of the
+// source ids) and its sum by destination (d p, accumulated here). Nothing is saved by the forward: a lane group walks its
+// destination's edges twice. Sweep 1 is the forward's own `accumulate` (the same sum, sum of squares, min and max, bit for bit
+// for rows the forward did not reduce piecewise); between the sweeps the output gradient's A x S blocks are folded, once per
+// row, into one coefficient per aggregator (the scalers depend on the degree only); sweep 2 recomputes each message — its rows
+// are in cache from sweep 1 — and writes
+//   d m_e = ga_sum + ga_mean / deg + ga_std * [var > 0] * (m_e - mean) / (deg * std) + [e is the min's edge] ga_min + [e is the max's edge] ga_max
+// min / max hand their gradient to ONE edge per column: the smallest edge id among those that attain the value (the arg rule of
+// gnnops.scatter). The plan is stable — ascending edge ids inside a destination — so that edge is the first hit in plan order and
+// a per-column "taken" bit decides. No atomics, one writer per element: the same bits every run. A destination with more than
+// T_HUB edges takes the same loop (correct, one lane group per column chunk: slow); a piecewise pass is not written.
+// mean(m^2) - mean^2 is good to a few ulp of mean(m^2); where var + 1e-5 is a small part of that (a few nearly equal messages)
+// 1 / std is not, and such a row takes one more sweep for the centred variance. Registers (gfx950, compiler resource-usage
+// remarks, all instances): no scratch, no VGPR spill, at most 172 VGPRs; DESIGN.md §4 "Message-passing layers".
+namespace {
+struct MultiGradArgs {
+    Args a;           // the forward's operands and plan; out / add / the hub fields are unused
+    const void* g;    // [N, n_scal * n_aggr * K] output gradient, blocks as finish_row writes them
+    int64_t ldg;      // its row pitch; 0 = one row for all
+    void* gm;         // [E, K] d m_e, row = ORIGINAL edge id
+    void* gp;         // [N, K] d p (ADD), or nullptr (COPY)
+};
+
+__device__ inline bool gstd_used(const Args& a) {
+    for (int g = 0; g < a.n_aggr; ++g)
+        if (a.aggr[g] == A_STD) return true;
+    return false;
+}
+
+template <typename T, int F, bool HAS_W, int VEC, bool WAVE_ROW>
+__device__ inline void multi_grad_row(const MultiGradArgs& b, int n, int c0, bool in_row, int32_t beg, int32_t end) {
+    constexpr int U = 4;
+    constexpr bool HAS_P = Parts<F>::P > 0;
+    const Args& a = b.a;
+    const int K = (int)a.K;
+    const int32_t cnt = end - beg;
+    if (cnt == 0) {   // no edge: d p = 0, nothing else to write
+        if constexpr (HAS_P) {
+            if (in_row) {
+                float z[VEC];
+#pragma unroll
+                for (int v = 0; v < VEC; ++v) z[v] = 0.f;
+                store_vec<T, VEC>((T*)b.gp + (int64_t)n * K + c0, z);
+            }
+        }
+        return;
+    }
+    float sum[VEC], sq[VEC], mn[VEC], mx[VEC];
+    reset<VEC>(sum, sq, mn, mx);
+    accumulate<T, F, true, HAS_W, VEC, WAVE_ROW>(a, n, c0, beg, end, sum, sq, mn, mx);   // sweep 1 (every lane of a WAVE_ROW wave takes part)
+    if (!in_row) return;
+
+    // one coefficient per aggregator: ga_a = sum over the scalers of scale_s(deg) * G[n, s, a]
+    const float degc = (float)cnt;
+    const float inv_deg = 1.f / degc;
+    const float logd = __builtin_amdgcn_logf(degc + 1.f) * 0.693147181f;
+    float gsum[VEC], gmean[VEC], gmin[VEC], gmax[VEC], gstd[VEC];
+#pragma unroll
+    for (int v = 0; v < VEC; ++v) { gsum[v] = 0.f; gmean[v] = 0.f; gmin[v] = 0.f; gmax[v] = 0.f; gstd[v] = 0.f; }
+    const T* grow = (const T*)b.g + (int64_t)n * b.ldg + c0;
+    for (int s = 0; s < a.n_scal; ++s) {
+        const float scale = degree_scale(a, s, degc, inv_deg, logd);
+        for (int g = 0; g < a.n_aggr; ++g) {
+            float t[VEC];
+            load_vec<T, VEC>(grow + (int64_t)(s * a.n_aggr + g) * K, t);
+#pragma unroll
+            for (int v = 0; v < VEC; ++v) {
+                const float x = t[v] * scale;
+                switch (a.aggr[g]) {
+                    case A_SUM: gsum[v] += x; break;
+                    case A_MEAN: gmean[v] += x; break;
+                    case A_MIN: gmin[v] += x; break;
+                    case A_MAX: gmax[v] += x; break;
+                    default: gstd[v] += x; break;
+                }
+            }
+        }
+    }
+    const T* __restrict__ q = (const T*)a.q;
+    const T* __restrict__ w = (const T*)a.w;
+    const int32_t* __restrict__ perm = a.perm;
+    const int64_t* __restrict__ col = a.col;
+    T* __restrict__ gm = (T*)b.gm;
+    float pv[1][VEC], dp[VEC];
+#pragma unroll
+    for (int v = 0; v < VEC; ++v) { pv[0][v] = 0.f; dp[v] = 0.f; }
+    if constexpr (HAS_P) load_vec<T, VEC>((const T*)a.p + (int64_t)n * a.ldp + c0, pv[0]);
+
+    // per column: d m_e = base + cs * (m_e - mean) (+ gmin / gmax at the arg edges); mean and var as finish_row forms them
+    float mean[VEC], var[VEC], base[VEC], cs[VEC];
+    bool cancels = false;
+#pragma unroll
+    for (int v = 0; v < VEC; ++v) {
+        mean[v] = sum[v] * inv_deg;
+        const float msq = sq[v] * inv_deg;
+        var[v] = msq - mean[v] * mean[v];
+        // mean(m^2) - mean^2 is good to a few ulp of mean(m^2): fine for the forward's std, but d std / d m divides by std, and where
+        // var + 1e-5 is a small part of mean(m^2) (a few nearly equal messages) those ulps are percents of it
+        cancels = cancels || (fmaxf(var[v], 0.f) + 1e-5f < 0.1f * msq);
+    }
+    if (cancels && gstd_used(a)) {   // rare and short rows: the variance once more, as the mean of (m - mean)^2
+#pragma unroll
+        for (int v = 0; v < VEC; ++v) var[v] = 0.f;
+        for (int32_t j = beg; j < end; ++j) {
+            float qv[1][VEC], wv[1][VEC], m[VEC];
+            load_vec<T, VEC>(q + col[j] * a.ldq + c0, qv[0]);
+            if constexpr (HAS_W) load_vec<T, VEC>(w + (int64_t)(perm ? perm[j] : j) * a.ldw + c0, wv[0]);
+            message<F, HAS_W, VEC, sizeof(T) == 4>(pv, qv, wv, m);
+#pragma unroll
+            for (int v = 0; v < VEC; ++v) var[v] += (m[v] - mean[v]) * (m[v] - mean[v]);
+        }
+#pragma unroll
+        for (int v = 0; v < VEC; ++v) var[v] *= inv_deg;
+    }
+#pragma unroll
+    for (int v = 0; v < VEC; ++v) {
+        const float stdv = __builtin_amdgcn_sqrtf(fmaxf(var[v], 0.f) + 1e-5f);
+        base[v] = gsum[v] + gmean[v] * inv_deg;
+        cs[v] = var[v] > 0.f ? gstd[v] * inv_deg / stdv : 0.f;   // relu passes no gradient at 0 (torch)
+    }
+
+    // sweep 2
+    unsigned int took_min = 0u, took_max = 0u;   // bit v: column v's min / max gradient has been handed out
+    for (int32_t j = beg; j < end; j += U) {
+        int64_t c[U], e[U];
+        u32x4 qr[U], wr[U];
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            c[u] = 0; e[u] = 0;
+            if (j + u < end) {
+                c[u] = col[j + u];
+                e[u] = perm ? perm[j + u] : j + u;
+            }
+        }
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            if (j + u < end) {
+                qr[u] = load_raw<T, VEC>(q + c[u] * a.ldq + c0);
+                if constexpr (HAS_W) wr[u] = load_raw<T, VEC>(w + e[u] * a.ldw + c0);
+            }
+        }
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            if (j + u < end) {
+                float qv[1][VEC], wv[1][VEC], m[VEC], d[VEC];
+                unpack_vec<T, VEC>(qr[u], qv[0]);
+                if constexpr (HAS_W) unpack_vec<T, VEC>(wr[u], wv[0]);
+                message<F, HAS_W, VEC, sizeof(T) == 4>(pv, qv, wv, m);   // the same additions as sweep 1: the same bits
+#pragma unroll
+                for (int v = 0; v < VEC; ++v) {
+                    float t = base[v] + cs[v] * (m[v] - mean[v]);
+                    if (!((took_min >> v) & 1u) && m[v] == mn[v]) { t += gmin[v]; took_min |= 1u << v; }
+                    if (!((took_max >> v) & 1u) && m[v] == mx[v]) { t += gmax[v]; took_max |= 1u << v; }
+                    d[v] = t;
+                    dp[v] += t;
+                }
+                store_vec<T, VEC>(gm + e[u] * K + c0, d);
+            }
+        }
+    }
+    if constexpr (HAS_P) store_vec<T, VEC>((T*)b.gp + (int64_t)n * K + c0, dp);
+}
+
+template <typename T, int F, bool HAS_W, int VEC, bool WAVE_ROW>
+__global__ __launch_bounds__(256) void edge_multi_grad_kernel(const MultiGradArgs b) {
+    const Args& a = b.a;
+    const int G = 1 << a.gshift;
+    const int64_t gtid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int64_t ngroups = ((int64_t)gridDim.x * blockDim.x) >> a.gshift;
+    const int gl = (int)(gtid & (G - 1));
+    const int64_t items = (int64_t)a.kchunks * a.N;
+    for (int64_t item = gtid >> a.gshift; item < items; item += ngroups) {
+        int n, chunk;
+        if (a.kchunks == 1) { n = (int)item; chunk = 0; } else { n = (int)(item % a.N); chunk = (int)(item / a.N); }
+        if constexpr (WAVE_ROW) {   // the whole wave is on this row (G = 64)
+            n = __builtin_amdgcn_readfirstlane(n);
+            chunk = __builtin_amdgcn_readfirstlane(chunk);
+        }
+        int c0 = (chunk * G + gl) * VEC;
+        const bool in_row = c0 < (int)a.K;
+        if constexpr (WAVE_ROW) {
+            if (!in_row) c0 = 0;   // stays for sweep 1 (its lanes hand the edge ids round), redoes column 0, stores nothing
+        } else if (!in_row) {
+            continue;
+        }
+        multi_grad_row<T, F, HAS_W, VEC, WAVE_ROW>(b, n, c0, in_row, a.rowptr[n], a.rowptr[n + 1]);
+    }
+}
+
+template <typename T, int F, bool HAS_W, int VEC>
+int launch_multi_grad_vec(MultiGradArgs& b, hipStream_t stream) {   // lane layout and grid as launch_vec
+    Args& a = b.a;
+    a.nt = (double)a.N * (double)a.ldq * sizeof(T) > 2.0 * 1024 * 1024 * 1024;
+    const int64_t lanes = a.K / VEC;
+    int gshift = 0;
+    while ((1 << gshift) < lanes && gshift < 6) ++gshift;
+    a.gshift = gshift;
+    a.kchunks = (int)gnnops_cdiv(lanes, (int64_t)1 << gshift);
+    const int64_t items = (int64_t)a.kchunks * a.N;
+    const int grid = gnnops_grid_cap(gnnops_cdiv(items, 256 >> gshift), 256 * 64);
+    if (gshift == 6) hipLaunchKernelGGL((edge_multi_grad_kernel<T, F, HAS_W, VEC, true>), dim3(grid), dim3(256), 0, stream, b);
+    else hipLaunchKernelGGL((edge_multi_grad_kernel<T, F, HAS_W, VEC, false>), dim3(grid), dim3(256), 0, stream, b);
+    return gnnops_check_launch("edge_multi_grad");
+}
+
+template <typename T, int F, bool HAS_W>
+int launch_multi_grad(MultiGradArgs& b, int max_vec, hipStream_t stream) {   // piece width as launch<> picks it for MULTI
+    int vec = Elem<T>::VEC;
+    while (vec > 1 && (vec > max_vec || b.a.K % vec != 0)) vec >>= 1;
+    while (vec > 1 && vec * sizeof(T) > 4 && b.a.K / vec < 64) vec >>= 1;
+    if constexpr (Elem<T>::VEC == 8) {
+        if (vec == 8) return launch_multi_grad_vec<T, F, HAS_W, 8>(b, stream);
+    }
+    if (vec == 4) return launch_multi_grad_vec<T, F, HAS_W, 4>(b, stream);
+    if (vec == 2) return launch_multi_grad_vec<T, F, HAS_W, 2>(b, stream);
+    return launch_multi_grad_vec<T, F, HAS_W, 1>(b, stream);
+}
+
+template <typename T>
+int dispatch_multi_grad(int functor, MultiGradArgs& b, int max_vec, hipStream_t stream) {
+    if (functor == F_COPY) return launch_multi_grad<T, F_COPY, false>(b, max_vec, stream);
+    return b.a.w ? launch_multi_grad<T, F_ADD, true>(b, max_vec, stream) : launch_multi_grad<T, F_ADD, false>(b, max_vec, stream);
+}
+}  // namespace
+
+extern "C" int gnnops_edge_multi_grad(int functor, const void* q, int64_t ldq, const void* p, int64_t ldp, const void* w, int64_t ldw,
+                                      const void* g, int64_t ldg, const int32_t* rowptr, const int32_t* perm, const int64_t* col,
+                                      void* gm, void* gp, int64_t N, int64_t E, int64_t K, const int* aggr, int n_aggr,
+                                      const int* scalers, int n_scalers, float avg_deg_log, float avg_deg_lin, int dtype,
+                                      gnnops_stream_t s) {
+    GNNOPS_REQUIRE(functor == F_COPY || functor == F_ADD, GNNOPS_EUNSUPPORTED,
+                   "edge_multi_grad: functor %d is not affine in its operands (copy / add only)", functor);
+    GNNOPS_REQUIRE(N >= 0 && E >= 0 && K >= 0 && ldg >= 0, GNNOPS_EINVAL, "edge_multi_grad: negative size");
+    GNNOPS_REQUIRE(N < ((int64_t)1 << 31) && E < ((int64_t)1 << 31), GNNOPS_EUNSUPPORTED, "edge_multi_grad: N and E must be < 2^31");
+    GNNOPS_REQUIRE(K < ((int64_t)1 << 24) && ldq < ((int64_t)1 << 31) && ldw < ((int64_t)1 << 31), GNNOPS_EUNSUPPORTED,
+                   "edge_multi_grad: rows of 2^24 or more elements");
+    GNNOPS_REQUIRE(n_aggr >= 1 && n_aggr <= 5 && aggr, GNNOPS_EINVAL, "edge_multi_grad: 1..5 aggregators");
+    GNNOPS_REQUIRE(n_scalers >= 0 && n_scalers <= 5 && (n_scalers == 0 || scalers), GNNOPS_EINVAL, "edge_multi_grad: 0..5 scalers");
+    if (N * K == 0) return GNNOPS_OK;
+    if (functor == F_COPY) { p = nullptr; w = nullptr; gp = nullptr; }
+    GNNOPS_REQUIRE(rowptr && g && (E == 0 || (q && col && gm)), GNNOPS_EINVAL, "edge_multi_grad: null pointer");
+    GNNOPS_REQUIRE(functor == F_COPY || (p && gp), GNNOPS_EINVAL, "edge_multi_grad: the add message needs p and gp");
+    MultiGradArgs b{};
+    Args& a = b.a;
+    a.q = q; a.p = p; a.w = w; a.rowptr = rowptr; a.perm = perm; a.col = col;
+    a.N = N; a.K = K; a.ldq = ldq; a.ldp = ldp; a.ldw = ldw;
+    a.n_aggr = n_aggr;
+    for (int i = 0; i < n_aggr; ++i) {
+        GNNOPS_REQUIRE(aggr[i] >= A_SUM && aggr[i] <= A_STD, GNNOPS_EINVAL, "edge_multi_grad: unknown aggregator %d", aggr[i]);
+        a.aggr[i] = aggr[i];
+    }
+    a.n_scal = n_scalers > 0 ? n_scalers : 1;
+    a.scal[0] = S_IDENTITY;
+    for (int i = 0; i < n_scalers; ++i) {
+        GNNOPS_REQUIRE(scalers[i] >= S_IDENTITY && scalers[i] <= S_INVERSE_LINEAR, GNNOPS_EINVAL, "edge_multi_grad: unknown scaler %d",
+                       scalers[i]);
+        a.scal[i] = scalers[i];
+    }
+    a.avg_log = avg_deg_log;
+    a.avg_lin = avg_deg_lin;
+    b.g = g; b.ldg = ldg; b.gm = gm; b.gp = gp;
+    GNNOPS_REQUIRE(ldq >= K && (!p || ldp >= K) && (!w || ldw >= K) && (ldg == 0 || ldg >= (int64_t)a.n_scal * n_aggr * K), GNNOPS_EINVAL,
+                   "edge_multi_grad: a row pitch is shorter than the row");
+    size_t es;
+    int vec;
+    switch (dtype) {
+        case GNNOPS_F32: es = 4; vec = 4; break;
+        case GNNOPS_F16: case GNNOPS_BF16: es = 2; vec = 8; break;
+        default: gnnops_set_error("edge_multi_grad: unknown dtype %d", dtype); return GNNOPS_EINVAL;
+    }
+    int max_vec = vec;   // widest aligned piece (elements) every operand row allows, as gnnops_edge_reduce_hubs
+    auto narrow = [&](const void* ptr, int64_t ld) {
+        if (!ptr) return;
+        while (max_vec > 1 && ((uintptr_t)ptr % (max_vec * es) != 0 || (ld * es) % (max_vec * es) != 0)) max_vec >>= 1;
+    };
+    narrow(q, ldq); narrow(p, ldp); narrow(w, ldw); narrow(g, ldg); narrow(gm, K); narrow(gp, K);
+    while (max_vec > 1 && K % max_vec != 0) max_vec >>= 1;
+    hipStream_t stream = (hipStream_t)s;
+    switch (dtype) {
+        case GNNOPS_F32: return dispatch_multi_grad<float>(functor, b, max_vec, stream);
+        case GNNOPS_F16: return dispatch_multi_grad<__half>(functor, b, max_vec, stream);
+        default: return dispatch_multi_grad<__hip_bfloat16>(functor, b, max_vec, stream);
     }
 }

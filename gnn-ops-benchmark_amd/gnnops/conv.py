@@ -15,9 +15,10 @@ differentiable — the dense products through gnnops.autograd.addmm, the edge pa
 is the forward's own machinery run the other way: the output gradient gathered along the TRANSPOSED plan (copy messages), or
 one streaming kernel that writes the per-edge gradient of the message (gnnops_edge_grad: cgconv / film) followed by two
 segment sums over the plans the forward already holds (by destination for the p side, by source for the q side). Packed
-weight operands are cached only while nothing requires grad. PNAConv (min / max / std aggregators with degree scalers): the
-fused multi-aggregator pass has no backward, so in a graph that needs gradients the layer runs the propagate-order chain
-(`_forward_train`: per-edge messages, one differentiable scatter per aggregator) on this package's differentiable ops.
+weight operands are cached only while nothing requires grad. PNAConv (min / max / std aggregators with degree scalers) trains
+through `edge_aggregate`: the same fused multi-aggregator pass forward, and ONE kernel backward (gnnops_edge_multi_grad: each
+destination's edges walked twice, nothing saved from the forward) that writes the per-edge gradient of the message and d p;
+d q is a segment sum over the source plan as above. `edge_reduce` itself keeps refusing a gradient for those forms.
 
 Attention: `GATv2Conv` (the reference's model zoo, graph_benchmark/models/ptg_models.py:208-236) is one dense product and one
 attention pass, `edge_attention` (csrc/attention.hip: online softmax per destination and head, trainable) — SURVEY.md §8(f) rank 1.
@@ -70,7 +71,8 @@ def edge_reduce(functor, q, edge_index, num_dst, p=None, w=None, add=None, aggr=
     if _wants_grad(q, p, w, add):
         if len(aggr) != 1 or aggr[0] not in ("sum", "add", "mean") or scalers or out is not None or flip or functor == "add":
             raise NotImplementedError("gnnops.conv.edge_reduce: an operand requires grad, but only one sum / mean aggregator "
-                                      "without scalers of a copy / cgconv / film message has a backward (PNAConv is forward-only)")
+                                      "without scalers of a copy / cgconv / film message has a backward (several aggregators, scalers or "
+                                      "the add message: gnnops.conv.edge_aggregate)")
         return _EdgeReduce.apply(functor, "mean" if aggr[0] == "mean" else "sum", edge_index, num_dst, q, p, w, add)
     _require_gpu(q, edge_index, p, w, add, out)
     edge_index, src_rows, dst_rows = _coo_rows_cols(edge_index, "edge_reduce")
@@ -191,6 +193,89 @@ class _EdgeReduce(torch.autograd.Function):
         if has_w and need_w:
             d_w = gp
         return None, None, None, None, d_q, d_p, d_w, d_add
+
+
+def edge_aggregate(functor, q, edge_index, num_dst, p=None, w=None, aggr=("mean", "min", "max", "std"), scalers=(), avg_deg=None):
+    """`edge_reduce` for the messages that are affine in their operands — "copy" (q[j]) and "add" (p[i] + q[j] (+ w[e])) — with any
+    ordered subset of sum / mean / min / max / std and PNA's degree scalers, differentiable in q, p and w: PNAConv's edge pass in a
+    training loop. The forward is the launch of `edge_reduce` (the same bits); the backward is one launch of
+    gnnops_edge_multi_grad (csrc/conv.hip), which walks every destination's edges twice and saves nothing from the forward.
+    min / max send their gradient to one edge per destination and column, the smallest edge id among those that attain the value
+    (the arg rule of gnnops.scatter); std passes nothing where the variance is 0 (torch's relu)."""
+    if functor not in ("copy", "add"):
+        raise NotImplementedError(f"gnnops.conv.edge_aggregate: the {functor} message is not affine in its operands (copy / add)")
+    if functor == "copy":
+        p = w = None
+    if _wants_grad(q, p, w):
+        return _EdgeAggregate.apply(functor, tuple(aggr), tuple(scalers), avg_deg, edge_index, num_dst, q, p, w)
+    return _aggregate_forward(functor, tuple(aggr), tuple(scalers), avg_deg, edge_index, num_dst, q, p, w)
+
+
+def _aggregate_forward(functor, aggr, scalers, avg_deg, edge_index, num_dst, q, p, w):
+    if num_dst == 0:
+        return q.new_zeros((0, max(len(scalers), 1) * len(aggr) * q.size(1)))
+    return edge_reduce(functor, q, edge_index, num_dst, p=p, w=w, aggr=aggr, scalers=scalers, avg_deg=avg_deg)
+
+
+class _EdgeAggregate(torch.autograd.Function):
+    """The multi-aggregator edge pass, differentiable in q [N_src, .], p [N_dst, .] and w [E, .]; saves its operands only.
+
+    backward: gnnops_edge_multi_grad writes gm [E, K] = d message per edge, in edge order, and d p (its sums by destination);
+    d w = gm, d q = the segment sum of gm over the plan of the source ids — as `_EdgeReduce` and `_EdgeAttention`."""
+
+    @staticmethod
+    def forward(ctx, functor, aggr, scalers, avg_deg, edge_index, num_dst, q, p, w):
+        out = _aggregate_forward(functor, aggr, scalers, avg_deg, edge_index, num_dst, q, p, w)
+        ctx.meta = (functor, aggr, scalers, avg_deg, num_dst)
+        ctx.has = (p is not None, w is not None)
+        ctx.save_for_backward(edge_index, q, *(t for t in (p, w) if t is not None))
+        return out
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        edge_index, q0, *rest = ctx.saved_tensors
+        functor, aggr, scalers, avg_deg, num_dst = ctx.meta
+        has_p, has_w = ctx.has
+        p0 = rest.pop(0) if has_p else None
+        w0 = rest.pop(0) if has_w else None
+        need_q, need_p, need_w = ctx.needs_input_grad[6:9]
+        index, src_rows, dst_rows = _coo_rows_cols(edge_index, "edge_aggregate")
+        E, K = index.size(1), q0.size(1)
+        zeros = lambda t, need: torch.zeros_like(t) if (t is not None and need) else None   # noqa: E731
+        if E == 0 or num_dst == 0 or K == 0:
+            return (None,) * 6 + (zeros(q0, need_q), zeros(p0, need_p), zeros(w0, need_w))
+        q, ldq = _rows(q0, "q", 1, K, op="edge_aggregate")
+        p, ldp = _rows(p0, "p", 1, K, op="edge_aggregate")
+        w, ldw = _rows(w0, "w", 1, K, op="edge_aggregate")
+        # autograd hands over whatever layout the consumer made (`_EdgeAttention.backward`): rows of unit column stride are read
+        # in place (pitch 0 = one expanded row for all), anything else is copied
+        g = grad_out if grad_out.stride(1) == 1 or grad_out.size(1) == 1 else grad_out.contiguous()
+        g, ldg = _rows(g, "the output gradient", 1, g.size(1), op="edge_aggregate")
+        if g.size(0) > 1 and g.stride(0) == 0:
+            ldg = 0
+        plan = get_plan(dst_rows, num_dst, owner=edge_index, tag=1, companion=src_rows)   # cached by the forward
+        col = plan.col if plan.col is not None else _csr_arrays(plan, src_rows, None, owner=edge_index, tag=0)[0]
+        gm = torch.empty((E, K), dtype=q.dtype, device=q.device)
+        d_p = torch.empty((num_dst, K), dtype=q.dtype, device=q.device) if has_p else None
+        aggr_ids = [AGGREGATORS[a] for a in aggr]
+        scal_ids = [SCALERS[s] for s in scalers]
+        c_aggr = (ctypes.c_int * len(aggr_ids))(*aggr_ids)
+        c_scal = (ctypes.c_int * max(len(scal_ids), 1))(*scal_ids)
+        avg_log, avg_lin = (1.0, 1.0) if avg_deg is None else (float(avg_deg["log"]), float(avg_deg["lin"]))
+        ptr = lambda t: t.data_ptr() if t is not None else None   # noqa: E731
+        with _on(q.device):
+            check(_lib.load().gnnops_edge_multi_grad(FUNCTORS[functor], q.data_ptr(), ldq, ptr(p), ldp, ptr(w), ldw, g.data_ptr(), ldg,
+                                                     plan.rowptr.data_ptr(), plan.perm.data_ptr(), col.data_ptr(), gm.data_ptr(),
+                                                     ptr(d_p), num_dst, E, K, c_aggr, len(aggr_ids), c_scal, len(scal_ids), avg_log,
+                                                     avg_lin, _dtype_code(q, "edge_aggregate"), _stream()), "edge_multi_grad")
+        pad = lambda d, t: d if t.size(1) == K else torch.nn.functional.pad(d, (0, t.size(1) - K))   # noqa: E731  (column blocks wider than K)
+        d_q = None
+        if need_q:
+            plan_src = get_plan(src_rows, q0.size(0), owner=edge_index, tag=0)
+            d_q = pad(ops.scatter(gm, plan_src, 0, None, None, "sum"), q0)
+        d_p = pad(d_p, p0) if (has_p and need_p) else None
+        d_w = pad(gm, w0) if (has_w and need_w) else None
+        return (None,) * 6 + (d_q, d_p, d_w)
 
 
 # ---- dense side: every weight block a layer applies per node, as ONE operand of the MFMA product ------------------------
@@ -431,7 +516,7 @@ class PNAConv(_Layer):
     aggregators mean/min/max/std, scalers identity/amplification/attenuation, deg = in-degree histogram).
     message = pre_nn([x_i, x_j (, enc(e))]) with ONE pre-layer is p_i + q_j (+ w_e); the aggregators and scalers come out of
     one edge pass, written next to x into the [N, (1 + A S) F] operand of the post layer (inference; when a gradient is needed
-    the layer runs `_forward_train`: the same mathematics as a chain of this package's differentiable ops). pre_layers > 1: the first layer is
+    the same route runs on `edge_aggregate` and a cat). pre_layers > 1: the first layer is
     still split per node, the rest of the MLP runs on per-edge rows (see forward); post_layers > 1: more node-row products."""
 
     def __init__(self, in_channels, out_channels, aggregators, scalers, deg, edge_dim=None, towers=1, pre_layers=1,
@@ -472,63 +557,19 @@ class PNAConv(_Layer):
             self._pk[name] = _Packed()
         return self._pk[name]
 
-    def _forward_train(self, x, edge_index, edge_attr):
-        """In a graph that needs gradients: the propagate-order chain — per-edge messages [E, F], one differentiable scatter per
-        aggregator (min / max route the gradient to their arg, std through its two means), the degree scalers as constant
-        factors — built from the differentiable front ends of this package's own kernels (gnnops.autograd: index_select,
-        scatter, addmm). The fused multi-aggregator edge pass has no backward; inference keeps it."""
-        from . import autograd as ad
-
-        F, T = self.F_in, self.towers
-        n = x.size(0)
-        src, dst = edge_index[0].contiguous(), edge_index[1].contiguous()
-        xt = x.view(n, T, F) if self.divide_input else x.view(n, 1, F).expand(n, T, F)
-
-        def lin(z, layer):
-            return ad.addmm(layer.bias, z.contiguous(), layer.weight.t().contiguous())
-
-        def mlp(z, seq):
-            z = lin(z, seq[0])
-            for li in range(1, (len(seq) + 1) // 2):
-                z = lin(torch.relu(z), seq[2 * li])
-            return z
-
-        e = lin(edge_attr, self.edge_encoder) if self.edge_dim is not None else None
-        deg = ad.scatter(torch.ones(dst.numel(), 1, dtype=x.dtype, device=x.device), dst, 0, None, n, "sum").clamp_(min=1)
-        logd = torch.log(deg + 1)
-        fac = {"identity": None, "amplification": logd / self.avg_deg["log"], "attenuation": self.avg_deg["log"] / logd,
-               "linear": deg / self.avg_deg["lin"], "inverse_linear": self.avg_deg["lin"] / deg}
-        outs = []
-        for t in range(T):
-            xin = xt[:, t].contiguous()
-            z = [ad.index_select(xin, 0, dst), ad.index_select(xin, 0, src)] + ([e] if e is not None else [])
-            m = mlp(torch.cat(z, dim=1), self.pre_nns[t])
-            aggs = []
-            for a in self.aggregators:
-                if a == "std":
-                    mean = ad.scatter(m, dst, 0, None, n, "mean")
-                    aggs.append(torch.sqrt(torch.relu(ad.scatter(m * m, dst, 0, None, n, "mean") - mean * mean) + 1e-5))
-                else:
-                    r = ad.scatter(m, dst, 0, None, n, "sum" if a == "add" else a)
-                    aggs.append(r[0] if isinstance(r, tuple) else r)
-            out = torch.cat(aggs, dim=1)
-            out = torch.cat([out if fac[sc] is None else out * fac[sc] for sc in self.scalers], dim=1) if self.scalers else out
-            outs.append(mlp(torch.cat([xin, out], dim=1), self.post_nns[t]))
-        return lin(outs[0] if T == 1 else torch.cat(outs, dim=1), self.lin)
-
     def forward(self, x, edge_index, edge_attr=None):
         if self.edge_dim is not None and edge_attr is None:
             raise RuntimeError("PNAConv: edge_attr is required when edge_dim is set")
-        if _wants_grad(x, edge_attr, *self.parameters()):
-            return self._forward_train(x, edge_index, edge_attr)
+        # in a graph that needs gradients the same route on the differentiable front ends: `edge_aggregate` for the edge pass, a
+        # cat for the post layer's operand (an out= view has no backward), out-of-place ReLU
+        train = _wants_grad(x, edge_attr, *self.parameters())
+        relu = torch.relu if train else torch.relu_
         F, T = self.F_in, self.towers
         n = x.size(0)
         xt = x.view(n, T, F) if self.divide_input else x.view(n, 1, F).expand(n, T, F)
         A, S = len(self.aggregators), len(self.scalers)
         e = None
         if self.edge_dim is not None:
-            if edge_attr is None:
-                raise RuntimeError("PNAConv: edge_attr is required when edge_dim is set")
             e = _linear(edge_attr.contiguous(), self.edge_encoder, self._cache("enc"))
         outs = []
         for t in range(T):
@@ -537,26 +578,35 @@ class PNAConv(_Layer):
             Wp = pre.weight                                              # [F, 2F or 3F]: columns follow cat([x_i, x_j, e])
             pq = _dense(xin, self._cache(f"pre{t}").get([Wp, pre.bias], [(Wp[:, :F], pre.bias), (Wp[:, F:2 * F], None)]))
             w = _dense(e, self._cache(f"edge{t}").get([Wp], [(Wp[:, 2 * F:], None)])) if e is not None else None
-            h = torch.empty((n, (1 + A * S) * F), dtype=x.dtype, device=x.device)
-            h[:, :F] = xin
+            if train:
+                reduce, h = edge_aggregate, None
+            else:
+                h = torch.empty((n, (1 + A * S) * F), dtype=x.dtype, device=x.device)
+                h[:, :F] = xin
+                reduce = lambda *a, **kw: edge_reduce(*a, out=h[:, F:], **kw)   # noqa: E731
             if self.pre_layers == 1:
-                edge_reduce("add", pq[:, F:], edge_index, n, p=pq[:, :F], w=w, aggr=self.aggregators, scalers=self.scalers,
-                            avg_deg=self.avg_deg, out=h[:, F:])
+                agg = reduce("add", pq[:, F:], edge_index, n, p=pq[:, :F], w=w, aggr=self.aggregators, scalers=self.scalers,
+                             avg_deg=self.avg_deg)
             else:
                 # a deeper pre-MLP is not linear in [x_i, x_j]: only its FIRST layer leaves the edge loop (the split product
                 # above); its output is materialised per edge, the remaining (ReLU, Linear) pairs run as [E, F] products, and
                 # the aggregators take the finished messages as "copy" rows of a graph whose sources are the edges themselves
+                from . import autograd as ad
+
+                select = ad.index_select if train else ops.index_select
                 src_rows, dst_rows = edge_index[0].contiguous(), edge_index[1].contiguous()
-                m = ops.index_select(pq[:, :F].contiguous(), 0, dst_rows) + ops.index_select(pq[:, F:].contiguous(), 0, src_rows)
+                m = select(pq[:, :F].contiguous(), 0, dst_rows) + select(pq[:, F:].contiguous(), 0, src_rows)
                 if w is not None:
                     m = m + w
                 for li in range(1, self.pre_layers):
-                    m = _linear(torch.relu_(m), self.pre_nns[t][2 * li], self._cache(f"pre{t}.{li}"))
+                    m = _linear(relu(m), self.pre_nns[t][2 * li], self._cache(f"pre{t}.{li}"))
                 per_edge = torch.stack([torch.arange(m.size(0), device=m.device), dst_rows])
-                edge_reduce("copy", m, per_edge, n, aggr=self.aggregators, scalers=self.scalers, avg_deg=self.avg_deg, out=h[:, F:])
+                agg = reduce("copy", m, per_edge, n, aggr=self.aggregators, scalers=self.scalers, avg_deg=self.avg_deg)
+            if train:
+                h = torch.cat([xin, agg], dim=1)
             o = _linear(h, post, self._cache(f"post{t}"))
             for li in range(1, self.post_layers):
-                o = _linear(torch.relu_(o), self.post_nns[t][2 * li], self._cache(f"post{t}.{li}"))
+                o = _linear(relu(o), self.post_nns[t][2 * li], self._cache(f"post{t}.{li}"))
             outs.append(o)
         out = outs[0] if T == 1 else torch.cat(outs, dim=1)
         return _linear(out, self.lin, self._cache("lin"))

@@ -580,6 +580,26 @@ int gnnops_edge_grad(int functor, const void* p, int64_t ldp, const void* q, int
                      const void* g, int64_t ldg, const int64_t* src, const int64_t* dst, void* gp, void* gq, int64_t E,
                      int64_t K, int dtype, gnnops_stream_t stream);
 
+/* Backward of the edge pass for SEVERAL aggregators and degree scalers (PNAConv in a training loop), for the messages that are
+ * affine in their operands: COPY (m = q[j]) and ADD (m = p[i] + q[j] (+ w[e])); other functors: GNNOPS_EUNSUPPORTED. Operands,
+ * plan (rowptr, perm, col), aggr[], scalers[] and the two averages exactly as gnnops_edge_reduce_hubs was called; nothing of the
+ * forward is saved: each destination's edges are walked twice (sum, sum of squares, min and max recomputed, then the gradient).
+ * g [N, max(n_scalers, 1) * n_aggr * K] = d loss / d out, blocks in the forward's order, row pitch ldg (0 = one row for all).
+ *   ga_a[i] = sum over the scalers s of scaler_s(deg_i) * g[i, s, a]                       (deg clamped to >= 1)
+ *   gm[e]   = ga_sum + ga_mean / deg + ga_std * [var > 0] * (m_e - mean) / (deg * std)
+ *             + [e is the min's edge] ga_min + [e is the max's edge] ga_max              var, std as the forward's std block
+ *   min / max: ONE edge per destination and column, the smallest edge id among those that attain the value.
+ * gm [E, K] dense, row = ORIGINAL edge id (perm NULL = identity): d w = gm, d q = its segment sum over the plan of the source
+ * ids (gnnops_segment_reduce). gp [N, K] dense = d p = the sum of gm over each destination's edges, accumulated in fp32 (zero
+ * row for a destination without edges); COPY: not written, pass NULL. fp32 arithmetic, one rounding on store, no atomics: the
+ * same bits every run. N, E, ldq, ldw < 2^31. One launch on `stream`, no workspace, no synchronisation. A destination with
+ * more than 8192 edges is walked by one lane group per column chunk like any other (correct, slow). */
+int gnnops_edge_multi_grad(int functor, const void* q, int64_t ldq, const void* p, int64_t ldp, const void* w, int64_t ldw,
+                           const void* g, int64_t ldg, const int32_t* rowptr, const int32_t* perm, const int64_t* col,
+                           void* gm, void* gp, int64_t N, int64_t E, int64_t K, const int* aggr, int n_aggr,
+                           const int* scalers, int n_scalers, float avg_deg_log, float avg_deg_lin, int dtype,
+                           gnnops_stream_t stream);
+
 /* ---------------------------------------------------------------------------------------------
  * Attention edge pass (csrc/attention.hip): the softmax-weighted aggregation of GATv2Conv — the reference's model zoo builds
  * GATv2REG from it (graph_benchmark/models/ptg_models.py:208-236) — in one pass with an online softmax. Operands as
