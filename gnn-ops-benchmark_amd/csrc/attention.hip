@@ -35,6 +35,17 @@
 //   out[i,h,:] = sum_{e into i} exp(s[e,h] - lse[i,h]) * k[e,h] * r[e,h,:]
 // gate_fwd_kernel / gate_bwd_kernel below: the same layout, group sums, id hand-out, online softmax and d att partials; u and k
 // are read through perm (row = original edge id, int64 offsets). With u a step holds two raw rows per edge, so its unroll halves.
+//
+// Edge features (GATv2Conv / GATConv with edge_dim), compile-time instances beside the ones above, which compile as before:
+//   first family, HASU:   z[e,h,c] = p[i,h,c] + q[j,h,c] + u[e,h,c]   (u = lin_edge(edge_attr), [E, H * C], read through perm like the
+//       gate kernels' u: row = ORIGINAL edge id, offset (int64) id * H * C, perm == NULL = identity); the message stays q[j]. Forward, the
+//       online softmax keeps its steps of Unroll<NCH>::U edges — the same maxima and rescalings, so u = 0 gives the bits of the pass
+//       without u — and fetches the raw rows of a step in two halves (AttUnroll::FWL), holding the first half's q rows for the weighted
+//       sum. Backward, where an edge stands alone, the step halves (2 / 1 / 1 / 1); t = ds * att * leaky'(z) is stored twice: inside
+//       gq[e] = a * g[i] + t[e] as before, and alone as gu[e] = d u, [E, H * C], row = original edge id. d p and d att as before.
+//   second family, HASC:  pre[e,h] = att[h,:] . r[e,h,:] + d[i,h] + c[e,h]   (c = att_edge . lin_edge(edge_attr), [E, H], read through
+//       perm exactly as edge_scale is); backward writes gc[e,h] = d pre, one store per edge and head. Instantiated without u only.
+// No atomics anywhere: two runs give the same bits.
 #include <initializer_list>
 #include <utility>
 #include "common.h"
@@ -44,6 +55,8 @@ namespace {
 
 struct AttArgs {
     const void *q, *p, *att, *g, *o;    // o, g: the stored forward output and its gradient (backward only)
+    const void* u;                      // [E, H * C], rows = ORIGINAL edge ids (read through perm), or null
+    void* gu;                           // d u [E, H * C], rows = original edge ids (backward with u only)
     const int32_t *rowptr, *perm;
     const int64_t* col;
     void *out, *dp, *gq;
@@ -94,6 +107,15 @@ __device__ inline void att_store(T* p, const float* f) {
 
 template <int NCH> struct Unroll { static constexpr int U = NCH == 1 ? 8 : NCH == 2 ? 4 : NCH <= 4 ? 2 : 1; };
 
+// With a per-edge row u an edge brings two raw rows, so the rows in flight together are those of half as many edges: forward,
+// the online softmax keeps its steps of Unroll<NCH>::U edges (the same maxima and rescalings as without u, so u = 0 gives the same
+// bits) and fetches a step's rows in two halves of FWL edges, the q rows of the first half held for the weighted sum; backward,
+// where every edge stands alone, the step itself halves.
+template <int NCH, bool HASU> struct AttUnroll {
+    static constexpr int FWL = HASU && Unroll<NCH>::U > 1 ? Unroll<NCH>::U / 2 : Unroll<NCH>::U;
+    static constexpr int BW = HASU ? (NCH == 1 ? 2 : 1) : (NCH == 1 ? 4 : NCH == 2 ? 2 : 1);
+};
+
 // where a lane stands: its head, and per piece k its element offset inside a row of H * C (0 and !ok past the head's end)
 struct Place {
     int lane, gl, G, h, C;
@@ -119,17 +141,21 @@ struct Place {
     template <int VEC> __device__ inline int off(int k) const { return ok<VEC>(k) ? h * C + (k * G + gl) * VEC : 0; }
 };
 
-template <typename T, int VEC, int NCH>
+template <typename T, int VEC, int NCH, bool HASU>
 __global__ __launch_bounds__(256) void attention_fwd_kernel(const AttArgs a) {
     constexpr int U = Unroll<NCH>::U;
+    constexpr int UL = AttUnroll<NCH, HASU>::FWL;   // edges whose raw rows are fetched together (U without u)
     constexpr bool HOLD = NCH <= 4;   // p and att pieces stay in registers
     const T* __restrict__ q = (const T*)a.q;
     const T* __restrict__ p = (const T*)a.p;
     const T* __restrict__ att = (const T*)a.att;
+    const T* __restrict__ ue = (const T*)a.u;
+    const int32_t* __restrict__ perm = a.perm;
     const int64_t* __restrict__ col = a.col;
     const int wave = __builtin_amdgcn_readfirstlane((int)(((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6));
     const int64_t items = a.N * a.hblocks;
     const int ldq = (int)a.ldq;
+    const int HC = a.H * a.C;
     const float slope = a.slope;
     const float NEG_INF = -__builtin_huge_valf();
     for (int64_t it = wave; it < items; it += a.nwaves) {
@@ -154,48 +180,64 @@ __global__ __launch_bounds__(256) void attention_fwd_kernel(const AttArgs a) {
         float m = NEG_INF, l = 0.f;
         for (int32_t jrun = jb; jrun < je; jrun += 64) {
             const int32_t jrun_end = min(jrun + 64, je);
-            int cl = 0;
-            if (jrun + lane < je) cl = (int)col[jrun + lane];   // one coalesced load: lane l holds id l of the run
+            int cl = 0, el = 0;
+            if (jrun + lane < je) {
+                cl = (int)col[jrun + lane];   // one coalesced load: lane l holds id l of the run
+                if constexpr (HASU) el = perm ? perm[jrun + lane] : jrun + lane;
+            }
             for (int32_t j = jrun; j < jrun_end; j += U) {
-                int64_t qrow[U];
+                int64_t qrow[U], erow[HASU ? U : 1];
 #pragma unroll
                 for (int u = 0; u < U; ++u) {
                     qrow[u] = (int64_t)__builtin_amdgcn_readlane(cl, (j - jrun + u) & 63) * ldq;
                     asm volatile("" : "+s"(qrow[u]));   // the row bases are computed HERE, ahead of every row load (conv.hip:209-224)
-                }
-                u32x4 qr[U][NCH];
-#pragma unroll
-                for (int u = 0; u < U; ++u) {           // every row load of the step in flight before the first is consumed
-                    if (j + u < jrun_end) {
-#pragma unroll
-                        for (int k = 0; k < NCH; ++k)
-                            if (pl.live<VEC>(k)) qr[u][k] = att_load_raw<T, VEC>(q + qrow[u] + pl.off<VEC>(k));
+                    if constexpr (HASU) {
+                        erow[u] = (int64_t)__builtin_amdgcn_readlane(el, (j - jrun + u) & 63) * HC;
+                        asm volatile("" : "+s"(erow[u]));
                     }
                 }
+                u32x4 qr[U][NCH];
                 float s[U];
 #pragma unroll
-                for (int u = 0; u < U; ++u) {
-                    s[u] = 0.f;
-                    if (j + u < jrun_end) {
-                        float part = 0.f;
+                for (int u0 = 0; u0 < U; u0 += UL) {        // one round without u, two halves with it
+                    u32x4 ur[HASU ? UL : 1][HASU ? NCH : 1];
 #pragma unroll
-                        for (int k = 0; k < NCH; ++k) {
-                            if (!pl.live<VEC>(k)) continue;
-                            float qv[VEC], pk[VEC], ak[VEC];
-                            att_unpack<T, VEC>(qr[u][k], qv);
-                            if constexpr (!HOLD) {
-                                att_unpack<T, VEC>(att_load_raw<T, VEC>(p + (int64_t)i * a.ldp + pl.off<VEC>(k)), pk);
-                                att_unpack<T, VEC>(att_load_raw<T, VEC>(att + pl.off<VEC>(k)), ak);
-                            }
-                            float sub = 0.f;
+                    for (int u = u0; u < u0 + UL; ++u) {    // every row load of the round in flight before the first is consumed
+                        if (j + u < jrun_end) {
 #pragma unroll
-                            for (int v = 0; v < VEC; ++v) {
-                                const float z = (HOLD ? pv[k][v] : pk[v]) + qv[v];
-                                sub += (HOLD ? av[k][v] : ak[v]) * (z > 0.f ? z : z * slope);
+                            for (int k = 0; k < NCH; ++k) {
+                                if (!pl.live<VEC>(k)) continue;
+                                qr[u][k] = att_load_raw<T, VEC>(q + qrow[u] + pl.off<VEC>(k));
+                                if constexpr (HASU) ur[u - u0][k] = att_load_raw<T, VEC>(ue + erow[u] + pl.off<VEC>(k));
                             }
-                            part += pl.ok<VEC>(k) ? sub : 0.f;
                         }
-                        s[u] = group_sum(part, a.gshift, lane);
+                    }
+#pragma unroll
+                    for (int u = u0; u < u0 + UL; ++u) {
+                        s[u] = 0.f;
+                        if (j + u < jrun_end) {
+                            float part = 0.f;
+#pragma unroll
+                            for (int k = 0; k < NCH; ++k) {
+                                if (!pl.live<VEC>(k)) continue;
+                                float qv[VEC], pk[VEC], ak[VEC], uv[VEC];
+                                att_unpack<T, VEC>(qr[u][k], qv);
+                                if constexpr (HASU) att_unpack<T, VEC>(ur[u - u0][k], uv);
+                                if constexpr (!HOLD) {
+                                    att_unpack<T, VEC>(att_load_raw<T, VEC>(p + (int64_t)i * a.ldp + pl.off<VEC>(k)), pk);
+                                    att_unpack<T, VEC>(att_load_raw<T, VEC>(att + pl.off<VEC>(k)), ak);
+                                }
+                                float sub = 0.f;
+#pragma unroll
+                                for (int v = 0; v < VEC; ++v) {
+                                    float z = (HOLD ? pv[k][v] : pk[v]) + qv[v];
+                                    if constexpr (HASU) z = z + uv[v];
+                                    sub += (HOLD ? av[k][v] : ak[v]) * (z > 0.f ? z : z * slope);
+                                }
+                                part += pl.ok<VEC>(k) ? sub : 0.f;
+                            }
+                            s[u] = group_sum(part, a.gshift, lane);
+                        }
                     }
                 }
                 float mn = m;
@@ -241,15 +283,16 @@ __global__ __launch_bounds__(256) void attention_fwd_kernel(const AttArgs a) {
 
 // Backward. The wave's head block is the same for all its destinations (nwaves is a multiple of hblocks), so the d att sums
 // of its lanes stay in registers across destinations and are written once, to row wave / hblocks of the partials.
-template <typename T, int VEC, int NCH>
+template <typename T, int VEC, int NCH, bool HASU>
 __global__ __launch_bounds__(256) void attention_bwd_kernel(const AttArgs a) {
-    constexpr int U = NCH == 1 ? 4 : NCH == 2 ? 2 : 1;
+    constexpr int U = AttUnroll<NCH, HASU>::BW;
     constexpr bool HOLD = NCH <= 4;
     const T* __restrict__ q = (const T*)a.q;
     const T* __restrict__ p = (const T*)a.p;
     const T* __restrict__ att = (const T*)a.att;
     const T* __restrict__ g = (const T*)a.g;
     const T* __restrict__ o = (const T*)a.o;
+    const T* __restrict__ ue = (const T*)a.u;
     const int64_t* __restrict__ col = a.col;
     const int32_t* __restrict__ perm = a.perm;
     const int wave = __builtin_amdgcn_readfirstlane((int)(((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6));
@@ -312,13 +355,16 @@ __global__ __launch_bounds__(256) void attention_bwd_kernel(const AttArgs a) {
                     asm volatile("" : "+s"(qrow[u]));
                     asm volatile("" : "+s"(erow[u]));
                 }
-                u32x4 qr[U][NCH];
+                u32x4 qr[U][NCH], ur[HASU ? U : 1][HASU ? NCH : 1];
 #pragma unroll
                 for (int u = 0; u < U; ++u) {
                     if (j + u < jrun_end) {
 #pragma unroll
-                        for (int k = 0; k < NCH; ++k)
-                            if (pl.live<VEC>(k)) qr[u][k] = att_load_raw<T, VEC>(q + qrow[u] + pl.off<VEC>(k));
+                        for (int k = 0; k < NCH; ++k) {
+                            if (!pl.live<VEC>(k)) continue;
+                            qr[u][k] = att_load_raw<T, VEC>(q + qrow[u] + pl.off<VEC>(k));
+                            if constexpr (HASU) ur[u][k] = att_load_raw<T, VEC>(ue + erow[u] + pl.off<VEC>(k));
+                        }
                     }
                 }
 #pragma unroll
@@ -328,8 +374,9 @@ __global__ __launch_bounds__(256) void attention_bwd_kernel(const AttArgs a) {
 #pragma unroll
                     for (int k = 0; k < NCH; ++k) {
                         if (!pl.live<VEC>(k)) continue;
-                        float qv[VEC], pk[VEC], ak[VEC], gk[VEC];
+                        float qv[VEC], pk[VEC], ak[VEC], gk[VEC], uv[VEC];
                         att_unpack<T, VEC>(qr[u][k], qv);
+                        if constexpr (HASU) att_unpack<T, VEC>(ur[u][k], uv);
                         if constexpr (!HOLD) {
                             att_unpack<T, VEC>(att_load_raw<T, VEC>(p + (int64_t)i * a.ldp + pl.off<VEC>(k)), pk);
                             att_unpack<T, VEC>(att_load_raw<T, VEC>(att + pl.off<VEC>(k)), ak);
@@ -338,7 +385,8 @@ __global__ __launch_bounds__(256) void attention_bwd_kernel(const AttArgs a) {
                         float s1 = 0.f, s2 = 0.f;
 #pragma unroll
                         for (int v = 0; v < VEC; ++v) {
-                            const float z = (HOLD ? pv[k][v] : pk[v]) + qv[v];
+                            float z = (HOLD ? pv[k][v] : pk[v]) + qv[v];
+                            if constexpr (HASU) z = z + uv[v];
                             s1 += (HOLD ? av[k][v] : ak[v]) * (z > 0.f ? z : z * slope);
                             s2 += (HOLD ? gv[k][v] : gk[v]) * qv[v];
                         }
@@ -352,8 +400,9 @@ __global__ __launch_bounds__(256) void attention_bwd_kernel(const AttArgs a) {
 #pragma unroll
                     for (int k = 0; k < NCH; ++k) {
                         if (!pl.live<VEC>(k)) continue;
-                        float qv[VEC], pk[VEC], ak[VEC], gk[VEC], row[VEC];
+                        float qv[VEC], pk[VEC], ak[VEC], gk[VEC], row[VEC], uv[VEC], trow[VEC];
                         att_unpack<T, VEC>(qr[u][k], qv);
+                        if constexpr (HASU) att_unpack<T, VEC>(ur[u][k], uv);
                         if constexpr (!HOLD) {
                             att_unpack<T, VEC>(att_load_raw<T, VEC>(p + (int64_t)i * a.ldp + pl.off<VEC>(k)), pk);
                             att_unpack<T, VEC>(att_load_raw<T, VEC>(att + pl.off<VEC>(k)), ak);
@@ -361,13 +410,18 @@ __global__ __launch_bounds__(256) void attention_bwd_kernel(const AttArgs a) {
                         }
 #pragma unroll
                         for (int v = 0; v < VEC; ++v) {
-                            const float z = (HOLD ? pv[k][v] : pk[v]) + qv[v];
+                            float z = (HOLD ? pv[k][v] : pk[v]) + qv[v];
+                            if constexpr (HASU) z = z + uv[v];
                             const float t = ds * (HOLD ? av[k][v] : ak[v]) * (z > 0.f ? 1.f : slope);
                             dp[k][v] = dp[k][v] + t;
                             datt[k][v] = datt[k][v] + ds * (z > 0.f ? z : z * slope);
                             row[v] = w * (HOLD ? gv[k][v] : gk[v]) + t;
+                            if constexpr (HASU) trow[v] = t;
                         }
                         if (pl.ok<VEC>(k)) att_store<T, VEC>((T*)a.gq + erow[u] + pl.off<VEC>(k), row);
+                        if constexpr (HASU) {
+                            if (pl.ok<VEC>(k)) att_store<T, VEC>((T*)a.gu + erow[u] + pl.off<VEC>(k), trow);   // d u = t, row = original edge id
+                        }
                     }
                 }
             }
@@ -398,6 +452,8 @@ __global__ __launch_bounds__(256) void attention_datt_kernel(const float* __rest
 // ---- GATConv (v1) / GATEConv ---------------------------------------------------------------------------------------------------
 struct GateArgs {
     const void *q, *d, *att, *u, *ks, *g, *o;   // u [E, H * C], ks [E, H] (edge_scale): rows = ORIGINAL edge ids, either may be null
+    const void* c;                              // [E, H], a per-edge term of the pre-activation: rows = original edge ids, or null
+    void* gc;                                   // d c [E, H] = d pre, rows = original edge ids (backward with c only)
     const int32_t *rowptr, *perm;
     const int64_t* col;
     void *out, *dd, *gq;
@@ -431,7 +487,7 @@ __device__ inline void gate_row(const u32x4& qr, const u32x4& ur, float* t) {
     }
 }
 
-template <typename T, int VEC, int NCH, bool HASU>
+template <typename T, int VEC, int NCH, bool HASU, bool HASC>
 __global__ __launch_bounds__(256) void gate_fwd_kernel(const GateArgs a) {
     constexpr int U = GateUnroll<NCH, HASU>::FW;
     constexpr bool HOLD = NCH <= 4;   // att pieces stay in registers
@@ -440,6 +496,7 @@ __global__ __launch_bounds__(256) void gate_fwd_kernel(const GateArgs a) {
     const T* __restrict__ att = (const T*)a.att;
     const T* __restrict__ ue = (const T*)a.u;
     const T* __restrict__ ks = (const T*)a.ks;
+    const T* __restrict__ ce = (const T*)a.c;
     const int64_t* __restrict__ col = a.col;
     const int32_t* __restrict__ perm = a.perm;
     const int wave = __builtin_amdgcn_readfirstlane((int)(((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6));
@@ -447,7 +504,7 @@ __global__ __launch_bounds__(256) void gate_fwd_kernel(const GateArgs a) {
     const int ldq = (int)a.ldq;
     const int HC = a.H * a.C;
     const float slope = a.slope, rs = a.row_slope;
-    const bool by_edge = HASU || ks != nullptr;   // something is read by original edge id
+    const bool by_edge = HASU || HASC || ks != nullptr;   // something is read by original edge id
     const float NEG_INF = -__builtin_huge_valf();
     for (int64_t it = wave; it < items; it += a.nwaves) {
         const int i = __builtin_amdgcn_readfirstlane((int)(it / a.hblocks));
@@ -492,7 +549,7 @@ __global__ __launch_bounds__(256) void gate_fwd_kernel(const GateArgs a) {
                     }
                 }
                 u32x4 qr[U][NCH], ur[HASU ? U : 1][HASU ? NCH : 1];
-                float kv[U];
+                float kv[U], cv[HASC ? U : 1];
 #pragma unroll
                 for (int u = 0; u < U; ++u) {           // every row load of the step in flight before the first is consumed
                     kv[u] = 1.f;
@@ -504,6 +561,7 @@ __global__ __launch_bounds__(256) void gate_fwd_kernel(const GateArgs a) {
                             if constexpr (HASU) ur[u][k] = att_load_raw<T, VEC>(ue + erow[HASU ? u : 0] + pl.off<VEC>(k));
                         }
                         if (ks) kv[u] = gate_scalar<T>(ks + krow[u] + hk);
+                        if constexpr (HASC) cv[u] = gate_scalar<T>(ce + krow[u] + hk);
                     }
                 }
                 float s[U];
@@ -523,7 +581,8 @@ __global__ __launch_bounds__(256) void gate_fwd_kernel(const GateArgs a) {
                             for (int v = 0; v < VEC; ++v) sub += (HOLD ? av[k][v] : ak[v]) * (t[v] > 0.f ? t[v] : t[v] * rs);
                             part += pl.ok<VEC>(k) ? sub : 0.f;
                         }
-                        const float pre = group_sum(part, a.gshift, lane) + dv;
+                        float pre = group_sum(part, a.gshift, lane) + dv;
+                        if constexpr (HASC) pre = pre + cv[u];
                         s[u] = pre > 0.f ? pre : pre * slope;
                     }
                 }
@@ -571,7 +630,7 @@ __global__ __launch_bounds__(256) void gate_fwd_kernel(const GateArgs a) {
 
 // Backward: as attention_bwd_kernel (one head block per wave, d att in registers across its destinations); d d[i, h] is the sum
 // of dpre over the edges of i, in a register, stored once.
-template <typename T, int VEC, int NCH, bool HASU>
+template <typename T, int VEC, int NCH, bool HASU, bool HASC>
 __global__ __launch_bounds__(256) void gate_bwd_kernel(const GateArgs a) {
     constexpr int U = GateUnroll<NCH, HASU>::BW;
     constexpr bool HOLD = NCH <= 4;
@@ -580,6 +639,7 @@ __global__ __launch_bounds__(256) void gate_bwd_kernel(const GateArgs a) {
     const T* __restrict__ att = (const T*)a.att;
     const T* __restrict__ ue = (const T*)a.u;
     const T* __restrict__ ks = (const T*)a.ks;
+    const T* __restrict__ ce = (const T*)a.c;
     const T* __restrict__ g = (const T*)a.g;
     const T* __restrict__ o = (const T*)a.o;
     const int64_t* __restrict__ col = a.col;
@@ -642,12 +702,12 @@ __global__ __launch_bounds__(256) void gate_bwd_kernel(const GateArgs a) {
                     qrow[u] = (int64_t)__builtin_amdgcn_readlane(cl, (j - jrun + u) & 63) * ldq;
                     const int64_t e = __builtin_amdgcn_readlane(el, (j - jrun + u) & 63);
                     erow[u] = e * HC;                   // always: the row of gq
-                    krow[u] = ks ? e * a.H : 0;
+                    krow[u] = (HASC || ks) ? e * a.H : 0;
                     asm volatile("" : "+s"(qrow[u]));
                     asm volatile("" : "+s"(erow[u]));
                 }
                 u32x4 qr[U][NCH], ur[HASU ? U : 1][HASU ? NCH : 1];
-                float kv[U];
+                float kv[U], cv[HASC ? U : 1];
 #pragma unroll
                 for (int u = 0; u < U; ++u) {
                     kv[u] = 1.f;
@@ -659,6 +719,7 @@ __global__ __launch_bounds__(256) void gate_bwd_kernel(const GateArgs a) {
                             if constexpr (HASU) ur[u][k] = att_load_raw<T, VEC>(ue + erow[u] + pl.off<VEC>(k));
                         }
                         if (ks) kv[u] = gate_scalar<T>(ks + krow[u] + hk);
+                        if constexpr (HASC) cv[u] = gate_scalar<T>(ce + krow[u] + hk);
                     }
                 }
 #pragma unroll
@@ -685,13 +746,17 @@ __global__ __launch_bounds__(256) void gate_bwd_kernel(const GateArgs a) {
                         spart += ok ? s1 : 0.f;
                         dapart += ok ? s2 : 0.f;
                     }
-                    const float pre = group_sum(spart, a.gshift, lane) + dv;
+                    float pre = group_sum(spart, a.gshift, lane) + dv;
+                    if constexpr (HASC) pre = pre + cv[u];
                     const float da = kv[u] * group_sum(dapart, a.gshift, lane);
                     const float w = expf((pre > 0.f ? pre : pre * slope) - lse);
                     const float ds = w * (da - delta);
                     const float dpre = ds * (pre > 0.f ? 1.f : slope);
                     const float wk = w * kv[u];
                     dd = dd + dpre;
+                    if constexpr (HASC) {
+                        if (pl.head_ok && pl.gl == 0) att_store<T, 1>((T*)a.gc + krow[u] + pl.h, &dpre);   // d c = d pre, row = original edge id
+                    }
 #pragma unroll
                     for (int k = 0; k < NCH; ++k) {
                         if (!pl.live<VEC>(k)) continue;
@@ -758,28 +823,34 @@ inline int max_vec_of(int es, std::initializer_list<std::pair<const void*, int64
     return max_vec;
 }
 
-template <typename T, bool BW, int VEC, int NCH>
+template <typename T, bool BW, bool HASU, int VEC, int NCH>
 void launch_kernel(const AttArgs& a, int grid, hipStream_t stream) {
-    if constexpr (BW) hipLaunchKernelGGL((attention_bwd_kernel<T, VEC, NCH>), dim3(grid), dim3(256), 0, stream, a);
-    else hipLaunchKernelGGL((attention_fwd_kernel<T, VEC, NCH>), dim3(grid), dim3(256), 0, stream, a);
+    if constexpr (BW) hipLaunchKernelGGL((attention_bwd_kernel<T, VEC, NCH, HASU>), dim3(grid), dim3(256), 0, stream, a);
+    else hipLaunchKernelGGL((attention_fwd_kernel<T, VEC, NCH, HASU>), dim3(grid), dim3(256), 0, stream, a);
 }
 
-template <typename T, bool BW, int VEC>
+template <typename T, bool BW, bool HASU, int VEC>
 void launch_nch(const AttArgs& a, int nch, int grid, hipStream_t stream) {
-    if (nch == 1) launch_kernel<T, BW, VEC, 1>(a, grid, stream);
-    else if (nch == 2) launch_kernel<T, BW, VEC, 2>(a, grid, stream);
-    else launch_kernel<T, BW, VEC, 4>(a, grid, stream);
+    if (nch == 1) launch_kernel<T, BW, HASU, VEC, 1>(a, grid, stream);
+    else if (nch == 2) launch_kernel<T, BW, HASU, VEC, 2>(a, grid, stream);
+    else launch_kernel<T, BW, HASU, VEC, 4>(a, grid, stream);
+}
+
+template <typename T, bool BW, bool HASU>
+void launch_vec(const AttArgs& a, const Geometry& geo, int grid, hipStream_t stream) {
+    if (geo.nch == 128) return launch_kernel<T, BW, HASU, 1, 128>(a, grid, stream);
+    if constexpr (Elem<T>::VEC == 8) {
+        if (geo.vec == 8) return launch_nch<T, BW, HASU, 8>(a, geo.nch, grid, stream);
+    }
+    if (geo.vec == 4) return launch_nch<T, BW, HASU, 4>(a, geo.nch, grid, stream);
+    if (geo.vec == 2) return launch_nch<T, BW, HASU, 2>(a, geo.nch, grid, stream);
+    return launch_nch<T, BW, HASU, 1>(a, geo.nch, grid, stream);
 }
 
 template <typename T, bool BW>
 void launch(const AttArgs& a, const Geometry& geo, int grid, hipStream_t stream) {
-    if (geo.nch == 128) return launch_kernel<T, BW, 1, 128>(a, grid, stream);
-    if constexpr (Elem<T>::VEC == 8) {
-        if (geo.vec == 8) return launch_nch<T, BW, 8>(a, geo.nch, grid, stream);
-    }
-    if (geo.vec == 4) return launch_nch<T, BW, 4>(a, geo.nch, grid, stream);
-    if (geo.vec == 2) return launch_nch<T, BW, 2>(a, geo.nch, grid, stream);
-    return launch_nch<T, BW, 1>(a, geo.nch, grid, stream);
+    if (a.u) launch_vec<T, BW, true>(a, geo, grid, stream);
+    else launch_vec<T, BW, false>(a, geo, grid, stream);
 }
 
 int check_sizes(const char* what, int64_t N, int64_t E, int64_t H, int64_t C, int64_t ldq, int64_t ldp, int dtype, int* es) {
@@ -797,55 +868,64 @@ int check_sizes(const char* what, int64_t N, int64_t E, int64_t H, int64_t C, in
     return GNNOPS_OK;
 }
 
-template <typename T, bool BW, bool HASU, int VEC, int NCH>
+template <typename T, bool BW, bool HASU, bool HASC, int VEC, int NCH>
 void gate_launch_kernel(const GateArgs& a, int grid, hipStream_t stream) {
-    if constexpr (BW) hipLaunchKernelGGL((gate_bwd_kernel<T, VEC, NCH, HASU>), dim3(grid), dim3(256), 0, stream, a);
-    else hipLaunchKernelGGL((gate_fwd_kernel<T, VEC, NCH, HASU>), dim3(grid), dim3(256), 0, stream, a);
+    if constexpr (BW) hipLaunchKernelGGL((gate_bwd_kernel<T, VEC, NCH, HASU, HASC>), dim3(grid), dim3(256), 0, stream, a);
+    else hipLaunchKernelGGL((gate_fwd_kernel<T, VEC, NCH, HASU, HASC>), dim3(grid), dim3(256), 0, stream, a);
 }
 
-template <typename T, bool BW, bool HASU, int VEC>
+template <typename T, bool BW, bool HASU, bool HASC, int VEC>
 void gate_launch_nch(const GateArgs& a, int nch, int grid, hipStream_t stream) {
-    if (nch == 1) gate_launch_kernel<T, BW, HASU, VEC, 1>(a, grid, stream);
-    else if (nch == 2) gate_launch_kernel<T, BW, HASU, VEC, 2>(a, grid, stream);
-    else gate_launch_kernel<T, BW, HASU, VEC, 4>(a, grid, stream);
+    if (nch == 1) gate_launch_kernel<T, BW, HASU, HASC, VEC, 1>(a, grid, stream);
+    else if (nch == 2) gate_launch_kernel<T, BW, HASU, HASC, VEC, 2>(a, grid, stream);
+    else gate_launch_kernel<T, BW, HASU, HASC, VEC, 4>(a, grid, stream);
 }
 
-template <typename T, bool BW, bool HASU>
+template <typename T, bool BW, bool HASU, bool HASC>
 void gate_launch_vec(const GateArgs& a, const Geometry& geo, int grid, hipStream_t stream) {
-    if (geo.nch == 128) return gate_launch_kernel<T, BW, HASU, 1, 128>(a, grid, stream);
+    if (geo.nch == 128) return gate_launch_kernel<T, BW, HASU, HASC, 1, 128>(a, grid, stream);
     if constexpr (Elem<T>::VEC == 8) {
-        if (geo.vec == 8) return gate_launch_nch<T, BW, HASU, 8>(a, geo.nch, grid, stream);
+        if (geo.vec == 8) return gate_launch_nch<T, BW, HASU, HASC, 8>(a, geo.nch, grid, stream);
     }
-    if (geo.vec == 4) return gate_launch_nch<T, BW, HASU, 4>(a, geo.nch, grid, stream);
-    if (geo.vec == 2) return gate_launch_nch<T, BW, HASU, 2>(a, geo.nch, grid, stream);
-    return gate_launch_nch<T, BW, HASU, 1>(a, geo.nch, grid, stream);
+    if (geo.vec == 4) return gate_launch_nch<T, BW, HASU, HASC, 4>(a, geo.nch, grid, stream);
+    if (geo.vec == 2) return gate_launch_nch<T, BW, HASU, HASC, 2>(a, geo.nch, grid, stream);
+    return gate_launch_nch<T, BW, HASU, HASC, 1>(a, geo.nch, grid, stream);
+}
+
+// the instances with the per-edge score term c are those of GATConv(edge_dim): no per-edge row beside it
+template <typename T, bool BW>
+void gate_launch_type(const GateArgs& a, const Geometry& geo, int grid, hipStream_t stream) {
+    if (a.c) gate_launch_vec<T, BW, false, true>(a, geo, grid, stream);
+    else if (a.u) gate_launch_vec<T, BW, true, false>(a, geo, grid, stream);
+    else gate_launch_vec<T, BW, false, false>(a, geo, grid, stream);
 }
 
 template <bool BW>
 void gate_launch(const GateArgs& a, const Geometry& geo, int grid, int dtype, hipStream_t stream) {
-    const bool has_u = a.u != nullptr;
     switch (dtype) {
-        case GNNOPS_F32: has_u ? gate_launch_vec<float, BW, true>(a, geo, grid, stream) : gate_launch_vec<float, BW, false>(a, geo, grid, stream); break;
-        case GNNOPS_F16: has_u ? gate_launch_vec<__half, BW, true>(a, geo, grid, stream) : gate_launch_vec<__half, BW, false>(a, geo, grid, stream); break;
-        default: has_u ? gate_launch_vec<__hip_bfloat16, BW, true>(a, geo, grid, stream) : gate_launch_vec<__hip_bfloat16, BW, false>(a, geo, grid, stream); break;
+        case GNNOPS_F32: gate_launch_type<float, BW>(a, geo, grid, stream); break;
+        case GNNOPS_F16: gate_launch_type<__half, BW>(a, geo, grid, stream); break;
+        default: gate_launch_type<__hip_bfloat16, BW>(a, geo, grid, stream); break;
     }
 }
 
 }  // namespace
 
-extern "C" int gnnops_edge_attention(const void* q, int64_t ldq, const void* p, int64_t ldp, const void* att, const int32_t* rowptr,
-                                     const int64_t* col, void* out, int64_t ldo, float* lse, int64_t N, int64_t E, int64_t H,
-                                     int64_t C, float negative_slope, int dtype, gnnops_stream_t s) {
+extern "C" int gnnops_edge_attention_u(const void* q, int64_t ldq, const void* p, int64_t ldp, const void* att, const void* u,
+                                       const int32_t* rowptr, const int32_t* perm, const int64_t* col, void* out, int64_t ldo,
+                                       float* lse, int64_t N, int64_t E, int64_t H, int64_t C, float negative_slope, int dtype,
+                                       gnnops_stream_t s) {
     int es = 0;
     const int rc = check_sizes("edge_attention", N, E, H, C, ldq, ldp, dtype, &es);
     if (rc != GNNOPS_OK) return rc;
     GNNOPS_REQUIRE(ldo >= H * C, GNNOPS_EINVAL, "edge_attention: a row pitch is shorter than the row");
     if (N == 0) return GNNOPS_OK;
     GNNOPS_REQUIRE(rowptr && out && lse && p && att && (E == 0 || (q && col)), GNNOPS_EINVAL, "edge_attention: null pointer");
-    const int max_vec = max_vec_of(es, {{q, ldq}, {p, ldp}, {att, 0}, {out, ldo}});
+    if (E == 0) u = nullptr;   // no edge: u is never read
+    const int max_vec = max_vec_of(es, {{q, ldq}, {p, ldp}, {att, 0}, {u, H * C}, {out, ldo}});
     const Geometry geo = geometry((int)H, (int)C, max_vec, es);
     AttArgs a{};
-    a.q = q; a.p = p; a.att = att; a.rowptr = rowptr; a.col = col; a.out = out; a.lse = lse;
+    a.q = q; a.p = p; a.att = att; a.u = u; a.rowptr = rowptr; a.perm = perm; a.col = col; a.out = out; a.lse = lse;
     a.N = N; a.ldq = ldq; a.ldp = ldp; a.ldo = ldo; a.H = (int)H; a.C = (int)C; a.slope = negative_slope;
     a.gshift = geo.gshift; a.hblocks = geo.hblocks;
     const int grid = gnnops_grid_cap(gnnops_cdiv(N * geo.hblocks, 4), 256 * 32);
@@ -859,17 +939,27 @@ extern "C" int gnnops_edge_attention(const void* q, int64_t ldq, const void* p, 
     return gnnops_check_launch("edge_attention");
 }
 
+extern "C" int gnnops_edge_attention(const void* q, int64_t ldq, const void* p, int64_t ldp, const void* att, const int32_t* rowptr,
+                                     const int64_t* col, void* out, int64_t ldo, float* lse, int64_t N, int64_t E, int64_t H,
+                                     int64_t C, float negative_slope, int dtype, gnnops_stream_t s) {
+    return gnnops_edge_attention_u(q, ldq, p, ldp, att, nullptr, rowptr, nullptr, col, out, ldo, lse, N, E, H, C, negative_slope, dtype, s);
+}
+
 extern "C" size_t gnnops_edge_attention_backward_workspace_bytes(int64_t N, int64_t H, int64_t C) {
     if (N <= 0 || H < 1 || C < 1 || H * C > 8192) return 0;
     return (size_t)rows_of_partials(N, (int)H, (int)C) * (size_t)(H * C) * sizeof(float);
 }
 
-extern "C" int gnnops_edge_attention_backward(const void* q, int64_t ldq, const void* p, int64_t ldp, const void* att,
-                                              const void* out, int64_t ldo, const float* lse, const void* grad_out, int64_t ldg,
-                                              const int32_t* rowptr, const int32_t* perm, const int64_t* col, void* grad_p,
-                                              void* gq, void* grad_att, int64_t N, int64_t E, int64_t H, int64_t C,
-                                              float negative_slope, int dtype, void* workspace, size_t workspace_bytes,
-                                              gnnops_stream_t s) {
+extern "C" size_t gnnops_edge_attention_u_backward_workspace_bytes(int64_t N, int64_t H, int64_t C) {
+    return gnnops_edge_attention_backward_workspace_bytes(N, H, C);
+}
+
+extern "C" int gnnops_edge_attention_u_backward(const void* q, int64_t ldq, const void* p, int64_t ldp, const void* att, const void* u,
+                                                const void* out, int64_t ldo, const float* lse, const void* grad_out, int64_t ldg,
+                                                const int32_t* rowptr, const int32_t* perm, const int64_t* col, void* grad_p,
+                                                void* gq, void* gu, void* grad_att, int64_t N, int64_t E, int64_t H, int64_t C,
+                                                float negative_slope, int dtype, void* workspace, size_t workspace_bytes,
+                                                gnnops_stream_t s) {
     int es = 0;
     const int rc = check_sizes("edge_attention_backward", N, E, H, C, ldq, ldp, dtype, &es);
     if (rc != GNNOPS_OK) return rc;
@@ -880,15 +970,18 @@ extern "C" int gnnops_edge_attention_backward(const void* q, int64_t ldq, const 
     if (N == 0) return GNNOPS_OK;   // no destination: nothing is written
     GNNOPS_REQUIRE(rowptr && out && lse && p && att && grad_out && grad_p && (E == 0 || (q && col && gq)), GNNOPS_EINVAL,
                    "edge_attention_backward: null pointer");
+    if (E == 0) u = nullptr;        // no edge: u is never read, gu never written
+    GNNOPS_REQUIRE(!u || gu, GNNOPS_EINVAL, "edge_attention_backward: u without a place for its gradient");
     const size_t need = gnnops_edge_attention_backward_workspace_bytes(N, H, C);
     GNNOPS_REQUIRE(workspace && workspace_bytes >= need && (uintptr_t)workspace % 16 == 0, GNNOPS_EWORKSPACE,
                    "edge_attention_backward: workspace %zu < %zu", workspace_bytes, need);
-    const int max_vec = max_vec_of(es, {{q, ldq}, {p, ldp}, {att, 0}, {out, ldo}, {grad_out, ldg}, {grad_p, HC}, {gq, HC}});
+    const int max_vec = max_vec_of(es, {{q, ldq}, {p, ldp}, {att, 0}, {out, ldo}, {grad_out, ldg}, {grad_p, HC}, {gq, HC}, {u, HC},
+                                        {u ? gu : nullptr, HC}});
     const Geometry geo = geometry((int)H, (int)C, max_vec, es);
     const int rows = rows_of_partials(N, (int)H, (int)C);
     AttArgs a{};
-    a.q = q; a.p = p; a.att = att; a.g = grad_out; a.o = out; a.rowptr = rowptr; a.perm = perm; a.col = col;
-    a.dp = grad_p; a.gq = gq; a.lse = const_cast<float*>(lse); a.partial = (float*)workspace;
+    a.q = q; a.p = p; a.att = att; a.u = u; a.g = grad_out; a.o = out; a.rowptr = rowptr; a.perm = perm; a.col = col;
+    a.dp = grad_p; a.gq = gq; a.gu = gu; a.lse = const_cast<float*>(lse); a.partial = (float*)workspace;
     a.N = N; a.ldq = ldq; a.ldp = ldp; a.ldo = ldo; a.ldg = ldg; a.H = (int)H; a.C = (int)C; a.slope = negative_slope;
     a.gshift = geo.gshift; a.hblocks = geo.hblocks;
     a.nwaves = rows * geo.hblocks;
@@ -907,20 +1000,33 @@ extern "C" int gnnops_edge_attention_backward(const void* q, int64_t ldq, const 
     return gnnops_check_launch("edge_attention_backward");
 }
 
-extern "C" int gnnops_edge_attention_v1(const void* q, int64_t ldq, const void* d, int64_t ldd, const void* att, const void* u,
-                                        const void* edge_scale, const int32_t* rowptr, const int32_t* perm, const int64_t* col,
-                                        void* out, int64_t ldo, float* lse, int64_t N, int64_t E, int64_t H, int64_t C,
-                                        int has_row_slope, float row_slope, float negative_slope, int dtype, gnnops_stream_t s) {
+extern "C" int gnnops_edge_attention_backward(const void* q, int64_t ldq, const void* p, int64_t ldp, const void* att,
+                                              const void* out, int64_t ldo, const float* lse, const void* grad_out, int64_t ldg,
+                                              const int32_t* rowptr, const int32_t* perm, const int64_t* col, void* grad_p,
+                                              void* gq, void* grad_att, int64_t N, int64_t E, int64_t H, int64_t C,
+                                              float negative_slope, int dtype, void* workspace, size_t workspace_bytes,
+                                              gnnops_stream_t s) {
+    return gnnops_edge_attention_u_backward(q, ldq, p, ldp, att, nullptr, out, ldo, lse, grad_out, ldg, rowptr, perm, col, grad_p, gq,
+                                            nullptr, grad_att, N, E, H, C, negative_slope, dtype, workspace, workspace_bytes, s);
+}
+
+extern "C" int gnnops_edge_attention_v1_c(const void* q, int64_t ldq, const void* d, int64_t ldd, const void* att, const void* u,
+                                          const void* c, const void* edge_scale, const int32_t* rowptr, const int32_t* perm,
+                                          const int64_t* col, void* out, int64_t ldo, float* lse, int64_t N, int64_t E, int64_t H,
+                                          int64_t C, int has_row_slope, float row_slope, float negative_slope, int dtype,
+                                          gnnops_stream_t s) {
     int es = 0;
     const int rc = check_sizes("edge_attention_v1", N, E, H, C, ldq, H * C, dtype, &es);
     if (rc != GNNOPS_OK) return rc;
     GNNOPS_REQUIRE(ldo >= H * C && ldd >= H, GNNOPS_EINVAL, "edge_attention_v1: a row pitch is shorter than the row");
+    GNNOPS_REQUIRE(!(u && c), GNNOPS_EUNSUPPORTED, "edge_attention_v1: a per-edge row u and a per-edge score term c together have no kernel instance");
     if (N == 0) return GNNOPS_OK;
     GNNOPS_REQUIRE(rowptr && out && lse && d && att && (E == 0 || (q && col)), GNNOPS_EINVAL, "edge_attention_v1: null pointer");
     const int max_vec = max_vec_of(es, {{q, ldq}, {att, 0}, {u, H * C}, {out, ldo}});
     const Geometry geo = geometry((int)H, (int)C, max_vec, es);
     GateArgs a{};
-    a.q = q; a.d = d; a.att = att; a.u = E ? u : nullptr; a.ks = E ? edge_scale : nullptr; a.rowptr = rowptr; a.perm = perm; a.col = col;
+    a.q = q; a.d = d; a.att = att; a.u = E ? u : nullptr; a.c = E ? c : nullptr; a.ks = E ? edge_scale : nullptr;
+    a.rowptr = rowptr; a.perm = perm; a.col = col;
     a.out = out; a.lse = lse;
     a.N = N; a.ldq = ldq; a.ldd = ldd; a.ldo = ldo; a.H = (int)H; a.C = (int)C;
     a.slope = negative_slope; a.row_slope = has_row_slope ? row_slope : 1.f;
@@ -931,27 +1037,43 @@ extern "C" int gnnops_edge_attention_v1(const void* q, int64_t ldq, const void* 
     return gnnops_check_launch("edge_attention_v1");
 }
 
+extern "C" int gnnops_edge_attention_v1(const void* q, int64_t ldq, const void* d, int64_t ldd, const void* att, const void* u,
+                                        const void* edge_scale, const int32_t* rowptr, const int32_t* perm, const int64_t* col,
+                                        void* out, int64_t ldo, float* lse, int64_t N, int64_t E, int64_t H, int64_t C,
+                                        int has_row_slope, float row_slope, float negative_slope, int dtype, gnnops_stream_t s) {
+    return gnnops_edge_attention_v1_c(q, ldq, d, ldd, att, u, nullptr, edge_scale, rowptr, perm, col, out, ldo, lse, N, E, H, C,
+                                      has_row_slope, row_slope, negative_slope, dtype, s);
+}
+
 extern "C" size_t gnnops_edge_attention_v1_backward_workspace_bytes(int64_t N, int64_t H, int64_t C) {
     return gnnops_edge_attention_backward_workspace_bytes(N, H, C);
 }
 
-extern "C" int gnnops_edge_attention_v1_backward(const void* q, int64_t ldq, const void* d, int64_t ldd, const void* att, const void* u,
-                                                 const void* edge_scale, const void* out, int64_t ldo, const float* lse,
-                                                 const void* grad_out, int64_t ldg, const int32_t* rowptr, const int32_t* perm,
-                                                 const int64_t* col, void* grad_d, void* gq, void* grad_att, int64_t N, int64_t E,
-                                                 int64_t H, int64_t C, int has_row_slope, float row_slope, float negative_slope,
-                                                 int dtype, void* workspace, size_t workspace_bytes, gnnops_stream_t s) {
+extern "C" size_t gnnops_edge_attention_v1_c_backward_workspace_bytes(int64_t N, int64_t H, int64_t C) {
+    return gnnops_edge_attention_backward_workspace_bytes(N, H, C);
+}
+
+extern "C" int gnnops_edge_attention_v1_c_backward(const void* q, int64_t ldq, const void* d, int64_t ldd, const void* att, const void* u,
+                                                   const void* c, const void* edge_scale, const void* out, int64_t ldo,
+                                                   const float* lse, const void* grad_out, int64_t ldg, const int32_t* rowptr,
+                                                   const int32_t* perm, const int64_t* col, void* grad_d, void* gq, void* gc,
+                                                   void* grad_att, int64_t N, int64_t E, int64_t H, int64_t C, int has_row_slope,
+                                                   float row_slope, float negative_slope, int dtype, void* workspace,
+                                                   size_t workspace_bytes, gnnops_stream_t s) {
     int es = 0;
     const int rc = check_sizes("edge_attention_v1_backward", N, E, H, C, ldq, H * C, dtype, &es);
     if (rc != GNNOPS_OK) return rc;
     GNNOPS_REQUIRE(ldo >= H * C && ldd >= H && (ldg >= H * C || ldg == 0), GNNOPS_EINVAL,
                    "edge_attention_v1_backward: a row pitch is shorter than the row");
     GNNOPS_REQUIRE(grad_att, GNNOPS_EINVAL, "edge_attention_v1_backward: null pointer");
+    GNNOPS_REQUIRE(!(u && c), GNNOPS_EUNSUPPORTED,
+                   "edge_attention_v1_backward: a per-edge row u and a per-edge score term c together have no kernel instance");
     hipStream_t stream = (hipStream_t)s;
     const int HC = (int)(H * C);
     if (N == 0) return GNNOPS_OK;   // no destination: nothing is written
     GNNOPS_REQUIRE(rowptr && out && lse && d && att && grad_out && grad_d && (E == 0 || (q && col && gq)), GNNOPS_EINVAL,
                    "edge_attention_v1_backward: null pointer");
+    GNNOPS_REQUIRE(E == 0 || !c || gc, GNNOPS_EINVAL, "edge_attention_v1_backward: c without a place for its gradient");
     const size_t need = gnnops_edge_attention_v1_backward_workspace_bytes(N, H, C);
     GNNOPS_REQUIRE(workspace && workspace_bytes >= need && (uintptr_t)workspace % 16 == 0, GNNOPS_EWORKSPACE,
                    "edge_attention_v1_backward: workspace %zu < %zu", workspace_bytes, need);
@@ -959,9 +1081,9 @@ extern "C" int gnnops_edge_attention_v1_backward(const void* q, int64_t ldq, con
     const Geometry geo = geometry((int)H, (int)C, max_vec, es);
     const int rows = rows_of_partials(N, (int)H, (int)C);
     GateArgs a{};
-    a.q = q; a.d = d; a.att = att; a.u = E ? u : nullptr; a.ks = E ? edge_scale : nullptr; a.g = grad_out; a.o = out;
+    a.q = q; a.d = d; a.att = att; a.u = E ? u : nullptr; a.c = E ? c : nullptr; a.ks = E ? edge_scale : nullptr; a.g = grad_out; a.o = out;
     a.rowptr = rowptr; a.perm = perm; a.col = col;
-    a.dd = grad_d; a.gq = gq; a.lse = const_cast<float*>(lse); a.partial = (float*)workspace;
+    a.dd = grad_d; a.gq = gq; a.gc = gc; a.lse = const_cast<float*>(lse); a.partial = (float*)workspace;
     a.N = N; a.ldq = ldq; a.ldd = ldd; a.ldo = ldo; a.ldg = ldg; a.H = (int)H; a.C = (int)C;
     a.slope = negative_slope; a.row_slope = has_row_slope ? row_slope : 1.f;
     a.gshift = geo.gshift; a.hblocks = geo.hblocks;
@@ -975,4 +1097,15 @@ extern "C" int gnnops_edge_attention_v1_backward(const void* q, int64_t ldq, con
         default: hipLaunchKernelGGL(attention_datt_kernel<__hip_bfloat16>, dgrid, dim3(256), 0, stream, a.partial, rows, HC, (__hip_bfloat16*)grad_att); break;
     }
     return gnnops_check_launch("edge_attention_v1_backward");
+}
+
+extern "C" int gnnops_edge_attention_v1_backward(const void* q, int64_t ldq, const void* d, int64_t ldd, const void* att, const void* u,
+                                                 const void* edge_scale, const void* out, int64_t ldo, const float* lse,
+                                                 const void* grad_out, int64_t ldg, const int32_t* rowptr, const int32_t* perm,
+                                                 const int64_t* col, void* grad_d, void* gq, void* grad_att, int64_t N, int64_t E,
+                                                 int64_t H, int64_t C, int has_row_slope, float row_slope, float negative_slope,
+                                                 int dtype, void* workspace, size_t workspace_bytes, gnnops_stream_t s) {
+    return gnnops_edge_attention_v1_c_backward(q, ldq, d, ldd, att, u, nullptr, edge_scale, out, ldo, lse, grad_out, ldg, rowptr, perm, col,
+                                               grad_d, gq, nullptr, grad_att, N, E, H, C, has_row_slope, row_slope, negative_slope, dtype,
+                                               workspace, workspace_bytes, s);
 }

@@ -24,6 +24,9 @@ Attention: `GATv2Conv` (the reference's model zoo, graph_benchmark/models/ptg_mo
 attention pass, `edge_attention` (csrc/attention.hip: online softmax per destination and head, trainable) — SURVEY.md §8(f) rank 1.
 `GATConv` (the original GAT), `GATEConv` and the `AttentiveFP` model on them (the reference's AttentiveFPREG, ptg_models.py:91-120) run
 on the second member of that family, `edge_attention_v1`: per-edge rows, a leaky ReLU on the row, attention dropout after the softmax.
+Edge features: `GATv2Conv(edge_dim=)` adds u = lin_edge(edge_attr) to the score's pre-activation (`edge_attention(..., u=)`), `GATConv(edge_dim=)`
+adds the scalar att_edge . lin_edge(edge_attr) per head from one product with the folded weight (`edge_attention_v1(..., edge_score=)`); both
+are compile-time instances of the same two passes and train through them.
 
 The GATv2 MODEL (the reference's GATv2REG) is `GATv2`: per layer the product, the attention pass and ONE `head_act_norm` pass
 (csrc/norm.hip: mean over heads + bias + ReLU + feature-dropout mask + LayerNorm, trainable), then gnnops.pool.global_mean_pool.
@@ -664,12 +667,12 @@ class SplineConv(_Layer):
 
 
 # ---- attention: GATv2 (csrc/attention.hip) ---------------------------------------------------------------------------------
-def _attention_operands(q, p, att, edge_index, num_dst, heads):
-    _require_gpu(q, p, att, edge_index)
+def _attention_operands(q, p, att, edge_index, num_dst, heads, u=None):
+    _require_gpu(q, p, att, edge_index, u)
     HC = att.numel()
     if heads < 1 or HC == 0 or HC % heads:
         raise RuntimeError(f"edge_attention: heads = {heads} does not divide the row width {HC} (att has one entry per head and channel)")
-    if q.dtype != p.dtype or q.dtype != att.dtype:
+    if q.dtype != p.dtype or q.dtype != att.dtype or (u is not None and u.dtype != q.dtype):
         raise RuntimeError("edge_attention: operands must have the same dtype")
     q, ldq = _rows(q, "q", 1, HC, op="edge_attention")
     p, ldp = _rows(p, "p", 1, HC, op="edge_attention")
@@ -678,84 +681,135 @@ def _attention_operands(q, p, att, edge_index, num_dst, heads):
     if q.size(0) >= 2 ** 31:
         raise NotImplementedError("edge_attention: 2^31 or more source rows")
     edge_index, src_rows, dst_rows = _coo_rows_cols(edge_index, "edge_attention")
-    plan = get_plan(dst_rows, num_dst, owner=edge_index, tag=1, companion=src_rows)   # the plans of edge_reduce: nothing new on a warm call
     E = edge_index.size(1)
+    if u is not None:
+        if u.dim() != 2 or tuple(u.shape) != (E, HC):
+            raise RuntimeError(f"edge_attention: u must be [E, heads * channels] = [{E}, {HC}], in the order of edge_index")
+        if u.device != q.device:
+            raise RuntimeError("edge_attention: u must be on the device of q")
+        u = u.contiguous()
+    plan = get_plan(dst_rows, num_dst, owner=edge_index, tag=1, companion=src_rows)   # the plans of edge_reduce: nothing new on a warm call
     if plan.col is not None or E == 0:
         col = plan.col if E else src_rows
     else:
         col, _ = _csr_arrays(plan, src_rows, None, owner=edge_index, tag=0)
-    return q, ldq, p, ldp, att.contiguous().view(-1), edge_index, src_rows, plan, col, E, HC
+    return q, ldq, p, ldp, att.contiguous().view(-1), u, edge_index, src_rows, plan, col, E, HC
 
 
-def _attention_forward(q, p, att, edge_index, num_dst, heads, negative_slope):
-    """(out [num_dst, H * C], lse fp32 [num_dst, H]) of one launch of gnnops_edge_attention."""
-    q, ldq, p, ldp, att, edge_index, _, plan, col, E, HC = _attention_operands(q, p, att, edge_index, num_dst, heads)
+def _attention_forward(q, p, att, edge_index, num_dst, heads, negative_slope, u=None, identity_perm=False):
+    """(out [num_dst, H * C], lse fp32 [num_dst, H]) of one launch of gnnops_edge_attention (gnnops_edge_attention_u with u).
+    identity_perm: the caller knows the edge list to be sorted by destination already, and u is read without the plan's perm."""
+    q, ldq, p, ldp, att, u, edge_index, _, plan, col, E, HC = _attention_operands(q, p, att, edge_index, num_dst, heads, u)
     out = torch.empty((num_dst, HC), dtype=q.dtype, device=q.device)
     lse = torch.empty((num_dst, heads), dtype=torch.float32, device=q.device)
+    L = _lib.load()
     with _on(q.device):
-        check(_lib.load().gnnops_edge_attention(q.data_ptr(), ldq, p.data_ptr(), ldp, att.data_ptr(), plan.rowptr.data_ptr(),
-                                                col.data_ptr(), out.data_ptr(), HC, lse.data_ptr(), num_dst, E, heads, HC // heads,
-                                                float(negative_slope), _dtype_code(q, "edge_attention"), _stream()), "edge_attention")
+        if u is None:
+            check(L.gnnops_edge_attention(q.data_ptr(), ldq, p.data_ptr(), ldp, att.data_ptr(), plan.rowptr.data_ptr(),
+                                          col.data_ptr(), out.data_ptr(), HC, lse.data_ptr(), num_dst, E, heads, HC // heads,
+                                          float(negative_slope), _dtype_code(q, "edge_attention"), _stream()), "edge_attention")
+        else:
+            check(L.gnnops_edge_attention_u(q.data_ptr(), ldq, p.data_ptr(), ldp, att.data_ptr(), u.data_ptr(), plan.rowptr.data_ptr(),
+                                            None if identity_perm else plan.perm.data_ptr(), col.data_ptr(), out.data_ptr(), HC,
+                                            lse.data_ptr(), num_dst, E, heads, HC // heads, float(negative_slope),
+                                            _dtype_code(q, "edge_attention"), _stream()), "edge_attention")
     return out, lse
 
 
-def edge_attention(q, p, att, edge_index, num_dst, heads, negative_slope=0.2):
-    """out[i, h, :] = sum over the edges (j -> i) of softmax_e(s[e, h]) * q[j, h, :],  s[e, h] = att[h] . leaky_relu(p[i, h] + q[j, h])
+def _attention_backward(q0, p0, att0, u0, edge_index, out, lse, grad_out, num_dst, heads, slope, identity_perm=False):
+    """(gq [E, H * C] or None, d p [num_dst, H * C], d att [H * C], d u [E, H * C] or None, src_rows, edge_index) of one launch of
+    gnnops_edge_attention_backward (gnnops_edge_attention_u_backward with u); None where there is no edge."""
+    q, ldq, p, ldp, att, u, edge_index, src_rows, plan, col, E, HC = _attention_operands(q0, p0, att0, edge_index, num_dst, heads, u0)
+    if E == 0 or num_dst == 0:
+        return None, None, None, None, src_rows, edge_index
+    # autograd hands over whatever layout the consumer made: out.sum() an expanded scalar (strides 0, 0), W @ out.t() a
+    # transposed one. Rows of unit column stride are read in place (pitch 0 = one row for all); anything else is copied.
+    g = grad_out if grad_out.dim() == 2 and (grad_out.stride(1) == 1 or grad_out.size(1) == 1) else grad_out.contiguous()
+    g, ldg = _rows(g, "the output gradient", 1, HC, op="edge_attention")
+    if g.size(0) > 1 and g.stride(0) == 0:
+        ldg = 0
+    d_p = torch.empty((num_dst, HC), dtype=q.dtype, device=q.device)
+    gq = torch.empty((E, HC), dtype=q.dtype, device=q.device)
+    d_att = torch.empty(HC, dtype=q.dtype, device=q.device)
+    L = _lib.load()
+    perm = None if identity_perm else plan.perm.data_ptr()
+    with _on(q.device):
+        if u is None:
+            ws_bytes = L.gnnops_edge_attention_backward_workspace_bytes(num_dst, heads, HC // heads)
+            ws = torch.empty(ws_bytes, dtype=torch.uint8, device=q.device)
+            d_u = None
+            check(L.gnnops_edge_attention_backward(q.data_ptr(), ldq, p.data_ptr(), ldp, att.data_ptr(), out.data_ptr(), HC,
+                                                   lse.data_ptr(), g.data_ptr(), ldg, plan.rowptr.data_ptr(), perm,
+                                                   col.data_ptr(), d_p.data_ptr(), gq.data_ptr(), d_att.data_ptr(), num_dst, E, heads,
+                                                   HC // heads, slope, _dtype_code(q, "edge_attention"), ws.data_ptr(), ws_bytes,
+                                                   _stream()), "edge_attention_backward")
+        else:
+            ws_bytes = L.gnnops_edge_attention_u_backward_workspace_bytes(num_dst, heads, HC // heads)
+            ws = torch.empty(ws_bytes, dtype=torch.uint8, device=q.device)
+            d_u = torch.empty((E, HC), dtype=q.dtype, device=q.device)
+            check(L.gnnops_edge_attention_u_backward(q.data_ptr(), ldq, p.data_ptr(), ldp, att.data_ptr(), u.data_ptr(), out.data_ptr(), HC,
+                                                     lse.data_ptr(), g.data_ptr(), ldg, plan.rowptr.data_ptr(), perm,
+                                                     col.data_ptr(), d_p.data_ptr(), gq.data_ptr(), d_u.data_ptr(), d_att.data_ptr(), num_dst,
+                                                     E, heads, HC // heads, slope, _dtype_code(q, "edge_attention"), ws.data_ptr(), ws_bytes,
+                                                     _stream()), "edge_attention_backward")
+    return gq, d_p, d_att, d_u, src_rows, edge_index
+
+
+def edge_attention(q, p, att, edge_index, num_dst, heads, negative_slope=0.2, u=None):
+    """out[i, h, :] = sum over the edges (j -> i) of softmax_e(s[e, h]) * q[j, h, :],  s[e, h] = att[h] . leaky_relu(p[i, h] + q[j, h] + u[e, h])
     — GATv2's message and aggregation in one pass with an online softmax (csrc/attention.hip). q [N_src, H * C] and p [num_dst, H * C]
-    may be column blocks of one product; att holds H * C entries (any shape); edge_index int64 [2, E] = (source, destination). A
-    destination without edges gets a zero row. Differentiable in q, p and att."""
-    if _wants_grad(q, p, att):
-        return _EdgeAttention.apply(q, p, att, edge_index, num_dst, heads, float(negative_slope))
-    return _attention_forward(q, p, att, edge_index, num_dst, heads, negative_slope)[0]
+    may be column blocks of one product; att holds H * C entries (any shape); edge_index int64 [2, E] = (source, destination); u, when
+    given, is [E, H * C] in the order of edge_index (GATv2Conv's lin_edge(edge_attr)) and enters the score only, never the message. A
+    destination without edges gets a zero row. Differentiable in q, p, att and u."""
+    if _wants_grad(q, p, att, u):
+        return _EdgeAttention.apply(q, p, att, u, edge_index, num_dst, heads, float(negative_slope))
+    return _attention_forward(q, p, att, edge_index, num_dst, heads, negative_slope, u)[0]
 
 
 class _EdgeAttention(torch.autograd.Function):
     """backward (gnnops_edge_attention_backward, destination-ordered like the forward): d p and d att from the kernel, and one
-    per-edge tensor gq [E, H * C] in edge order whose segment sum over the plan of the source ids is d q — as `_EdgeReduce`."""
+    per-edge tensor gq [E, H * C] in edge order whose segment sum over the plan of the source ids is d q — as `_EdgeReduce`. With u
+    (gnnops_edge_attention_u_backward) a second per-edge tensor in edge order is d u."""
 
     @staticmethod
-    def forward(ctx, q, p, att, edge_index, num_dst, heads, negative_slope):
-        out, lse = _attention_forward(q, p, att, edge_index, num_dst, heads, negative_slope)
-        ctx.meta = (num_dst, heads, negative_slope)
-        ctx.save_for_backward(q, p, att, edge_index, out, lse)
+    def forward(ctx, q, p, att, u, edge_index, num_dst, heads, negative_slope):
+        out, lse = _attention_forward(q, p, att, edge_index, num_dst, heads, negative_slope, u)
+        ctx.meta = (num_dst, heads, negative_slope, u is not None)
+        ctx.save_for_backward(q, p, att, edge_index, out, lse, *(() if u is None else (u,)))
         return out
 
     @staticmethod
     def backward(ctx, grad_out):
-        q0, p0, att0, edge_index, out, lse = ctx.saved_tensors
-        num_dst, heads, slope = ctx.meta
-        q, ldq, p, ldp, att, edge_index, src_rows, plan, col, E, HC = _attention_operands(q0, p0, att0, edge_index, num_dst, heads)
-        need_q, need_p, need_att = ctx.needs_input_grad[:3]
-        if E == 0 or num_dst == 0:
+        q0, p0, att0, edge_index, out, lse, *rest = ctx.saved_tensors
+        num_dst, heads, slope, has_u = ctx.meta
+        u0 = rest[0] if has_u else None
+        need_q, need_p, need_att, need_u = ctx.needs_input_grad[:4]
+        gq, d_p, d_att, d_u, src_rows, edge_index = _attention_backward(q0, p0, att0, u0, edge_index, out, lse, grad_out, num_dst, heads, slope)
+        if gq is None:
             return (torch.zeros_like(q0) if need_q else None, torch.zeros_like(p0) if need_p else None,
-                    torch.zeros_like(att0) if need_att else None, None, None, None, None)
-        # autograd hands over whatever layout the consumer made: out.sum() an expanded scalar (strides 0, 0), W @ out.t() a
-        # transposed one. Rows of unit column stride are read in place (pitch 0 = one row for all); anything else is copied.
-        g = grad_out if grad_out.dim() == 2 and (grad_out.stride(1) == 1 or grad_out.size(1) == 1) else grad_out.contiguous()
-        g, ldg = _rows(g, "the output gradient", 1, HC, op="edge_attention")
-        if g.size(0) > 1 and g.stride(0) == 0:
-            ldg = 0
-        d_p = torch.empty((num_dst, HC), dtype=q.dtype, device=q.device)
-        gq = torch.empty((E, HC), dtype=q.dtype, device=q.device)
-        d_att = torch.empty(HC, dtype=q.dtype, device=q.device)
-        L = _lib.load()
-        ws_bytes = L.gnnops_edge_attention_backward_workspace_bytes(num_dst, heads, HC // heads)
-        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=q.device)
-        with _on(q.device):
-            check(L.gnnops_edge_attention_backward(q.data_ptr(), ldq, p.data_ptr(), ldp, att.data_ptr(), out.data_ptr(), HC,
-                                                   lse.data_ptr(), g.data_ptr(), ldg, plan.rowptr.data_ptr(), plan.perm.data_ptr(),
-                                                   col.data_ptr(), d_p.data_ptr(), gq.data_ptr(), d_att.data_ptr(), num_dst, E, heads,
-                                                   HC // heads, slope, _dtype_code(q, "edge_attention"), ws.data_ptr(), ws_bytes,
-                                                   _stream()), "edge_attention_backward")
+                    torch.zeros_like(att0) if need_att else None, torch.zeros_like(u0) if has_u and need_u else None, None, None, None, None)
+        HC = att0.numel()
         d_q = None
         if need_q:
-            plan_src = get_plan(src_rows, q.size(0), owner=edge_index, tag=0)
+            plan_src = get_plan(src_rows, q0.size(0), owner=edge_index, tag=0)
             d_q = ops.scatter(gq, plan_src, 0, None, None, "sum")
             if q0.size(1) != HC:         # q was a column block wider than the H * C the pass reads
                 d_q = torch.nn.functional.pad(d_q, (0, q0.size(1) - HC))
         if need_p and p0.size(1) != HC:
             d_p = torch.nn.functional.pad(d_p, (0, p0.size(1) - HC))
-        return d_q, (d_p if need_p else None), (d_att.view(att0.shape) if need_att else None), None, None, None, None
+        return (d_q, (d_p if need_p else None), (d_att.view(att0.shape) if need_att else None), (d_u if has_u and need_u else None),
+                None, None, None, None)
+
+
+def _checked_fill_value(fill_value, who):
+    """The attribute of an added self loop (PyG's add_self_loops): "mean", or a constant."""
+    if isinstance(fill_value, str):
+        if fill_value != "mean":
+            raise ValueError(f"{who}: fill_value must be 'mean' or a number, got {fill_value!r}")
+        return fill_value
+    if isinstance(fill_value, bool) or not isinstance(fill_value, (int, float)):
+        raise ValueError(f"{who}: fill_value must be 'mean' or a number, got {fill_value!r}")
+    return float(fill_value)
 
 
 class GATv2Conv(_Layer):
@@ -765,13 +819,18 @@ class GATv2Conv(_Layer):
     shared), one attention pass (`edge_attention`), then the mean over heads (concat=False) and the bias. Parameter names and shapes
     follow PyG so a state_dict moves across; torch_geometric is not available to compare against: parity unpinned. Self loops:
     existing ones are removed, then one is added per node, and the augmented index is kept per edge_index object so that its
-    plans stay cached. Attention dropout is not implemented (the reference uses the default 0)."""
+    plans stay cached. Attention dropout is not implemented (the reference uses the default 0).
+    Edge features (edge_dim set): alpha_ij = softmax_j(att . leaky_relu(W_l x_j + W_r x_i + W_e e_ij)), lin_edge without a bias as in
+    PyG; u = edge_attr @ W_e^T is one more product, read by the same attention pass (the message stays W_l x_j). The self loops'
+    attributes follow PyG's add_self_loops: fill_value "mean" = the mean of the attributes of a node's remaining in-edges (this
+    package's scatter; a zero row for a node without any), or a constant; they are rebuilt per call, differentiable in edge_attr."""
 
     def __init__(self, in_channels, out_channels, heads=1, concat=True, negative_slope=0.2, dropout=0.0, add_self_loops=True,
-                 bias=True, share_weights=False):
+                 bias=True, share_weights=False, edge_dim=None, fill_value="mean"):
         super().__init__()
         self.in_channels, self.out_channels, self.heads, self.concat = in_channels, out_channels, heads, concat
         self.negative_slope, self.dropout, self.add_self_loops, self.share_weights = negative_slope, dropout, add_self_loops, share_weights
+        self.edge_dim, self.fill_value = edge_dim, _checked_fill_value(fill_value, "GATv2Conv")
         in_l, in_r = (in_channels, in_channels) if isinstance(in_channels, int) else in_channels
         self.lin_l = torch.nn.Linear(in_l, heads * out_channels, bias=bias)
         self.lin_r = self.lin_l if share_weights else torch.nn.Linear(in_r, heads * out_channels, bias=bias)
@@ -782,8 +841,12 @@ class GATv2Conv(_Layer):
         for lin in (self.lin_l, self.lin_r):
             if lin.bias is not None:
                 torch.nn.init.zeros_(lin.bias)
-        self._pk_both, self._pk_l, self._pk_r = _Packed(), _Packed(), _Packed()
+        if edge_dim is not None:       # present only with edge features, so that a state_dict without them keeps PyG's keys
+            self.lin_edge = torch.nn.Linear(edge_dim, heads * out_channels, bias=False)
+            torch.nn.init.xavier_uniform_(self.lin_edge.weight)
+        self._pk_both, self._pk_l, self._pk_r, self._pk_e = _Packed(), _Packed(), _Packed(), _Packed()
         self._looped = None   # (weakref to edge_index, its version, number of nodes, augmented copy)
+        self._kept = None     # (weakref to edge_index, its version, positions of the edges that are no self loops)
 
     def _with_self_loops(self, edge_index, n):
         import weakref
@@ -798,7 +861,47 @@ class GATv2Conv(_Layer):
         self._looped = (weakref.ref(edge_index), edge_index._version, n, looped) if cacheable else None
         return looped
 
-    def _attend(self, x, edge_index, size=None):
+    def _kept_edges(self, edge_index):
+        """Positions in edge_index of the edges `_with_self_loops` keeps, in their order; kept per edge_index object like the
+        augmented index, so that a warm call reads nothing back from the device."""
+        import weakref
+
+        cacheable = ops._plan_cache_enabled and ops._version_of(edge_index) is not None
+        hit = self._kept if cacheable else None
+        if hit is not None and hit[0]() is edge_index and hit[1] == ops._version_of(edge_index):
+            return hit[2]
+        kept = (edge_index[0] != edge_index[1]).nonzero().view(-1)
+        self._kept = (weakref.ref(edge_index), edge_index._version, kept) if cacheable else None
+        return kept
+
+    def _edge_rows(self, edge_attr, edge_index, n_dst, looped):
+        """edge_attr [E, edge_dim] checked against the layer and the edge list, and — with self loops — carried over to the
+        augmented list of `_with_self_loops`: the kept edges' rows in their order, then one row per node (fill_value)."""
+        who = type(self).__name__
+        if self.edge_dim is None:
+            if edge_attr is not None:
+                raise RuntimeError(f"{who}: edge_attr given, but the layer was built without edge_dim")
+            return None
+        if edge_attr is None:
+            raise RuntimeError(f"{who}: the layer was built with edge_dim = {self.edge_dim} and needs edge_attr")
+        if edge_attr.dim() == 1:
+            edge_attr = edge_attr.view(-1, 1)
+        if edge_attr.dim() != 2 or edge_attr.size(0) != edge_index.size(1) or edge_attr.size(1) != self.edge_dim:
+            raise RuntimeError(f"{who}: edge_attr must be [E, edge_dim] = [{edge_index.size(1)}, {self.edge_dim}], got {tuple(edge_attr.shape)}")
+        _require_gpu(edge_attr)
+        if not looped:
+            return edge_attr.contiguous()
+        from . import autograd
+
+        kept = self._kept_edges(edge_index)
+        rows = autograd.index_select(edge_attr.contiguous(), 0, kept)
+        if self.fill_value == "mean":      # of the in-edges that remain; a node without any gets a zero row
+            loops = autograd.scatter(rows, edge_index[1].index_select(0, kept), 0, None, n_dst, "mean")
+        else:
+            loops = rows.new_full((n_dst, self.edge_dim), self.fill_value)
+        return torch.cat([rows, loops], dim=0)
+
+    def _attend(self, x, edge_index, size=None, edge_attr=None):
         """The attention output [n_dst, H * C] before the head mean / bias of `forward` (`GATv2` fuses those into `head_act_norm`)."""
         if self.dropout > 0.0 and self.training:
             raise NotImplementedError("gnnops.conv.GATv2Conv: attention dropout is not implemented in the fused pass; construct the "
@@ -813,6 +916,7 @@ class GATv2Conv(_Layer):
             q = _dense(x_src.contiguous(), self._pk_l.get([ll.weight, ll.bias], [(ll.weight, ll.bias)]))
             p = _dense(x_dst.contiguous(), self._pk_r.get([lr.weight, lr.bias], [(lr.weight, lr.bias)]))
             n_dst = x_dst.size(0) if size is None else size[1]
+            rows = self._edge_rows(edge_attr, edge_index, n_dst, False)
         else:
             n_dst = x.size(0)
             if self.share_weights:
@@ -820,12 +924,17 @@ class GATv2Conv(_Layer):
             else:       # [q | p] = x @ [W_l^T | W_r^T]: the two projections reach the kernel as column blocks
                 qp = _dense(x.contiguous(), self._pk_both.get([ll.weight, lr.weight, ll.bias, lr.bias], [(ll.weight, ll.bias), (lr.weight, lr.bias)]))
                 q, p = qp[:, :HC], qp[:, HC:]
+            rows = self._edge_rows(edge_attr, edge_index, n_dst, self.add_self_loops)
             if self.add_self_loops:
                 edge_index = self._with_self_loops(edge_index, n_dst)
-        return edge_attention(q, p, self.att, edge_index, n_dst, H, self.negative_slope)
+        u = None
+        if rows is not None:            # u = lin_edge(edge_attr) of the augmented list: one product
+            we = self.lin_edge.weight
+            u = _edge_dense(rows, self._pk_e.get([we], [(we, None)]))
+        return edge_attention(q, p, self.att, edge_index, n_dst, H, self.negative_slope, u=u)
 
-    def forward(self, x, edge_index, size=None):
-        out = self._attend(x, edge_index, size)
+    def forward(self, x, edge_index, edge_attr=None, size=None):
+        out = self._attend(x, edge_index, size, edge_attr)
         if not self.concat:
             out = out.view(out.size(0), self.heads, self.out_channels).mean(dim=1)
         return out if self.bias is None else out + self.bias
@@ -975,15 +1084,15 @@ class GATv2(torch.nn.Module):
 
 
 # ---- attention: GAT (v1), GATEConv and AttentiveFP (csrc/attention.hip, gate_fwd_kernel / gate_bwd_kernel) ------------------
-def _v1_operands(q, d, att, edge_index, num_dst, heads, u, edge_scale):
+def _v1_operands(q, d, att, edge_index, num_dst, heads, u, edge_scale, c=None):
     op = "edge_attention_v1"
-    _require_gpu(q, d, att, edge_index, u, edge_scale)
+    _require_gpu(q, d, att, edge_index, u, edge_scale, c)
     HC = att.numel()
     if heads < 1 or HC == 0 or HC % heads:
         raise RuntimeError(f"{op}: heads = {heads} does not divide the row width {HC} (att has one entry per head and channel)")
     if HC > 8192:
         raise RuntimeError(f"{op}: heads * channels = {HC} exceeds the row limit of 8192")
-    if any(t is not None and t.dtype != q.dtype for t in (d, att, u, edge_scale)):
+    if any(t is not None and t.dtype != q.dtype for t in (d, att, u, edge_scale, c)):
         raise RuntimeError(f"{op}: operands must have the same dtype")
     q, ldq = _rows(q, "q", 1, HC, op=op)
     d, ldd = _rows(d, "d", 1, heads, op=op)
@@ -1001,92 +1110,136 @@ def _v1_operands(q, d, att, edge_index, num_dst, heads, u, edge_scale):
         if edge_scale.dim() != 2 or tuple(edge_scale.shape) != (E, heads):
             raise RuntimeError(f"{op}: edge_scale must be [E, heads] = [{E}, {heads}], in the order of edge_index")
         edge_scale = edge_scale.detach().contiguous()
+    if c is not None:
+        if c.dim() != 2 or tuple(c.shape) != (E, heads):
+            raise RuntimeError(f"{op}: edge_score must be [E, heads] = [{E}, {heads}], in the order of edge_index")
+        if u is not None:
+            raise NotImplementedError(f"{op}: u and edge_score together have no kernel instance")
+        c = c.contiguous()
     plan = get_plan(dst_rows, num_dst, owner=edge_index, tag=1, companion=src_rows)   # the plans of edge_attention: nothing new on a warm call
     if plan.col is not None or E == 0:
         col = plan.col if E else src_rows
     else:
         col, _ = _csr_arrays(plan, src_rows, None, owner=edge_index, tag=0)
-    return q, ldq, d, ldd, att.contiguous().view(-1), u, edge_scale, edge_index, src_rows, plan, col, E, HC
+    return q, ldq, d, ldd, att.contiguous().view(-1), u, edge_scale, c, edge_index, src_rows, plan, col, E, HC
 
 
-def _v1_forward(q, d, att, edge_index, num_dst, heads, u, row_slope, negative_slope, edge_scale):
-    """(out [num_dst, H * C], lse fp32 [num_dst, H]) of one launch of gnnops_edge_attention_v1."""
-    q, ldq, d, ldd, att, u, ks, edge_index, _, plan, col, E, HC = _v1_operands(q, d, att, edge_index, num_dst, heads, u, edge_scale)
+def _v1_forward(q, d, att, edge_index, num_dst, heads, u, row_slope, negative_slope, edge_scale, c=None, identity_perm=False):
+    """(out [num_dst, H * C], lse fp32 [num_dst, H]) of one launch of gnnops_edge_attention_v1 (gnnops_edge_attention_v1_c with c).
+    identity_perm: the caller knows the edge list to be sorted by destination already; the per-edge operands are read without perm."""
+    q, ldq, d, ldd, att, u, ks, c, edge_index, _, plan, col, E, HC = _v1_operands(q, d, att, edge_index, num_dst, heads, u, edge_scale, c)
     out = torch.empty((num_dst, HC), dtype=q.dtype, device=q.device)
     lse = torch.empty((num_dst, heads), dtype=torch.float32, device=q.device)
     ptr = lambda t: t.data_ptr() if t is not None else None   # noqa: E731
+    perm = None if identity_perm else plan.perm.data_ptr()
+    L = _lib.load()
     with _on(q.device):
-        check(_lib.load().gnnops_edge_attention_v1(q.data_ptr(), ldq, d.data_ptr(), ldd, att.data_ptr(), ptr(u), ptr(ks), plan.rowptr.data_ptr(),
-                                                   plan.perm.data_ptr(), col.data_ptr(), out.data_ptr(), HC, lse.data_ptr(), num_dst, E, heads,
-                                                   HC // heads, int(row_slope is not None), float(row_slope or 0.0), float(negative_slope),
-                                                   _dtype_code(q, "edge_attention_v1"), _stream()), "edge_attention_v1")
+        if c is None:
+            check(L.gnnops_edge_attention_v1(q.data_ptr(), ldq, d.data_ptr(), ldd, att.data_ptr(), ptr(u), ptr(ks), plan.rowptr.data_ptr(),
+                                             perm, col.data_ptr(), out.data_ptr(), HC, lse.data_ptr(), num_dst, E, heads,
+                                             HC // heads, int(row_slope is not None), float(row_slope or 0.0), float(negative_slope),
+                                             _dtype_code(q, "edge_attention_v1"), _stream()), "edge_attention_v1")
+        else:
+            check(L.gnnops_edge_attention_v1_c(q.data_ptr(), ldq, d.data_ptr(), ldd, att.data_ptr(), ptr(u), c.data_ptr(), ptr(ks),
+                                               plan.rowptr.data_ptr(), perm, col.data_ptr(), out.data_ptr(), HC, lse.data_ptr(), num_dst, E,
+                                               heads, HC // heads, int(row_slope is not None), float(row_slope or 0.0),
+                                               float(negative_slope), _dtype_code(q, "edge_attention_v1"), _stream()), "edge_attention_v1")
     return out, lse
 
 
-def edge_attention_v1(q, d, att, edge_index, num_dst, heads, u=None, row_slope=None, negative_slope=0.2, edge_scale=None):
+def edge_attention_v1(q, d, att, edge_index, num_dst, heads, u=None, row_slope=None, negative_slope=0.2, edge_scale=None, edge_score=None):
     """out[i, h, :] = sum over the edges e = (j -> i) of softmax_e(s[e, h]) * edge_scale[e, h] * r[e, h, :], with
     r = q[j, h] + u[e, h] (through leaky_relu(., row_slope) when row_slope is given) and s[e, h] = leaky_relu(att[h] . r[e, h] + d[i, h],
     negative_slope): the message and aggregation of GATConv (u, row_slope absent) and of AttentiveFP's GATEConv in one pass with an
     online softmax (csrc/attention.hip). q [N_src, H * C] and d [num_dst, H] may be column blocks of one product; att holds H * C
     entries; u [E, H * C] and edge_scale [E, H] follow the order of edge_index. edge_scale (the attention dropout mask divided by
     1 - p) multiplies the weighted sum only, never the softmax denominator, and is not differentiated. A destination without edges
-    gets a zero row. Differentiable in q, d, att and u."""
-    if _wants_grad(q, d, att, u):
-        return _EdgeAttentionV1.apply(q, d, att, u, edge_scale, edge_index, num_dst, heads, row_slope, float(negative_slope))
-    return _v1_forward(q, d, att, edge_index, num_dst, heads, u, row_slope, negative_slope, edge_scale)[0]
+    gets a zero row. edge_score [E, H], in the order of edge_index, is added to att[h] . r[e, h] + d[i, h] before the leaky ReLU
+    (GATConv's att_edge . lin_edge(edge_attr)); it cannot be combined with u. Differentiable in q, d, att, u and edge_score."""
+    if _wants_grad(q, d, att, u, edge_score):
+        return _EdgeAttentionV1.apply(q, d, att, u, edge_score, edge_scale, edge_index, num_dst, heads, row_slope, float(negative_slope))
+    return _v1_forward(q, d, att, edge_index, num_dst, heads, u, row_slope, negative_slope, edge_scale, edge_score)[0]
+
+
+def _v1_backward(q0, d0, att0, u0, c0, ks0, edge_index, out, lse, grad_out, num_dst, heads, row_slope, slope, identity_perm=False):
+    """(gq [E, H * C] or None, d d [num_dst, H], d att [H * C], d edge_score [E, H] or None, src_rows, edge_index) of one launch of
+    gnnops_edge_attention_v1_backward (gnnops_edge_attention_v1_c_backward with c); None where there is no edge."""
+    q, ldq, d, ldd, att, u, ks, c, edge_index, src_rows, plan, col, E, HC = _v1_operands(q0, d0, att0, edge_index, num_dst, heads, u0, ks0, c0)
+    if E == 0 or num_dst == 0:
+        return None, None, None, None, src_rows, edge_index
+    # the layouts autograd hands over, as _attention_backward takes them
+    g = grad_out if grad_out.dim() == 2 and (grad_out.stride(1) == 1 or grad_out.size(1) == 1) else grad_out.contiguous()
+    g, ldg = _rows(g, "the output gradient", 1, HC, op="edge_attention_v1")
+    if g.size(0) > 1 and g.stride(0) == 0:
+        ldg = 0
+    d_d = torch.empty((num_dst, heads), dtype=q.dtype, device=q.device)
+    gq = torch.empty((E, HC), dtype=q.dtype, device=q.device)
+    d_att = torch.empty(HC, dtype=q.dtype, device=q.device)
+    L = _lib.load()
+    ptr = lambda t: t.data_ptr() if t is not None else None   # noqa: E731
+    perm = None if identity_perm else plan.perm.data_ptr()
+    with _on(q.device):
+        if c is None:
+            ws_bytes = L.gnnops_edge_attention_v1_backward_workspace_bytes(num_dst, heads, HC // heads)
+            ws = torch.empty(ws_bytes, dtype=torch.uint8, device=q.device)
+            d_c = None
+            check(L.gnnops_edge_attention_v1_backward(q.data_ptr(), ldq, d.data_ptr(), ldd, att.data_ptr(), ptr(u), ptr(ks), out.data_ptr(), HC,
+                                                      lse.data_ptr(), g.data_ptr(), ldg, plan.rowptr.data_ptr(), perm,
+                                                      col.data_ptr(), d_d.data_ptr(), gq.data_ptr(), d_att.data_ptr(), num_dst, E, heads,
+                                                      HC // heads, int(row_slope is not None), float(row_slope or 0.0), slope,
+                                                      _dtype_code(q, "edge_attention_v1"), ws.data_ptr(), ws_bytes, _stream()),
+                  "edge_attention_v1_backward")
+        else:
+            ws_bytes = L.gnnops_edge_attention_v1_c_backward_workspace_bytes(num_dst, heads, HC // heads)
+            ws = torch.empty(ws_bytes, dtype=torch.uint8, device=q.device)
+            d_c = torch.empty((E, heads), dtype=q.dtype, device=q.device)
+            check(L.gnnops_edge_attention_v1_c_backward(q.data_ptr(), ldq, d.data_ptr(), ldd, att.data_ptr(), ptr(u), c.data_ptr(), ptr(ks),
+                                                        out.data_ptr(), HC, lse.data_ptr(), g.data_ptr(), ldg, plan.rowptr.data_ptr(), perm,
+                                                        col.data_ptr(), d_d.data_ptr(), gq.data_ptr(), d_c.data_ptr(), d_att.data_ptr(),
+                                                        num_dst, E, heads, HC // heads, int(row_slope is not None), float(row_slope or 0.0),
+                                                        slope, _dtype_code(q, "edge_attention_v1"), ws.data_ptr(), ws_bytes, _stream()),
+                  "edge_attention_v1_backward")
+    return gq, d_d, d_att, d_c, src_rows, edge_index
 
 
 class _EdgeAttentionV1(torch.autograd.Function):
     """backward (gnnops_edge_attention_v1_backward, destination-ordered like the forward): d d and d att from the kernel, and one
-    per-edge tensor gq [E, H * C] in edge order: d u is gq itself, d q its segment sum over the plan of the source ids."""
+    per-edge tensor gq [E, H * C] in edge order: d u is gq itself, d q its segment sum over the plan of the source ids. With
+    edge_score (gnnops_edge_attention_v1_c_backward) its gradient [E, H] comes from the kernel in edge order too."""
 
     @staticmethod
-    def forward(ctx, q, d, att, u, edge_scale, edge_index, num_dst, heads, row_slope, negative_slope):
-        out, lse = _v1_forward(q, d, att, edge_index, num_dst, heads, u, row_slope, negative_slope, edge_scale)
-        ctx.meta = (num_dst, heads, row_slope, negative_slope, u is not None, edge_scale is not None)
-        ctx.save_for_backward(q, d, att, edge_index, out, lse, *(t for t in (u, edge_scale) if t is not None))
+    def forward(ctx, q, d, att, u, c, edge_scale, edge_index, num_dst, heads, row_slope, negative_slope):
+        out, lse = _v1_forward(q, d, att, edge_index, num_dst, heads, u, row_slope, negative_slope, edge_scale, c)
+        ctx.meta = (num_dst, heads, row_slope, negative_slope, u is not None, c is not None, edge_scale is not None)
+        ctx.save_for_backward(q, d, att, edge_index, out, lse, *(t for t in (u, c, edge_scale) if t is not None))
         return out
 
     @staticmethod
     def backward(ctx, grad_out):
         q0, d0, att0, edge_index, out, lse, *rest = ctx.saved_tensors
-        num_dst, heads, row_slope, slope, has_u, has_ks = ctx.meta
+        num_dst, heads, row_slope, slope, has_u, has_c, has_ks = ctx.meta
         u0 = rest.pop(0) if has_u else None
+        c0 = rest.pop(0) if has_c else None
         ks0 = rest.pop(0) if has_ks else None
-        q, ldq, d, ldd, att, u, ks, edge_index, src_rows, plan, col, E, HC = _v1_operands(q0, d0, att0, edge_index, num_dst, heads, u0, ks0)
-        need_q, need_d, need_att, need_u = ctx.needs_input_grad[:4]
+        need_q, need_d, need_att, need_u, need_c = ctx.needs_input_grad[:5]
         tail = (None,) * 6
-        if E == 0 or num_dst == 0:
+        gq, d_d, d_att, d_c, src_rows, edge_index = _v1_backward(q0, d0, att0, u0, c0, ks0, edge_index, out, lse, grad_out, num_dst, heads,
+                                                                 row_slope, slope)
+        if gq is None:
             return (torch.zeros_like(q0) if need_q else None, torch.zeros_like(d0) if need_d else None,
-                    torch.zeros_like(att0) if need_att else None, torch.zeros_like(u0) if has_u and need_u else None) + tail
-        # the layouts autograd hands over, as _EdgeAttention.backward takes them
-        g = grad_out if grad_out.dim() == 2 and (grad_out.stride(1) == 1 or grad_out.size(1) == 1) else grad_out.contiguous()
-        g, ldg = _rows(g, "the output gradient", 1, HC, op="edge_attention_v1")
-        if g.size(0) > 1 and g.stride(0) == 0:
-            ldg = 0
-        d_d = torch.empty((num_dst, heads), dtype=q.dtype, device=q.device)
-        gq = torch.empty((E, HC), dtype=q.dtype, device=q.device)
-        d_att = torch.empty(HC, dtype=q.dtype, device=q.device)
-        L = _lib.load()
-        ws_bytes = L.gnnops_edge_attention_v1_backward_workspace_bytes(num_dst, heads, HC // heads)
-        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=q.device)
-        ptr = lambda t: t.data_ptr() if t is not None else None   # noqa: E731
-        with _on(q.device):
-            check(L.gnnops_edge_attention_v1_backward(q.data_ptr(), ldq, d.data_ptr(), ldd, att.data_ptr(), ptr(u), ptr(ks), out.data_ptr(), HC,
-                                                      lse.data_ptr(), g.data_ptr(), ldg, plan.rowptr.data_ptr(), plan.perm.data_ptr(),
-                                                      col.data_ptr(), d_d.data_ptr(), gq.data_ptr(), d_att.data_ptr(), num_dst, E, heads,
-                                                      HC // heads, int(row_slope is not None), float(row_slope or 0.0), slope,
-                                                      _dtype_code(q, "edge_attention_v1"), ws.data_ptr(), ws_bytes, _stream()),
-                  "edge_attention_v1_backward")
+                    torch.zeros_like(att0) if need_att else None, torch.zeros_like(u0) if has_u and need_u else None,
+                    torch.zeros_like(c0) if has_c and need_c else None) + tail
+        HC = att0.numel()
         d_q = None
         if need_q:
-            plan_src = get_plan(src_rows, q.size(0), owner=edge_index, tag=0)
+            plan_src = get_plan(src_rows, q0.size(0), owner=edge_index, tag=0)
             d_q = ops.scatter(gq, plan_src, 0, None, None, "sum")
             if q0.size(1) != HC:         # q was a column block wider than the H * C the pass reads
                 d_q = torch.nn.functional.pad(d_q, (0, q0.size(1) - HC))
         if need_d and d0.size(1) != heads:
             d_d = torch.nn.functional.pad(d_d, (0, d0.size(1) - heads))
-        return (d_q, d_d if need_d else None, d_att.view(att0.shape) if need_att else None, gq if has_u and need_u else None) + tail
+        return (d_q, d_d if need_d else None, d_att.view(att0.shape) if need_att else None, gq if has_u and need_u else None,
+                d_c if has_c and need_c else None) + tail
 
 
 def _dropout_scale(E, heads, p, dtype, device):
@@ -1115,12 +1268,18 @@ class GATConv(_Layer):
     x @ [W^T | fold(att_dst, W_dst)^T]: the per-destination score term d comes out of it as H more columns (att_dst folded into the
     weight, `_fold`), then one attention pass (`edge_attention_v1`), the mean over heads (concat=False) and the bias. Parameter names
     follow PyG 2.0.x (lin_src, lin_dst, att_src, att_dst, bias); parity unpinned. Self loops and the bipartite pair as GATv2Conv.
-    Attention dropout: a Bernoulli mask [E, H] drawn with torch, scaled by 1 / (1 - p), applied after the softmax (edge_scale)."""
+    Attention dropout: a Bernoulli mask [E, H] drawn with torch, scaled by 1 / (1 - p), applied after the softmax (edge_scale).
+    Edge features (edge_dim set; parameters lin_edge.weight and att_edge as PyG): the score gains att_edge . lin_edge(e_ij) per head.
+    att_edge is folded into lin_edge's weight exactly as att_dst is into lin_dst's, so the term is ONE product edge_attr @ [H, edge_dim]^T
+    (padded to 8 columns) whose [E, H] result the attention pass adds before the leaky ReLU (edge_score): no [E, H * C] tensor exists.
+    Self-loop attributes (fill_value) as GATv2Conv."""
 
-    def __init__(self, in_channels, out_channels, heads=1, concat=True, negative_slope=0.2, dropout=0.0, add_self_loops=True, bias=True):
+    def __init__(self, in_channels, out_channels, heads=1, concat=True, negative_slope=0.2, dropout=0.0, add_self_loops=True, bias=True,
+                 edge_dim=None, fill_value="mean"):
         super().__init__()
         self.in_channels, self.out_channels, self.heads, self.concat = in_channels, out_channels, heads, concat
         self.negative_slope, self.dropout, self.add_self_loops = negative_slope, dropout, add_self_loops
+        self.edge_dim, self.fill_value = edge_dim, _checked_fill_value(fill_value, "GATConv")
         if isinstance(in_channels, int):
             self.lin_src = torch.nn.Linear(in_channels, heads * out_channels, bias=False)
             self.lin_dst = self.lin_src
@@ -1132,12 +1291,19 @@ class GATConv(_Layer):
         self.bias = torch.nn.Parameter(torch.zeros(heads * out_channels if concat else out_channels)) if bias else None
         for w in (self.lin_src.weight, self.lin_dst.weight, self.att_src, self.att_dst):      # glorot, as PyG
             torch.nn.init.xavier_uniform_(w)
-        self._pk_both, self._pk_src, self._pk_dst = _Packed(), _Packed(), _Packed()
-        self._looped = None
+        if edge_dim is not None:
+            self.lin_edge = torch.nn.Linear(edge_dim, heads * out_channels, bias=False)
+            self.att_edge = torch.nn.Parameter(torch.empty(1, heads, out_channels))
+            torch.nn.init.xavier_uniform_(self.lin_edge.weight)
+            torch.nn.init.xavier_uniform_(self.att_edge)
+        self._pk_both, self._pk_src, self._pk_dst, self._pk_e = _Packed(), _Packed(), _Packed(), _Packed()
+        self._looped = self._kept = None
 
     _with_self_loops = GATv2Conv._with_self_loops
+    _kept_edges = GATv2Conv._kept_edges
+    _edge_rows = GATv2Conv._edge_rows
 
-    def forward(self, x, edge_index, size=None):
+    def forward(self, x, edge_index, edge_attr=None, size=None):
         H, C = self.heads, self.out_channels
         HC = H * C
         ws, wd = self.lin_src.weight, self.lin_dst.weight
@@ -1149,17 +1315,23 @@ class GATConv(_Layer):
             q = _dense(x_src.contiguous(), self._pk_src.get([ws], [(ws, None)]))
             d = _dense(x_dst.contiguous(), self._pk_dst.get([wd, self.att_dst], lambda: _pad8([(_fold(self.att_dst, wd, H), None)], wd)))[:, :H]
             n_dst = x_dst.size(0) if size is None else size[1]
+            rows = self._edge_rows(edge_attr, edge_index, n_dst, False)
         else:
             _require_gpu(x, edge_index)
             n_dst = x.size(0)
             qd = _dense(x.contiguous(), self._pk_both.get([ws, wd, self.att_dst], lambda: _pad8([(ws, None), (_fold(self.att_dst, wd, H), None)], ws)))
             q, d = qd[:, :HC], qd[:, HC:HC + H]
+            rows = self._edge_rows(edge_attr, edge_index, n_dst, self.add_self_loops)
             if self.add_self_loops:
                 edge_index = self._with_self_loops(edge_index, n_dst)
+        c = None
+        if rows is not None:            # c[e, h] = att_edge[h] . lin_edge(edge_attr)[e, h]: one product with the folded weight
+            we = self.lin_edge.weight
+            c = _edge_dense(rows, self._pk_e.get([we, self.att_edge], lambda: _pad8([(_fold(self.att_edge, we, H), None)], we)))[:, :H]
         scale = None
         if self.dropout > 0.0 and self.training:
             scale = _dropout_scale(edge_index.size(1), H, self.dropout, q.dtype, q.device)
-        out = edge_attention_v1(q, d, self.att_src, edge_index, n_dst, H, negative_slope=self.negative_slope, edge_scale=scale)
+        out = edge_attention_v1(q, d, self.att_src, edge_index, n_dst, H, negative_slope=self.negative_slope, edge_scale=scale, edge_score=c)
         if not self.concat:
             out = out.view(n_dst, H, C).mean(dim=1)
         return out if self.bias is None else out + self.bias
@@ -1168,7 +1340,10 @@ class GATConv(_Layer):
 class _EdgeLinear(torch.autograd.Function):
     """u = edge_attr @ weight_t for [E, edge_dim] edge features, edge_dim tiny. The backward of gnnops.autograd.matmul copies the
     transpose of its left operand, and that copy stops at 64 * 65535 rows; the transpose of ONE column is the same memory, so for
-    edge_dim = 1 (the reference's config) d weight_t = edge_attr.view(1, E) @ g needs no copy and no limit."""
+    edge_dim = 1 (the reference's config) d weight_t = edge_attr.view(1, E) @ g needs no copy and no limit. A wider edge_attr of more
+    rows than that is transposed and multiplied in row blocks of that size, the blocks' products added in float32 in their order."""
+
+    MAX_ROWS = 64 * 65535
 
     @staticmethod
     def forward(ctx, edge_attr, weight_t):
@@ -1185,9 +1360,21 @@ class _EdgeLinear(torch.autograd.Function):
         if ctx.needs_input_grad[0]:
             d_e = ops.matmul(g, transpose_contiguous(weight_t))
         if ctx.needs_input_grad[1]:
-            e_t = edge_attr.view(1, -1) if edge_attr.size(1) == 1 else transpose_contiguous(edge_attr)
-            d_w = ops.matmul(e_t, g)
+            if edge_attr.size(1) == 1 or edge_attr.size(0) <= _EdgeLinear.MAX_ROWS:
+                e_t = edge_attr.view(1, -1) if edge_attr.size(1) == 1 else transpose_contiguous(edge_attr)
+                d_w = ops.matmul(e_t, g)
+            else:
+                step = _EdgeLinear.MAX_ROWS
+                parts = [ops.matmul(transpose_contiguous(edge_attr[k:k + step]), g[k:k + step]).float() for k in range(0, edge_attr.size(0), step)]
+                d_w = sum(parts[1:], parts[0]).to(g.dtype)
         return d_e, d_w
+
+
+def _edge_dense(rows, packed):
+    """rows [E, edge_dim] @ the packed weight [edge_dim, W]: `_dense` for the one product of a layer whose left operand has a row per
+    EDGE (`_EdgeLinear`: no row limit in its backward)."""
+    weight_t = packed[0]
+    return _EdgeLinear.apply(rows, weight_t) if _wants_grad(rows, weight_t) else ops.matmul(rows, weight_t)
 
 
 class GATEConv(_Layer):
@@ -1195,8 +1382,7 @@ class GATEConv(_Layer):
     x_j' = leaky_relu(lin1([x_j, e_ji])),  alpha_ji = softmax_j(leaky_relu(att_l . x_j' + att_r . x_i)),  x'_i = lin2(sum_j alpha_ji x_j') + bias
     (both slopes 0.01). lin1 splits into its node and its edge columns: one product x @ [W1x^T | att_r^T] gives q and d, one product
     edge_attr @ W1e^T gives the per-edge rows u, one attention pass (`edge_attention_v1` with u and row_slope), and lin2 — linear —
-    is applied once to the aggregate instead of once per edge. No self loops. Attention dropout as GATConv. Training with
-    edge_dim > 1 on more than 64 * 65535 edges meets the row limit of the package's transpose copy (`_EdgeLinear`); edge_dim = 1 does not."""
+    is applied once to the aggregate instead of once per edge. No self loops. Attention dropout as GATConv."""
 
     def __init__(self, in_channels, out_channels, edge_dim, dropout=0.0):
         super().__init__()

@@ -626,6 +626,25 @@ int gnnops_edge_attention_backward(const void* q, int64_t ldq, const void* p, in
                                    int64_t E, int64_t H, int64_t C, float negative_slope, int dtype, void* workspace,
                                    size_t workspace_bytes, gnnops_stream_t stream);
 
+/* The same pass with a per-edge row in the score (GATv2Conv with edge features: u = lin_edge(edge_attr)):
+ *   z[e,h,c] = p[i,h,c] + q[j,h,c] + u[e,h,c]; s, lse and out as above — the message stays q[j,h,:], without u.
+ * u [E, H*C] is dense, in `dtype`, its rows the ORIGINAL edge ids: the row of sorted position k is perm[k] (perm NULL =
+ * identity: the edge list is already destination-sorted), at the 64-bit element offset (int64) id * H*C. u NULL = absent: the
+ * call is gnnops_edge_attention, and an all-zero u gives the same bits as that call. E == 0 or N == 0: u is not dereferenced.
+ * Backward: operands and workspace (gnnops_edge_attention_u_backward_workspace_bytes, the same size) as
+ *   gnnops_edge_attention_backward, and a second per-edge tensor gu [E, H*C] dense, row = original edge id, = d u
+ *   (gq[e] = a[e] * grad_out[i] + gu[e]). gu is required when u is given and E > 0, ignored otherwise. No atomics: two runs
+ *   give the same bits. */
+int gnnops_edge_attention_u(const void* q, int64_t ldq, const void* p, int64_t ldp, const void* att, const void* u,
+                            const int32_t* rowptr, const int32_t* perm, const int64_t* col, void* out, int64_t ldo, float* lse,
+                            int64_t N, int64_t E, int64_t H, int64_t C, float negative_slope, int dtype, gnnops_stream_t stream);
+size_t gnnops_edge_attention_u_backward_workspace_bytes(int64_t N, int64_t H, int64_t C);
+int gnnops_edge_attention_u_backward(const void* q, int64_t ldq, const void* p, int64_t ldp, const void* att, const void* u,
+                                     const void* out, int64_t ldo, const float* lse, const void* grad_out, int64_t ldg,
+                                     const int32_t* rowptr, const int32_t* perm, const int64_t* col, void* grad_p, void* gq,
+                                     void* gu, void* grad_att, int64_t N, int64_t E, int64_t H, int64_t C, float negative_slope,
+                                     int dtype, void* workspace, size_t workspace_bytes, gnnops_stream_t stream);
+
 /* The second member of the family (GATConv, the original GAT, and AttentiveFP's GATEConv): the score is a per-edge scalar plus
  * a per-destination scalar, the row may carry a per-edge part u and a leaky ReLU of its own, and a per-edge, per-head scale
  * (the attention dropout mask divided by 1 - p) enters the weighted sum only, never the denominator.
@@ -651,6 +670,28 @@ int gnnops_edge_attention_v1_backward(const void* q, int64_t ldq, const void* d,
                                       const int64_t* col, void* grad_d, void* gq, void* grad_att, int64_t N, int64_t E,
                                       int64_t H, int64_t C, int has_row_slope, float row_slope, float negative_slope, int dtype,
                                       void* workspace, size_t workspace_bytes, gnnops_stream_t stream);
+
+/* The same pass with a per-edge, per-head term in the pre-activation (GATConv with edge features: c[e,h] = att_edge[h] .
+ * lin_edge(edge_attr)[e,h,:], one tiny product with att_edge folded into the weight):
+ *   s[e,h] = leaky_relu(att[h,:] . r[e,h,:] + d[i,h] + c[e,h], negative_slope); the message is unchanged.
+ * c [E, H] is dense, in `dtype`, its rows the ORIGINAL edge ids, read through perm exactly as edge_scale is; NULL = absent: the
+ * call is gnnops_edge_attention_v1, and an all-zero c gives the same bits as that call. c and u together have no kernel
+ * instance (GNNOPS_EUNSUPPORTED). E == 0 or N == 0: c is not dereferenced.
+ * Backward: operands and workspace (gnnops_edge_attention_v1_c_backward_workspace_bytes, the same size) as
+ *   gnnops_edge_attention_v1_backward, and gc [E, H] dense, row = original edge id, = d c = d pre (one store per edge and
+ *   head, no atomics). gc is required when c is given and E > 0, ignored otherwise. */
+int gnnops_edge_attention_v1_c(const void* q, int64_t ldq, const void* d, int64_t ldd, const void* att, const void* u,
+                               const void* c, const void* edge_scale, const int32_t* rowptr, const int32_t* perm,
+                               const int64_t* col, void* out, int64_t ldo, float* lse, int64_t N, int64_t E, int64_t H, int64_t C,
+                               int has_row_slope, float row_slope, float negative_slope, int dtype, gnnops_stream_t stream);
+size_t gnnops_edge_attention_v1_c_backward_workspace_bytes(int64_t N, int64_t H, int64_t C);
+int gnnops_edge_attention_v1_c_backward(const void* q, int64_t ldq, const void* d, int64_t ldd, const void* att, const void* u,
+                                        const void* c, const void* edge_scale, const void* out, int64_t ldo, const float* lse,
+                                        const void* grad_out, int64_t ldg, const int32_t* rowptr, const int32_t* perm,
+                                        const int64_t* col, void* grad_d, void* gq, void* gc, void* grad_att, int64_t N,
+                                        int64_t E, int64_t H, int64_t C, int has_row_slope, float row_slope,
+                                        float negative_slope, int dtype, void* workspace, size_t workspace_bytes,
+                                        gnnops_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
  * The remaining ops of the reference's list (ops.txt:17-19, 29-41) - SURVEY.md 8(f) rank 4. Neither package is in the
