@@ -21,7 +21,7 @@ from .ops import (
     set_plan_cache,
 )
 # the differentiable front ends (they ARE the raw ops when nothing requires grad; gnnops.ops.* are the raw forms)
-from .autograd import (addmm, gather, index_select, matmul, scatter, scatter_add, scatter_max, scatter_mean, scatter_min,
+from .autograd import (addmm, gather, index_select, matmul, matmul_tn, scatter, scatter_add, scatter_max, scatter_mean, scatter_min,
                        scatter_mul, scatter_sum)
 from .sparse import (SpmmTiles, coalesce, coalesce_sparse_tensor, sddmm, sort, sparse_mm, spgemm_hash_max_row, spgemm_max_span, spmm, spmm_csr, spmm_t, spmm_tiles,
                      spspmm, transpose, transpose_contiguous)
@@ -39,7 +39,7 @@ __all__ = [
     "index_add_", "index_max", "index_select", "index_select_sum", "scatter", "scatter_add", "scatter_add_",
     "scatter_max", "scatter_mean", "scatter_min", "scatter_mul", "scatter_reduce_mul_", "scatter_sum",
     "set_plan_cache", "install", "uninstall", "installed", "coalesce", "coalesce_sparse_tensor", "sort", "sparse_mm",
-    "spmm", "spmm_csr", "spmm_tiles", "SpmmTiles", "spmm_t", "sddmm", "expand_rowptr", "spspmm", "spgemm_max_span", "spgemm_hash_max_row", "transpose", "transpose_contiguous", "addmm", "matmul", "index_add_select_sum", "segment_csr", "segment_coo", "gather_csr", "gather_coo",
+    "spmm", "spmm_csr", "spmm_tiles", "SpmmTiles", "spmm_t", "sddmm", "expand_rowptr", "spspmm", "spgemm_max_span", "spgemm_hash_max_row", "transpose", "transpose_contiguous", "addmm", "matmul", "matmul_tn", "index_add_select_sum", "segment_csr", "segment_coo", "gather_csr", "gather_coo",
     "rowptr_from_sorted", "scatter_softmax", "scatter_log_softmax", "scatter_logsumexp", "scatter_std", "autograd", "layers", "GATv2Conv", "edge_attention", "GATConv", "GATEConv", "AttentiveFP", "edge_attention_v1",
     "GCNConv", "TopKPooling", "GraphUNet", "gcn_propagate", "pool", "topk", "filter_adj", "remove_self_loops",
     "GATv2", "head_act_norm", "global_add_pool", "global_mean_pool", "global_max_pool",

@@ -142,6 +142,10 @@ SIGNATURES = {
     "gnnops_addmm_workspace_bytes": (_sz, [_i64, _i64, _i64]),
     "gnnops_addmm": (_ci, [_vp, _vp, _vp, _vp, _i64, _i64, _i64, _ci, _vp, _sz, _vp]),
     "gnnops_addmm_ld": (_ci, [_vp, _i64, _vp, _vp, _vp, _i64, _i64, _i64, _ci, _vp, _sz, _vp]),
+    "gnnops_gemm_tn_workspace_bytes": (_sz, [_i64, _i64, _i64, _ci]),
+    "gnnops_gemm_tn": (_ci, [_vp, _vp, _vp, _i64, _i64, _i64, _ci, _vp, _sz, _vp]),
+    "gnnops_gemm_tn_geometry": (_ci, [_i64, _i64, _i64, _ci, ctypes.POINTER(_i64), ctypes.POINTER(_i64), ctypes.POINTER(_i64),
+                                      ctypes.POINTER(_i64)]),
     "gnnops_fused_index_add_select_sum_workspace_bytes": (_sz, [_i64, _i64]),
     "gnnops_fused_index_add_select_sum": (_ci, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _ci, _vp, _sz, _vp]),
     "gnnops_segment_topk_max_len": (_i64, []),

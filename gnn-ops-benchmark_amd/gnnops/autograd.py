@@ -357,7 +357,9 @@ def scatter_max(src, index, dim=-1, out=None, dim_size=None):
 
 class _AddMM(torch.autograd.Function):
     """addmm / matmul on the MFMA kernels: d input = g (summed over broadcast dims), d mat1 = g @ mat2^T,
-    d mat2 = mat1^T @ g; the transposes are our tiled transpose copy, the products the same GEMM kernel."""
+    d mat2 = mat1^T @ g; the transposes are our tiled transpose copy, the products the same GEMM kernel — but for d mat2 where
+    ops.matmul_tn_preferred holds (mat1 tall): there ops.matmul_tn contracts the long dimension across the whole machine and
+    copies no transpose."""
 
     @staticmethod
     def forward(ctx, input, mat1, mat2):
@@ -379,7 +381,10 @@ class _AddMM(torch.autograd.Function):
         if ctx.needs_input_grad[1]:
             d1 = ops.matmul(g, transpose_contiguous(mat2))
         if ctx.needs_input_grad[2]:
-            d2 = ops.matmul(transpose_contiguous(mat1), g)
+            if ops.matmul_tn_preferred(mat1.size(0), mat1.size(1), g.size(1), g.dtype):
+                d2 = ops.matmul_tn(mat1, g)
+            else:
+                d2 = ops.matmul(transpose_contiguous(mat1), g)
         return d_in, d1, d2
 
 
@@ -393,6 +398,32 @@ def addmm(input, mat1, mat2, *, beta=1, alpha=1):
 
 def matmul(input, other):
     return addmm(None, input, other)
+
+
+class _MatMulTN(torch.autograd.Function):
+    """a^T @ b on the split-R kernel: d a = b @ g^T, d b = a @ g, both ordinary products on the GEMM kernels."""
+
+    @staticmethod
+    def forward(ctx, a, b):
+        ctx.save_for_backward(a, b)
+        return ops.matmul_tn(a, b)
+
+    @staticmethod
+    def backward(ctx, g):
+        from .sparse import transpose_contiguous
+
+        a, b = ctx.saved_tensors
+        g = g.contiguous()
+        d_a = d_b = None
+        if ctx.needs_input_grad[0]:
+            d_a = ops.matmul(b.contiguous(), transpose_contiguous(g))
+        if ctx.needs_input_grad[1]:
+            d_b = ops.matmul(a.contiguous(), g)
+        return d_a, d_b
+
+
+def matmul_tn(a, b):
+    return _MatMulTN.apply(a, b) if _needs_grad(a) or _needs_grad(b) else ops.matmul_tn(a, b)
 
 
 # ---- torch_spline_conv (gnnops/spatial.py; kernels csrc/spline.hip forward, csrc/spline_bw.hip backward) ----------------

@@ -1341,7 +1341,8 @@ class _EdgeLinear(torch.autograd.Function):
     """u = edge_attr @ weight_t for [E, edge_dim] edge features, edge_dim tiny. The backward of gnnops.autograd.matmul copies the
     transpose of its left operand, and that copy stops at 64 * 65535 rows; the transpose of ONE column is the same memory, so for
     edge_dim = 1 (the reference's config) d weight_t = edge_attr.view(1, E) @ g needs no copy and no limit. A wider edge_attr of more
-    rows than that is transposed and multiplied in row blocks of that size, the blocks' products added in float32 in their order."""
+    rows than that is transposed and multiplied in row blocks of that size, the blocks' products added in float32 in their order.
+    Where ops.matmul_tn_preferred holds, d weight_t = ops.matmul_tn(edge_attr, g): no transpose, no row limit, no blocks."""
 
     MAX_ROWS = 64 * 65535
 
@@ -1360,7 +1361,9 @@ class _EdgeLinear(torch.autograd.Function):
         if ctx.needs_input_grad[0]:
             d_e = ops.matmul(g, transpose_contiguous(weight_t))
         if ctx.needs_input_grad[1]:
-            if edge_attr.size(1) == 1 or edge_attr.size(0) <= _EdgeLinear.MAX_ROWS:
+            if edge_attr.size(1) != 1 and ops.matmul_tn_preferred(edge_attr.size(0), edge_attr.size(1), g.size(1), g.dtype):
+                d_w = ops.matmul_tn(edge_attr, g)
+            elif edge_attr.size(1) == 1 or edge_attr.size(0) <= _EdgeLinear.MAX_ROWS:
                 e_t = edge_attr.view(1, -1) if edge_attr.size(1) == 1 else transpose_contiguous(edge_attr)
                 d_w = ops.matmul(e_t, g)
             else:

@@ -852,3 +852,68 @@ def addmm(input, mat1, mat2, *, beta=1, alpha=1):
 def matmul(input, other):
     """torch.matmul(input, other) for 2-D float16 / bfloat16 matrices (benchmark_native_matmul.py:13-16)."""
     return addmm(None, input, other)
+
+
+def matmul_tn_geometry(R, P, Q, dtype):
+    """What gnnops_gemm_tn does at this shape: {'tile_p', 'tile_q', 'slab_rows', 'slabs', 'workspace_bytes'}. Host only."""
+    import ctypes
+
+    try:
+        dt = _DT[dtype]
+    except KeyError:
+        raise NotImplementedError(f"gnnops.matmul_tn: dtype {dtype} is not supported (float32/float16/bfloat16)")
+    L = _lib.load()
+    v = [ctypes.c_int64() for _ in range(4)]
+    check(L.gnnops_gemm_tn_geometry(R, P, Q, dt, *[ctypes.byref(x) for x in v]), "matmul_tn_geometry")
+    return {"tile_p": v[0].value, "tile_q": v[1].value, "slab_rows": v[2].value, "slabs": v[3].value,
+            "workspace_bytes": L.gnnops_gemm_tn_workspace_bytes(R, P, Q, dt)}
+
+
+def matmul_tn(a, b):
+    """a^T @ b for a [R, P] and b [R, Q] with R long (a weight gradient X^T @ G): csrc/gemm_tn.hip splits R over the machine
+    instead of handing all of it to the ceil(P/128) * ceil(Q/128) workgroups of the ordinary GEMM, and copies no transpose.
+    fp32 sums, one rounding; the same bits on every run and every device."""
+    _require_gpu(a, b)
+    _refuse_grad("matmul_tn", a, b)
+    if a.dim() != 2 or b.dim() != 2:
+        raise RuntimeError("matmul_tn: a and b must be matrices")
+    if a.size(0) != b.size(0):
+        raise RuntimeError(f"matmul_tn: a and b must have the same number of rows ({a.size(0)} and {b.size(0)})")
+    if a.dtype != b.dtype:
+        raise RuntimeError("matmul_tn: operands must have the same dtype")
+    if a.device != b.device:
+        raise RuntimeError("matmul_tn: operands must be on the same device")
+    dt = _dtype_code(a, "matmul_tn")
+    a, b = a.contiguous(), b.contiguous()
+    R, P = a.shape
+    Q = b.size(1)
+    out = torch.empty((P, Q), dtype=a.dtype, device=a.device)
+    L = _lib.load()
+    ws_bytes = L.gnnops_gemm_tn_workspace_bytes(R, P, Q, dt)
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=a.device) if ws_bytes else None
+    with _on(a.device):
+        rc = L.gnnops_gemm_tn(a.data_ptr(), b.data_ptr(), out.data_ptr(), R, P, Q, dt, ws.data_ptr() if ws is not None else None,
+                              ws_bytes, _stream())
+    check(rc, "matmul_tn")
+    return out
+
+
+def matmul_tn_preferred(R, P, Q, dtype):
+    """Route predicate of the weight gradients (autograd._AddMM.backward, conv._EdgeLinear.backward): True where
+    matmul_tn(x, g) replaces transpose_contiguous(x) followed by the ordinary GEMM. A pure function of the shape.
+
+    The rule rests on profiles/matmul_tn.txt (R in {10^4, 10^5, 10^6, 6 * 10^6} x (P, Q) in {(1, 128), (8, 8), (8, 128), (11, 2048),
+    (64, 256), (128, 1024), (512, 512)} x fp32 / fp16 / bf16): true only where the new route's median is below the old route's
+    minimum at the recorded point and at its recorded neighbours, inside the box the sweep covers (P <= 512, Q <= 2048, at most the
+    16 output tiles of 512 x 512 and 11 x 2048).
+      fp32    ahead at every point, 1.8 x (512 x 512 at R = 10^4: 0.49 against 0.88 ms) to 490 x (8 x 8 at 6 * 10^6: 1.0 against
+              493 ms): R >= 10^4, any widths of the box.
+      16-bit  ahead at every point from R = 10^5 (3.2 x to 255 x); at R = 10^4 ahead for (1, 128), (8, 8), (8, 128), (64, 256)
+              and (11, 2048) but behind for (128, 1024) (0.163 against 0.157 ms) and (512, 512) (0.166 against 0.128 ms), so below
+              R = 10^5 only P <= 64 and Q <= 256 — which leaves (11, 2048), whose neighbour (128, 1024) is behind, to the GEMM.
+    Nothing below R = 10^4 was measured: the GEMM keeps it. The train steps this reroutes are in profiles/gat_edge_after.txt."""
+    if not (R >= 10_000 and 0 < P <= 512 and 0 < Q <= 2048 and -(-P // 128) * -(-Q // 128) <= 16):
+        return False
+    if dtype == torch.float32 or R >= 100_000:
+        return True
+    return P <= 64 and Q <= 256

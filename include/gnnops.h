@@ -420,6 +420,22 @@ int gnnops_addmm_ld(const void* input, int64_t ld_input, const void* mat1, const
                     int64_t N, int64_t K, int dtype, void* workspace, size_t workspace_bytes, gnnops_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Transposed-left product split along the long dimension (csrc/gemm_tn.hip): out[P,Q] = a[R,P]^T @ b[R,Q], the weight
+ * gradient X^T @ G of a dense layer (R = nodes or edges, P and Q = the layer's widths). Contiguous row-major operands of one
+ * dtype; products are summed in fp32 and rounded once. Stage 1: one workgroup per (128 x 128 output tile, slab of slab_rows
+ * consecutive rows) writes an fp32 partial tile to the workspace; stage 2 adds each element's partials in ascending slab order.
+ * No atomics; the geometry depends on (R, P, Q, dtype) alone, so the same call gives the same bits on every device.
+ * slabs > 1 only while tiles * slabs <= 1024: the workspace never exceeds max(64 MiB, one fp32 output padded to whole tiles).
+ * R == 0 writes zeros; P * Q == 0 returns OK at once. Operands need no alignment beyond their element size.
+ * ------------------------------------------------------------------------------------------- */
+size_t gnnops_gemm_tn_workspace_bytes(int64_t R, int64_t P, int64_t Q, int dtype);   /* 0 for a negative size or an unknown dtype */
+int gnnops_gemm_tn(const void* a, const void* b, void* out, int64_t R, int64_t P, int64_t Q, int dtype,
+                   void* workspace, size_t workspace_bytes, gnnops_stream_t stream);
+/* What the launcher will do (host only): slabs == ceil(R / slab_rows); any output pointer may be NULL. */
+int gnnops_gemm_tn_geometry(int64_t R, int64_t P, int64_t Q, int dtype, int64_t* tile_p, int64_t* tile_q,
+                            int64_t* slab_rows, int64_t* slabs);
+
+/* ---------------------------------------------------------------------------------------------
  * Fused index_select(index_add(input, dim, index, other), dim, index).sum(dim)
  * (benchmark_fused_index_add_reduce.py:12-20). input [B,N,K], other [B,E,K], plan of index over N.
  * out_f32 [B,K] (fp32: the reference's fp16 result overflows at its own sizes). Nothing of size [B,N,K]
