@@ -23,7 +23,7 @@ from .ops import (
 # the differentiable front ends (they ARE the raw ops when nothing requires grad; gnnops.ops.* are the raw forms)
 from .autograd import (addmm, gather, index_select, matmul, matmul_tn, scatter, scatter_add, scatter_max, scatter_mean, scatter_min,
                        scatter_mul, scatter_sum)
-from .sparse import (SpmmTiles, coalesce, coalesce_sparse_tensor, sddmm, sort, sparse_mm, spgemm_hash_max_row, spgemm_max_span, spmm, spmm_csr, spmm_t, spmm_tiles,
+from .sparse import (SpmmTiles, coalesce, coalesce_sparse_tensor, sddmm, sort, sparse_mm, spgemm_hash_max_row, spgemm_max_span, spmm, spmm_csr, spmm_reduce, spmm_t, spmm_tiles,
                      spspmm, transpose, transpose_contiguous)
 from .segment import (expand_rowptr, gather_coo, gather_csr, rowptr_from_sorted, scatter_log_softmax, scatter_logsumexp, scatter_softmax,
                       scatter_std, segment_coo, segment_csr)
@@ -32,6 +32,7 @@ from .conv import (AttentiveFP, GATConv, GATEConv, GATv2, GATv2Conv, GCNConv, Gr
                    head_act_norm)
 from .pool import filter_adj, global_add_pool, global_max_pool, global_mean_pool, remove_self_loops, topk
 from . import pool
+from .sparse_tensor import SparseTensor
 from .aten import install, uninstall, installed
 
 __all__ = [
@@ -42,5 +43,5 @@ __all__ = [
     "spmm", "spmm_csr", "spmm_tiles", "SpmmTiles", "spmm_t", "sddmm", "expand_rowptr", "spspmm", "spgemm_max_span", "spgemm_hash_max_row", "transpose", "transpose_contiguous", "addmm", "matmul", "matmul_tn", "index_add_select_sum", "segment_csr", "segment_coo", "gather_csr", "gather_coo",
     "rowptr_from_sorted", "scatter_softmax", "scatter_log_softmax", "scatter_logsumexp", "scatter_std", "autograd", "layers", "GATv2Conv", "edge_attention", "GATConv", "GATEConv", "AttentiveFP", "edge_attention_v1",
     "GCNConv", "TopKPooling", "GraphUNet", "gcn_propagate", "pool", "topk", "filter_adj", "remove_self_loops",
-    "GATv2", "head_act_norm", "global_add_pool", "global_mean_pool", "global_max_pool",
+    "GATv2", "head_act_norm", "global_add_pool", "global_mean_pool", "global_max_pool", "spmm_reduce", "SparseTensor",
 ]

@@ -63,6 +63,8 @@ SIGNATURES = {
     "gnnops_spmm": (_ci, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _ci, _vp]),
     "gnnops_spmm_hubs": (_ci, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _ci, _vp, _sz, _vp]),
     "gnnops_spmm_tiled": (_ci, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _ci, _vp, _vp, _vp, _ci, _ci, _vp]),
+    "gnnops_spmm_reduce": (_ci, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _ci, _ci, _vp]),
+    "gnnops_spmm_reduce_grad_terms": (_ci, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _ci, _vp]),
     "gnnops_permute": (_ci, [_vp, _vp, _vp, _i64, _ci, _vp]),
     "gnnops_sort_workspace_bytes": (_sz, [_i64, _i64, _i64, _ci]),
     "gnnops_sort": (_ci, [_vp, _vp, _vp, _i64, _i64, _i64, _ci, _ci, _vp, _sz, _vp]),

@@ -295,6 +295,75 @@ def spmm_t(index, value, m, n, matrix):
     return _SpMM.apply(index, value, m, n, matrix, True)
 
 
+class _SpMMReduce(torch.autograd.Function):
+    """gnnops.spmm_reduce (CSR x dense, reduce = sum | mean | min | max), differentiable in value and matrix.
+      min / max   the gradient of out[i, k] goes to position arg[i, k] only:  d matrix[col[arg], k] += value[arg] * g[i, k],
+                  d value[e] = sum over the (i, k) with arg == e of matrix[col[e], k] * g[i, k].  One launch of
+                  gnnops_spmm_reduce_grad_terms forms both products per output element and names the row of d matrix, then two
+                  element scatter_add_ (ours: sorted by destination, no atomics) sum them; row n of d matrix and slot nnz of
+                  d value swallow the rows without nonzeros (arg == nnz), as _SegmentCSR.backward does with slot E.
+      sum / mean  the backward of _SpMM over the (row, col) index of the row order, for a mean on g / max(count, 1) (the count
+                  and the division in float32, one rounding).
+    With ``perm`` the value gradient is formed in row order and carried back to the caller's order by one more scatter_add_."""
+
+    @staticmethod
+    def forward(ctx, rowptr, col, value, matrix, reduce, perm, index):
+        from . import sparse
+
+        res = sparse._spmm_reduce_raw(rowptr, perm, col, value, matrix, reduce)
+        ctx.reduce, ctx.index = reduce, index
+        if reduce in ("min", "max"):
+            out, arg = res
+            ctx.save_for_backward(rowptr, col, value, matrix, perm, arg)
+            ctx.mark_non_differentiable(arg)
+            return out, arg
+        ctx.save_for_backward(rowptr, col, value, matrix, perm, None)
+        return res
+
+    @staticmethod
+    def backward(ctx, g, *_):
+        from . import segment, sparse
+
+        rowptr, col, value, matrix, perm, arg = ctx.saved_tensors
+        g = g.contiguous()
+        matrix = matrix.contiguous()
+        nnz, n, (m, D) = col.numel(), matrix.size(0), g.shape
+        want_value = value is not None and ctx.needs_input_grad[2]
+        d_value = d_matrix = None
+        if nnz == 0 or m * D == 0:
+            d_matrix = torch.zeros_like(matrix) if ctx.needs_input_grad[3] else None
+            d_value = torch.zeros_like(value) if want_value else None
+            return None, None, d_value, d_matrix, None, None, None
+        if ctx.reduce in ("min", "max"):
+            dst, to_mat, to_val = sparse._spmm_reduce_grad_terms(arg, g, perm, col.contiguous(), value.contiguous() if value is not None else None,
+                                                                 matrix, want_value)
+            if ctx.needs_input_grad[3]:
+                d_matrix = ops.scatter_add_(torch.zeros((n + 1, D), dtype=g.dtype, device=g.device), 0, dst, to_mat)[:n]
+            if want_value:
+                d_value = ops.scatter_add_(torch.zeros(nnz + 1, dtype=g.dtype, device=g.device), 0, arg.view(-1), to_val.view(-1))[:nnz]
+        else:
+            if ctx.reduce == "mean":
+                cnt = (rowptr[1:] - rowptr[:-1]).clamp(min=1).to(torch.float32)
+                g = (g / cnt.unsqueeze(1)).to(g.dtype)
+            index, val_csr = ctx.index, value
+            if perm is not None:
+                val_csr = sparse._permute(value.contiguous(), perm, nnz) if value is not None else None
+            if index is None:
+                col_csr = sparse._permute(col.contiguous(), perm, nnz) if perm is not None else col
+                index = torch.stack([segment.expand_rowptr(rowptr, nnz), col_csr])
+            if ctx.needs_input_grad[3]:
+                d_matrix = sparse._spmm_t_raw(index, val_csr, m, n, g)
+            if want_value:
+                d_value = sparse.sddmm(index[0], index[1], g, matrix)
+        if d_value is not None and perm is not None:     # row order -> the caller's order: perm is a permutation, every slot gets one term
+            d_value = ops.scatter_add_(torch.zeros(nnz, dtype=g.dtype, device=g.device), 0, perm[:nnz].to(torch.int64), d_value.contiguous())
+        return None, None, d_value, d_matrix, None, None, None
+
+
+def spmm_reduce(rowptr, col, value, matrix, reduce, perm=None, index=None):
+    return _SpMMReduce.apply(rowptr, col, value, matrix, reduce, perm, index)
+
+
 def composite(src, index, dim, dim_size, mode, eps):
     """Differentiable entry for the composite ops (used by gnnops.segment when src requires grad)."""
     return _Composite.apply(src, index, dim, dim_size, mode, eps)

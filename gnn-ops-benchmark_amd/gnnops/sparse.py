@@ -285,6 +285,91 @@ def _spmm_launch(rowptr, perm, col, value, matrix, m, dt, plan=None, owner=None,
     return out
 
 
+_SPMM_REDUCES = ("sum", "add", "mean", "min", "max")
+
+
+def spmm_reduce(rowptr, col, value, matrix, reduce="sum", perm=None, index=None):
+    """CSR x dense with a reduction over each row's nonzeros — torch_sparse's spmm_sum / spmm_mean / spmm_min / spmm_max
+    (csrc/spmm_reduce.hip). ``rowptr`` int32 / int64 [M + 1], ``col`` int64 [nnz], ``value`` [nnz] or None (all ones),
+    ``matrix`` [n, D] or [n].
+
+    ``"sum"`` / ``"add"``: the product of :func:`spmm_csr`. ``"mean"``: that sum divided by the row's number of nonzeros (at
+    least 1) — torch_sparse's rule, not the sum of the weights. ``"min"`` / ``"max"`` return ``(out, arg)``: the extreme of
+    ``value[e] * matrix[col[e], k]`` over the row and its position in the row-ordered storage (``rowptr[i] <= arg < rowptr[i + 1]``);
+    of equal products the smallest position wins; a row without nonzeros gives ``out = 0`` and ``arg = nnz``.
+
+    ``perm`` (int32 [nnz], optional): ``col`` and ``value`` are in another order and position ``j`` of the row order is entry
+    ``perm[j]`` of them (the plan of a COO row index); ``arg`` still counts in the row order.
+    Differentiable in ``value`` and ``matrix`` (gnnops/autograd.py). ``index``: the [2, nnz] (row, col) tensor of the same
+    matrix in row order, if the caller keeps one — the backward of sum / mean then finds its plan in the cache instead of
+    building the index and sorting it again."""
+    if reduce not in _SPMM_REDUCES:
+        raise ValueError(f"spmm_reduce: reduce must be one of {_SPMM_REDUCES}, got {reduce!r}")
+    reduce = "sum" if reduce == "add" else reduce
+    if matrix.dim() == 1:
+        res = spmm_reduce(rowptr, col, value, matrix.unsqueeze(-1), reduce, perm, index)
+        return (res[0].squeeze(-1), res[1].squeeze(-1)) if isinstance(res, tuple) else res.squeeze(-1)
+    if _needs_grad(value, matrix):
+        from . import autograd
+
+        return autograd.spmm_reduce(rowptr, col, value, matrix, reduce, perm, index)
+    return _spmm_reduce_raw(rowptr, perm, col, value, matrix, reduce)
+
+
+def _rowptr32(rowptr, what):
+    if rowptr.dtype == torch.int64:
+        return rowptr.to(torch.int32).contiguous()   # kernel ABI is int32 row pointers (nnz < 2^31)
+    if rowptr.dtype != torch.int32:
+        raise RuntimeError(f"{what}: rowptr must be int32 or int64")
+    return rowptr.contiguous()
+
+
+def _spmm_reduce_raw(rowptr, perm, col, value, matrix, reduce):
+    _require_gpu(rowptr, perm, col, value, matrix)
+    _check_index(col, "spmm_reduce")
+    if matrix.dim() != 2:
+        raise NotImplementedError("gnnops.spmm_reduce: matrix must be 1-D or 2-D")
+    if rowptr.dim() != 1 or rowptr.numel() < 1 or col.dim() != 1:
+        raise RuntimeError("spmm_reduce: rowptr must be [M + 1] and col [nnz]")
+    dt = _dtype_code(matrix, "spmm_reduce")
+    nnz = col.numel()
+    if value is not None and (value.dtype != matrix.dtype or value.dim() != 1 or value.numel() != nnz):
+        raise RuntimeError("spmm_reduce: value must be [nnz] and of the dtype of matrix")
+    if perm is not None and (perm.dtype != torch.int32 or perm.dim() != 1 or perm.numel() < nnz):
+        raise RuntimeError("spmm_reduce: perm must be int32 [nnz]")
+    rowptr, col, matrix = _rowptr32(rowptr, "spmm_reduce"), col.contiguous(), matrix.contiguous()
+    m, D = rowptr.numel() - 1, matrix.size(1)
+    if reduce == "sum":
+        return _spmm_launch(rowptr, perm.contiguous() if perm is not None else None, col, value, matrix, m, dt)
+    out = torch.empty((m, D), dtype=matrix.dtype, device=matrix.device)
+    arg = torch.empty((m, D), dtype=torch.int64, device=matrix.device) if reduce != "mean" else None
+    value_c = value.contiguous() if value is not None else None
+    perm_c = perm.contiguous() if perm is not None else None
+    with _on(matrix.device):
+        rc = _lib.load().gnnops_spmm_reduce(rowptr.data_ptr(), perm_c.data_ptr() if perm_c is not None else None, col.data_ptr(),
+                                            value_c.data_ptr() if value_c is not None else None, matrix.data_ptr(), out.data_ptr(),
+                                            arg.data_ptr() if arg is not None else None, m, D, nnz, matrix.size(0),
+                                            _lib.REDUCE_CODE[reduce], dt, _stream())
+    check(rc, "spmm_reduce")
+    return out if arg is None else (out, arg)
+
+
+def _spmm_reduce_grad_terms(arg, g, perm, col, value, matrix, want_value):
+    """(dst int64 [M, D], to_mat [M, D], to_val [M, D] or None) of gnnops_spmm_reduce_grad_terms (include/gnnops.h)."""
+    m, D = g.shape
+    dst = torch.empty((m, D), dtype=torch.int64, device=g.device)
+    to_mat = torch.empty_like(g)
+    to_val = torch.empty_like(g) if want_value else None
+    with _on(g.device):
+        rc = _lib.load().gnnops_spmm_reduce_grad_terms(arg.data_ptr(), g.data_ptr(), perm.data_ptr() if perm is not None else None,
+                                                       col.data_ptr(), value.data_ptr() if value is not None else None,
+                                                       matrix.data_ptr(), dst.data_ptr(), to_mat.data_ptr(),
+                                                       to_val.data_ptr() if to_val is not None else None, m, D, col.numel(),
+                                                       matrix.size(0), _dtype_code(g, "spmm_reduce"), _stream())
+    check(rc, "spmm_reduce_grad_terms")
+    return dst, to_mat, to_val
+
+
 def sparse_mm(mat_a, mat_b):
     """torch.sparse.mm: sparse COO [m,n] x dense [n,D] -> dense (benchmark_sparse_spmm.py:12-14);
     sparse x sparse -> coalesced sparse COO (benchmark_sparse_spspmm.py:12-14)."""

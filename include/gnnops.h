@@ -341,6 +341,29 @@ int gnnops_spmm_tiled(const int32_t* rowptr, const int64_t* col, const void* val
                       int64_t M, int64_t D, int64_t nnz, int dtype, const int32_t* tile_ptr, const int64_t* tile_cols,
                       const uint16_t* slot, int block_rows, int slots, gnnops_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * torch_sparse.matmul(SparseTensor, dense, reduce = "mean" | "min" | "max") (spmm_mean / spmm_min / spmm_max of
+ * torch-sparse 0.6.12). Operands as gnnops_spmm; reduce is GNNOPS_MEAN, GNNOPS_MIN or GNNOPS_MAX (the sum is gnnops_spmm).
+ *   min / max  out[i,k] = max_j value[e_j] * mat[col[e_j], k] over j in [rowptr[i], rowptr[i+1]),  e_j = perm ? perm[j] : j;
+ *              arg[i,k] (int64 [M, D], or NULL) = the winning j, a position in the row-ordered storage (never perm[j]).
+ *              fp32 products compared strictly: of equal products the smallest j wins. The winner is rounded once.
+ *   mean       the sum of gnnops_spmm (same order and arithmetic) divided in fp32 by max(rowptr[i+1] - rowptr[i], 1).
+ * A row without nonzeros: out = 0, arg = nnz. NaN products: see csrc/spmm_reduce.hip. No atomics: reproducible bits.
+ * Rows of more than 8192 nonzeros are walked by one lane group (correct, slow). nnz < 2^31 - 8.
+ * Allocates nothing and does not synchronise; one launch on `stream`.
+ * ------------------------------------------------------------------------------------------- */
+int gnnops_spmm_reduce(const int32_t* rowptr, const int32_t* perm, const int64_t* col, const void* value,
+                       const void* mat, void* out, int64_t* arg, int64_t M, int64_t D, int64_t nnz, int64_t mat_rows,
+                       int reduce, int dtype, gnnops_stream_t stream);
+/* The per-element half of the min / max backward, for g = d out [M, D] and a = arg[i,k], e = perm ? perm[a] : a:
+ *   dst[i,k] (int64) = col[e],  to_mat[i,k] = round(value[e] * g[i,k]),  to_val[i,k] = round(mat[col[e], k] * g[i,k]);
+ *   a outside [0, nnz) (a row without nonzeros) or col[e] outside [0, mat_rows): dst = mat_rows and both terms 0.
+ * to_val may be NULL (no value gradient wanted); value == NULL means all ones. d mat is then the scatter-add of to_mat
+ * by dst over mat_rows + 1 rows and d value (row order) the scatter-add of to_val by arg over nnz + 1 slots. */
+int gnnops_spmm_reduce_grad_terms(const int64_t* arg, const void* g, const int32_t* perm, const int64_t* col,
+                                  const void* value, const void* mat, int64_t* dst, void* to_mat, void* to_val,
+                                  int64_t M, int64_t D, int64_t nnz, int64_t mat_rows, int dtype, gnnops_stream_t stream);
+
 /* out[j] = in[perm[j]] (elements of 2, 4 or 8 bytes): materialises the CSR column / value arrays of a plan-ordered COO
  * operand once, so gnnops_spmm can be called with perm == NULL and stream them. */
 int gnnops_permute(const void* in, const int32_t* perm, void* out, int64_t n, int elem_bytes, gnnops_stream_t stream);
