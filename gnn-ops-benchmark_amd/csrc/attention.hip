@@ -814,7 +814,9 @@ inline int rows_of_partials(int64_t N, int H, int C) {
     return (int)(rows < 1 ? 1 : rows);
 }
 
-inline int max_vec_of(int es, std::initializer_list<std::pair<const void*, int64_t>> operands) {
+using Operands = std::initializer_list<std::pair<const void*, int64_t>>;   // (pointer, row pitch) of what a kernel reads or writes in pieces
+
+inline int max_vec_of(int es, Operands operands) {
     int max_vec = 16 / es;
     for (const auto& op : operands) {
         if (!op.first) continue;
@@ -823,34 +825,77 @@ inline int max_vec_of(int es, std::initializer_list<std::pair<const void*, int64
     return max_vec;
 }
 
-template <typename T, bool BW, bool HASU, int VEC, int NCH>
-void launch_kernel(const AttArgs& a, int grid, hipStream_t stream) {
-    if constexpr (BW) hipLaunchKernelGGL((attention_bwd_kernel<T, VEC, NCH, HASU>), dim3(grid), dim3(256), 0, stream, a);
-    else hipLaunchKernelGGL((attention_fwd_kernel<T, VEC, NCH, HASU>), dim3(grid), dim3(256), 0, stream, a);
-}
-
-template <typename T, bool BW, bool HASU, int VEC>
-void launch_nch(const AttArgs& a, int nch, int grid, hipStream_t stream) {
-    if (nch == 1) launch_kernel<T, BW, HASU, VEC, 1>(a, grid, stream);
-    else if (nch == 2) launch_kernel<T, BW, HASU, VEC, 2>(a, grid, stream);
-    else launch_kernel<T, BW, HASU, VEC, 4>(a, grid, stream);
-}
-
-template <typename T, bool BW, bool HASU>
-void launch_vec(const AttArgs& a, const Geometry& geo, int grid, hipStream_t stream) {
-    if (geo.nch == 128) return launch_kernel<T, BW, HASU, 1, 128>(a, grid, stream);
-    if constexpr (Elem<T>::VEC == 8) {
-        if (geo.vec == 8) return launch_nch<T, BW, HASU, 8>(a, geo.nch, grid, stream);
+// A family names its Args and launches its forward or backward kernel for one <T, VEC, NCH>; which of its compile-time flags
+// an operand turns on is the only choice a family makes itself.
+struct AttFamily {
+    using Args = AttArgs;
+    template <typename T, bool BW, int VEC, int NCH, bool HASU>
+    static void run(const Args& a, int grid, hipStream_t stream) {
+        if constexpr (BW) hipLaunchKernelGGL((attention_bwd_kernel<T, VEC, NCH, HASU>), dim3(grid), dim3(256), 0, stream, a);
+        else hipLaunchKernelGGL((attention_fwd_kernel<T, VEC, NCH, HASU>), dim3(grid), dim3(256), 0, stream, a);
     }
-    if (geo.vec == 4) return launch_nch<T, BW, HASU, 4>(a, geo.nch, grid, stream);
-    if (geo.vec == 2) return launch_nch<T, BW, HASU, 2>(a, geo.nch, grid, stream);
-    return launch_nch<T, BW, HASU, 1>(a, geo.nch, grid, stream);
+    template <typename T, bool BW, int VEC, int NCH>
+    static void launch(const Args& a, int grid, hipStream_t stream) {
+        if (a.u) run<T, BW, VEC, NCH, true>(a, grid, stream);
+        else run<T, BW, VEC, NCH, false>(a, grid, stream);
+    }
+};
+
+struct GateFamily {
+    using Args = GateArgs;
+    template <typename T, bool BW, int VEC, int NCH, bool HASU, bool HASC>
+    static void run(const Args& a, int grid, hipStream_t stream) {
+        if constexpr (BW) hipLaunchKernelGGL((gate_bwd_kernel<T, VEC, NCH, HASU, HASC>), dim3(grid), dim3(256), 0, stream, a);
+        else hipLaunchKernelGGL((gate_fwd_kernel<T, VEC, NCH, HASU, HASC>), dim3(grid), dim3(256), 0, stream, a);
+    }
+    // the instances with the per-edge score term c are those of GATConv(edge_dim): no per-edge row beside it
+    template <typename T, bool BW, int VEC, int NCH>
+    static void launch(const Args& a, int grid, hipStream_t stream) {
+        if (a.c) run<T, BW, VEC, NCH, false, true>(a, grid, stream);
+        else if (a.u) run<T, BW, VEC, NCH, true, false>(a, grid, stream);
+        else run<T, BW, VEC, NCH, false, false>(a, grid, stream);
+    }
+};
+
+template <typename F, typename T, bool BW, int VEC>
+void launch_pieces(const typename F::Args& a, int nch, int grid, hipStream_t stream) {
+    if (nch == 1) F::template launch<T, BW, VEC, 1>(a, grid, stream);
+    else if (nch == 2) F::template launch<T, BW, VEC, 2>(a, grid, stream);
+    else F::template launch<T, BW, VEC, 4>(a, grid, stream);
 }
 
-template <typename T, bool BW>
-void launch(const AttArgs& a, const Geometry& geo, int grid, hipStream_t stream) {
-    if (a.u) launch_vec<T, BW, true>(a, geo, grid, stream);
-    else launch_vec<T, BW, false>(a, geo, grid, stream);
+template <typename F, typename T, bool BW>
+void launch_typed(const typename F::Args& a, const Geometry& geo, int grid, hipStream_t stream) {
+    if (geo.nch == 128) return F::template launch<T, BW, 1, 128>(a, grid, stream);
+    if constexpr (Elem<T>::VEC == 8) {
+        if (geo.vec == 8) return launch_pieces<F, T, BW, 8>(a, geo.nch, grid, stream);
+    }
+    if (geo.vec == 4) return launch_pieces<F, T, BW, 4>(a, geo.nch, grid, stream);
+    if (geo.vec == 2) return launch_pieces<F, T, BW, 2>(a, geo.nch, grid, stream);
+    return launch_pieces<F, T, BW, 1>(a, geo.nch, grid, stream);
+}
+
+// dtype was checked by check_sizes
+template <typename F, bool BW>
+void launch(const typename F::Args& a, const Geometry& geo, int grid, int dtype, hipStream_t stream) {
+    switch (dtype) {
+        case GNNOPS_F32: launch_typed<F, float, BW>(a, geo, grid, stream); break;
+        case GNNOPS_F16: launch_typed<F, __half, BW>(a, geo, grid, stream); break;
+        default: launch_typed<F, __hip_bfloat16, BW>(a, geo, grid, stream); break;
+    }
+}
+
+template <typename T>
+void launch_datt_typed(const float* partial, int rows, int HC, void* grad_att, hipStream_t stream) {
+    hipLaunchKernelGGL(attention_datt_kernel<T>, dim3((unsigned)gnnops_cdiv(HC, 256)), dim3(256), 0, stream, partial, rows, HC, (T*)grad_att);
+}
+
+void launch_datt(const float* partial, int rows, int HC, void* grad_att, int dtype, hipStream_t stream) {
+    switch (dtype) {
+        case GNNOPS_F32: launch_datt_typed<float>(partial, rows, HC, grad_att, stream); break;
+        case GNNOPS_F16: launch_datt_typed<__half>(partial, rows, HC, grad_att, stream); break;
+        default: launch_datt_typed<__hip_bfloat16>(partial, rows, HC, grad_att, stream); break;
+    }
 }
 
 int check_sizes(const char* what, int64_t N, int64_t E, int64_t H, int64_t C, int64_t ldq, int64_t ldp, int dtype, int* es) {
@@ -868,244 +913,139 @@ int check_sizes(const char* what, int64_t N, int64_t E, int64_t H, int64_t C, in
     return GNNOPS_OK;
 }
 
-template <typename T, bool BW, bool HASU, bool HASC, int VEC, int NCH>
-void gate_launch_kernel(const GateArgs& a, int grid, hipStream_t stream) {
-    if constexpr (BW) hipLaunchKernelGGL((gate_bwd_kernel<T, VEC, NCH, HASU, HASC>), dim3(grid), dim3(256), 0, stream, a);
-    else hipLaunchKernelGGL((gate_fwd_kernel<T, VEC, NCH, HASU, HASC>), dim3(grid), dim3(256), 0, stream, a);
+struct Launch { Geometry geo; int rows, grid, nwaves; };   // grid == 0: a valid call with nothing to launch
+
+// What the two forward entry points check and choose before they launch. The caller says what only it knows: its name, whether
+// its other pitches hold a row, whether it was given the u and c that no instance takes together, whether the pointers it needs
+// are there, and the operands that bound the piece width. ldp: the pitch of p, or H * C for the family without p.
+int forward_prologue(const char* what, int64_t N, int64_t E, int64_t H, int64_t C, int64_t ldq, int64_t ldp, bool pitches, bool u_and_c,
+                     bool pointers, int dtype, Operands operands, Launch* l) {
+    int es = 0;
+    const int rc = check_sizes(what, N, E, H, C, ldq, ldp, dtype, &es);
+    if (rc != GNNOPS_OK) return rc;
+    GNNOPS_REQUIRE(pitches, GNNOPS_EINVAL, "%s: a row pitch is shorter than the row", what);
+    GNNOPS_REQUIRE(!u_and_c, GNNOPS_EUNSUPPORTED, "%s: a per-edge row u and a per-edge score term c together have no kernel instance", what);
+    if (N == 0) return GNNOPS_OK;
+    GNNOPS_REQUIRE(pointers, GNNOPS_EINVAL, "%s: null pointer", what);
+    l->geo = geometry((int)H, (int)C, max_vec_of(es, operands), es);
+    l->grid = gnnops_grid_cap(gnnops_cdiv(N * l->geo.hblocks, 4), 256 * 32);
+    l->nwaves = l->grid * 4;
+    return GNNOPS_OK;
 }
 
-template <typename T, bool BW, bool HASU, bool HASC, int VEC>
-void gate_launch_nch(const GateArgs& a, int nch, int grid, hipStream_t stream) {
-    if (nch == 1) gate_launch_kernel<T, BW, HASU, HASC, VEC, 1>(a, grid, stream);
-    else if (nch == 2) gate_launch_kernel<T, BW, HASU, HASC, VEC, 2>(a, grid, stream);
-    else gate_launch_kernel<T, BW, HASU, HASC, VEC, 4>(a, grid, stream);
-}
-
-template <typename T, bool BW, bool HASU, bool HASC>
-void gate_launch_vec(const GateArgs& a, const Geometry& geo, int grid, hipStream_t stream) {
-    if (geo.nch == 128) return gate_launch_kernel<T, BW, HASU, HASC, 1, 128>(a, grid, stream);
-    if constexpr (Elem<T>::VEC == 8) {
-        if (geo.vec == 8) return gate_launch_nch<T, BW, HASU, HASC, 8>(a, geo.nch, grid, stream);
-    }
-    if (geo.vec == 4) return gate_launch_nch<T, BW, HASU, HASC, 4>(a, geo.nch, grid, stream);
-    if (geo.vec == 2) return gate_launch_nch<T, BW, HASU, HASC, 2>(a, geo.nch, grid, stream);
-    return gate_launch_nch<T, BW, HASU, HASC, 1>(a, geo.nch, grid, stream);
-}
-
-// the instances with the per-edge score term c are those of GATConv(edge_dim): no per-edge row beside it
-template <typename T, bool BW>
-void gate_launch_type(const GateArgs& a, const Geometry& geo, int grid, hipStream_t stream) {
-    if (a.c) gate_launch_vec<T, BW, false, true>(a, geo, grid, stream);
-    else if (a.u) gate_launch_vec<T, BW, true, false>(a, geo, grid, stream);
-    else gate_launch_vec<T, BW, false, false>(a, geo, grid, stream);
-}
-
-template <bool BW>
-void gate_launch(const GateArgs& a, const Geometry& geo, int grid, int dtype, hipStream_t stream) {
-    switch (dtype) {
-        case GNNOPS_F32: gate_launch_type<float, BW>(a, geo, grid, stream); break;
-        case GNNOPS_F16: gate_launch_type<__half, BW>(a, geo, grid, stream); break;
-        default: gate_launch_type<__hip_bfloat16, BW>(a, geo, grid, stream); break;
-    }
+// The same for the two backward entry points. orphan: the name of a per-edge operand given without a place for its gradient, or
+// null. One wave per (row of d att partials, head block).
+int backward_prologue(const char* what, int64_t N, int64_t E, int64_t H, int64_t C, int64_t ldq, int64_t ldp, bool pitches, bool u_and_c,
+                      const void* grad_att, bool pointers, const char* orphan, const void* workspace, size_t workspace_bytes, int dtype,
+                      Operands operands, Launch* l) {
+    int es = 0;
+    const int rc = check_sizes(what, N, E, H, C, ldq, ldp, dtype, &es);
+    if (rc != GNNOPS_OK) return rc;
+    GNNOPS_REQUIRE(pitches, GNNOPS_EINVAL, "%s: a row pitch is shorter than the row", what);
+    GNNOPS_REQUIRE(grad_att, GNNOPS_EINVAL, "%s: null pointer", what);
+    GNNOPS_REQUIRE(!u_and_c, GNNOPS_EUNSUPPORTED, "%s: a per-edge row u and a per-edge score term c together have no kernel instance", what);
+    if (N == 0) return GNNOPS_OK;   // no destination: nothing is written
+    GNNOPS_REQUIRE(pointers, GNNOPS_EINVAL, "%s: null pointer", what);
+    GNNOPS_REQUIRE(!orphan, GNNOPS_EINVAL, "%s: %s without a place for its gradient", what, orphan);
+    const size_t need = gnnops_edge_attention_backward_workspace_bytes(N, H, C);
+    GNNOPS_REQUIRE(workspace && workspace_bytes >= need && (uintptr_t)workspace % 16 == 0, GNNOPS_EWORKSPACE, "%s: workspace %zu < %zu",
+                   what, workspace_bytes, need);
+    l->geo = geometry((int)H, (int)C, max_vec_of(es, operands), es);
+    l->rows = rows_of_partials(N, (int)H, (int)C);
+    l->nwaves = l->rows * l->geo.hblocks;
+    l->grid = (int)gnnops_cdiv(l->nwaves, 4);
+    return GNNOPS_OK;
 }
 
 }  // namespace
-
-extern "C" int gnnops_edge_attention_u(const void* q, int64_t ldq, const void* p, int64_t ldp, const void* att, const void* u,
-                                       const int32_t* rowptr, const int32_t* perm, const int64_t* col, void* out, int64_t ldo,
-                                       float* lse, int64_t N, int64_t E, int64_t H, int64_t C, float negative_slope, int dtype,
-                                       gnnops_stream_t s) {
-    int es = 0;
-    const int rc = check_sizes("edge_attention", N, E, H, C, ldq, ldp, dtype, &es);
-    if (rc != GNNOPS_OK) return rc;
-    GNNOPS_REQUIRE(ldo >= H * C, GNNOPS_EINVAL, "edge_attention: a row pitch is shorter than the row");
-    if (N == 0) return GNNOPS_OK;
-    GNNOPS_REQUIRE(rowptr && out && lse && p && att && (E == 0 || (q && col)), GNNOPS_EINVAL, "edge_attention: null pointer");
-    if (E == 0) u = nullptr;   // no edge: u is never read
-    const int max_vec = max_vec_of(es, {{q, ldq}, {p, ldp}, {att, 0}, {u, H * C}, {out, ldo}});
-    const Geometry geo = geometry((int)H, (int)C, max_vec, es);
-    AttArgs a{};
-    a.q = q; a.p = p; a.att = att; a.u = u; a.rowptr = rowptr; a.perm = perm; a.col = col; a.out = out; a.lse = lse;
-    a.N = N; a.ldq = ldq; a.ldp = ldp; a.ldo = ldo; a.H = (int)H; a.C = (int)C; a.slope = negative_slope;
-    a.gshift = geo.gshift; a.hblocks = geo.hblocks;
-    const int grid = gnnops_grid_cap(gnnops_cdiv(N * geo.hblocks, 4), 256 * 32);
-    a.nwaves = grid * 4;
-    hipStream_t stream = (hipStream_t)s;
-    switch (dtype) {
-        case GNNOPS_F32: launch<float, false>(a, geo, grid, stream); break;
-        case GNNOPS_F16: launch<__half, false>(a, geo, grid, stream); break;
-        default: launch<__hip_bfloat16, false>(a, geo, grid, stream); break;
-    }
-    return gnnops_check_launch("edge_attention");
-}
-
-extern "C" int gnnops_edge_attention(const void* q, int64_t ldq, const void* p, int64_t ldp, const void* att, const int32_t* rowptr,
-                                     const int64_t* col, void* out, int64_t ldo, float* lse, int64_t N, int64_t E, int64_t H,
-                                     int64_t C, float negative_slope, int dtype, gnnops_stream_t s) {
-    return gnnops_edge_attention_u(q, ldq, p, ldp, att, nullptr, rowptr, nullptr, col, out, ldo, lse, N, E, H, C, negative_slope, dtype, s);
-}
 
 extern "C" size_t gnnops_edge_attention_backward_workspace_bytes(int64_t N, int64_t H, int64_t C) {
     if (N <= 0 || H < 1 || C < 1 || H * C > 8192) return 0;
     return (size_t)rows_of_partials(N, (int)H, (int)C) * (size_t)(H * C) * sizeof(float);
 }
 
-extern "C" size_t gnnops_edge_attention_u_backward_workspace_bytes(int64_t N, int64_t H, int64_t C) {
-    return gnnops_edge_attention_backward_workspace_bytes(N, H, C);
+extern "C" int gnnops_edge_attention(const void* q, int64_t ldq, const void* p, int64_t ldp, const void* att, const void* u,
+                                     const int32_t* rowptr, const int32_t* perm, const int64_t* col, void* out, int64_t ldo, float* lse,
+                                     int64_t N, int64_t E, int64_t H, int64_t C, float negative_slope, int dtype, gnnops_stream_t s) {
+    if (E == 0) u = nullptr;   // no edge: u is never read
+    Launch l{};
+    const int rc = forward_prologue("edge_attention", N, E, H, C, ldq, ldp, ldo >= H * C, false,
+                                    rowptr && out && lse && p && att && (E == 0 || (q && col)), dtype,
+                                    {{q, ldq}, {p, ldp}, {att, 0}, {u, H * C}, {out, ldo}}, &l);
+    if (rc != GNNOPS_OK || !l.grid) return rc;
+    AttArgs a{};
+    a.q = q; a.p = p; a.att = att; a.u = u; a.rowptr = rowptr; a.perm = perm; a.col = col; a.out = out; a.lse = lse;
+    a.N = N; a.ldq = ldq; a.ldp = ldp; a.ldo = ldo; a.H = (int)H; a.C = (int)C; a.slope = negative_slope;
+    a.gshift = l.geo.gshift; a.hblocks = l.geo.hblocks; a.nwaves = l.nwaves;
+    launch<AttFamily, false>(a, l.geo, l.grid, dtype, (hipStream_t)s);
+    return gnnops_check_launch("edge_attention");
 }
 
-extern "C" int gnnops_edge_attention_u_backward(const void* q, int64_t ldq, const void* p, int64_t ldp, const void* att, const void* u,
-                                                const void* out, int64_t ldo, const float* lse, const void* grad_out, int64_t ldg,
-                                                const int32_t* rowptr, const int32_t* perm, const int64_t* col, void* grad_p,
-                                                void* gq, void* gu, void* grad_att, int64_t N, int64_t E, int64_t H, int64_t C,
-                                                float negative_slope, int dtype, void* workspace, size_t workspace_bytes,
-                                                gnnops_stream_t s) {
-    int es = 0;
-    const int rc = check_sizes("edge_attention_backward", N, E, H, C, ldq, ldp, dtype, &es);
-    if (rc != GNNOPS_OK) return rc;
-    GNNOPS_REQUIRE(ldo >= H * C && (ldg >= H * C || ldg == 0), GNNOPS_EINVAL, "edge_attention_backward: a row pitch is shorter than the row");
-    GNNOPS_REQUIRE(grad_att, GNNOPS_EINVAL, "edge_attention_backward: null pointer");
-    hipStream_t stream = (hipStream_t)s;
-    const int HC = (int)(H * C);
-    if (N == 0) return GNNOPS_OK;   // no destination: nothing is written
-    GNNOPS_REQUIRE(rowptr && out && lse && p && att && grad_out && grad_p && (E == 0 || (q && col && gq)), GNNOPS_EINVAL,
-                   "edge_attention_backward: null pointer");
-    if (E == 0) u = nullptr;        // no edge: u is never read, gu never written
-    GNNOPS_REQUIRE(!u || gu, GNNOPS_EINVAL, "edge_attention_backward: u without a place for its gradient");
-    const size_t need = gnnops_edge_attention_backward_workspace_bytes(N, H, C);
-    GNNOPS_REQUIRE(workspace && workspace_bytes >= need && (uintptr_t)workspace % 16 == 0, GNNOPS_EWORKSPACE,
-                   "edge_attention_backward: workspace %zu < %zu", workspace_bytes, need);
-    const int max_vec = max_vec_of(es, {{q, ldq}, {p, ldp}, {att, 0}, {out, ldo}, {grad_out, ldg}, {grad_p, HC}, {gq, HC}, {u, HC},
-                                        {u ? gu : nullptr, HC}});
-    const Geometry geo = geometry((int)H, (int)C, max_vec, es);
-    const int rows = rows_of_partials(N, (int)H, (int)C);
+extern "C" int gnnops_edge_attention_backward(const void* q, int64_t ldq, const void* p, int64_t ldp, const void* att, const void* u,
+                                              const void* out, int64_t ldo, const float* lse, const void* grad_out, int64_t ldg,
+                                              const int32_t* rowptr, const int32_t* perm, const int64_t* col, void* grad_p, void* gq,
+                                              void* gu, void* grad_att, int64_t N, int64_t E, int64_t H, int64_t C, float negative_slope,
+                                              int dtype, void* workspace, size_t workspace_bytes, gnnops_stream_t s) {
+    if (E == 0) u = nullptr;   // no edge: u is never read, gu never written
+    Launch l{};
+    const int rc = backward_prologue("edge_attention_backward", N, E, H, C, ldq, ldp, ldo >= H * C && (ldg >= H * C || ldg == 0), false, grad_att,
+                                     rowptr && out && lse && p && att && grad_out && grad_p && (E == 0 || (q && col && gq)),
+                                     u && !gu ? "u" : nullptr, workspace, workspace_bytes, dtype,
+                                     {{q, ldq}, {p, ldp}, {att, 0}, {out, ldo}, {grad_out, ldg}, {grad_p, H * C}, {gq, H * C}, {u, H * C},
+                                      {u ? gu : nullptr, H * C}}, &l);
+    if (rc != GNNOPS_OK || !l.grid) return rc;
     AttArgs a{};
     a.q = q; a.p = p; a.att = att; a.u = u; a.g = grad_out; a.o = out; a.rowptr = rowptr; a.perm = perm; a.col = col;
     a.dp = grad_p; a.gq = gq; a.gu = gu; a.lse = const_cast<float*>(lse); a.partial = (float*)workspace;
     a.N = N; a.ldq = ldq; a.ldp = ldp; a.ldo = ldo; a.ldg = ldg; a.H = (int)H; a.C = (int)C; a.slope = negative_slope;
-    a.gshift = geo.gshift; a.hblocks = geo.hblocks;
-    a.nwaves = rows * geo.hblocks;
-    const int grid = (int)gnnops_cdiv(a.nwaves, 4);
-    switch (dtype) {
-        case GNNOPS_F32: launch<float, true>(a, geo, grid, stream); break;
-        case GNNOPS_F16: launch<__half, true>(a, geo, grid, stream); break;
-        default: launch<__hip_bfloat16, true>(a, geo, grid, stream); break;
-    }
-    const dim3 dgrid((unsigned)gnnops_cdiv(HC, 256));
-    switch (dtype) {
-        case GNNOPS_F32: hipLaunchKernelGGL(attention_datt_kernel<float>, dgrid, dim3(256), 0, stream, a.partial, rows, HC, (float*)grad_att); break;
-        case GNNOPS_F16: hipLaunchKernelGGL(attention_datt_kernel<__half>, dgrid, dim3(256), 0, stream, a.partial, rows, HC, (__half*)grad_att); break;
-        default: hipLaunchKernelGGL(attention_datt_kernel<__hip_bfloat16>, dgrid, dim3(256), 0, stream, a.partial, rows, HC, (__hip_bfloat16*)grad_att); break;
-    }
+    a.gshift = l.geo.gshift; a.hblocks = l.geo.hblocks; a.nwaves = l.nwaves;
+    launch<AttFamily, true>(a, l.geo, l.grid, dtype, (hipStream_t)s);
+    launch_datt(a.partial, l.rows, (int)(H * C), grad_att, dtype, (hipStream_t)s);
     return gnnops_check_launch("edge_attention_backward");
 }
 
-extern "C" int gnnops_edge_attention_backward(const void* q, int64_t ldq, const void* p, int64_t ldp, const void* att,
-                                              const void* out, int64_t ldo, const float* lse, const void* grad_out, int64_t ldg,
-                                              const int32_t* rowptr, const int32_t* perm, const int64_t* col, void* grad_p,
-                                              void* gq, void* grad_att, int64_t N, int64_t E, int64_t H, int64_t C,
-                                              float negative_slope, int dtype, void* workspace, size_t workspace_bytes,
-                                              gnnops_stream_t s) {
-    return gnnops_edge_attention_u_backward(q, ldq, p, ldp, att, nullptr, out, ldo, lse, grad_out, ldg, rowptr, perm, col, grad_p, gq,
-                                            nullptr, grad_att, N, E, H, C, negative_slope, dtype, workspace, workspace_bytes, s);
-}
-
-extern "C" int gnnops_edge_attention_v1_c(const void* q, int64_t ldq, const void* d, int64_t ldd, const void* att, const void* u,
-                                          const void* c, const void* edge_scale, const int32_t* rowptr, const int32_t* perm,
-                                          const int64_t* col, void* out, int64_t ldo, float* lse, int64_t N, int64_t E, int64_t H,
-                                          int64_t C, int has_row_slope, float row_slope, float negative_slope, int dtype,
-                                          gnnops_stream_t s) {
-    int es = 0;
-    const int rc = check_sizes("edge_attention_v1", N, E, H, C, ldq, H * C, dtype, &es);
-    if (rc != GNNOPS_OK) return rc;
-    GNNOPS_REQUIRE(ldo >= H * C && ldd >= H, GNNOPS_EINVAL, "edge_attention_v1: a row pitch is shorter than the row");
-    GNNOPS_REQUIRE(!(u && c), GNNOPS_EUNSUPPORTED, "edge_attention_v1: a per-edge row u and a per-edge score term c together have no kernel instance");
-    if (N == 0) return GNNOPS_OK;
-    GNNOPS_REQUIRE(rowptr && out && lse && d && att && (E == 0 || (q && col)), GNNOPS_EINVAL, "edge_attention_v1: null pointer");
-    const int max_vec = max_vec_of(es, {{q, ldq}, {att, 0}, {u, H * C}, {out, ldo}});
-    const Geometry geo = geometry((int)H, (int)C, max_vec, es);
+extern "C" int gnnops_edge_attention_v1(const void* q, int64_t ldq, const void* d, int64_t ldd, const void* att, const void* u,
+                                        const void* c, const void* edge_scale, const int32_t* rowptr, const int32_t* perm,
+                                        const int64_t* col, void* out, int64_t ldo, float* lse, int64_t N, int64_t E, int64_t H, int64_t C,
+                                        int has_row_slope, float row_slope, float negative_slope, int dtype, gnnops_stream_t s) {
+    Launch l{};
+    const int rc = forward_prologue("edge_attention_v1", N, E, H, C, ldq, H * C, ldo >= H * C && ldd >= H, u && c,
+                                    rowptr && out && lse && d && att && (E == 0 || (q && col)), dtype,
+                                    {{q, ldq}, {att, 0}, {u, H * C}, {out, ldo}}, &l);
+    if (rc != GNNOPS_OK || !l.grid) return rc;
     GateArgs a{};
     a.q = q; a.d = d; a.att = att; a.u = E ? u : nullptr; a.c = E ? c : nullptr; a.ks = E ? edge_scale : nullptr;
     a.rowptr = rowptr; a.perm = perm; a.col = col;
     a.out = out; a.lse = lse;
     a.N = N; a.ldq = ldq; a.ldd = ldd; a.ldo = ldo; a.H = (int)H; a.C = (int)C;
     a.slope = negative_slope; a.row_slope = has_row_slope ? row_slope : 1.f;
-    a.gshift = geo.gshift; a.hblocks = geo.hblocks;
-    const int grid = gnnops_grid_cap(gnnops_cdiv(N * geo.hblocks, 4), 256 * 32);
-    a.nwaves = grid * 4;
-    gate_launch<false>(a, geo, grid, dtype, (hipStream_t)s);
+    a.gshift = l.geo.gshift; a.hblocks = l.geo.hblocks; a.nwaves = l.nwaves;
+    launch<GateFamily, false>(a, l.geo, l.grid, dtype, (hipStream_t)s);
     return gnnops_check_launch("edge_attention_v1");
 }
 
-extern "C" int gnnops_edge_attention_v1(const void* q, int64_t ldq, const void* d, int64_t ldd, const void* att, const void* u,
-                                        const void* edge_scale, const int32_t* rowptr, const int32_t* perm, const int64_t* col,
-                                        void* out, int64_t ldo, float* lse, int64_t N, int64_t E, int64_t H, int64_t C,
-                                        int has_row_slope, float row_slope, float negative_slope, int dtype, gnnops_stream_t s) {
-    return gnnops_edge_attention_v1_c(q, ldq, d, ldd, att, u, nullptr, edge_scale, rowptr, perm, col, out, ldo, lse, N, E, H, C,
-                                      has_row_slope, row_slope, negative_slope, dtype, s);
-}
-
-extern "C" size_t gnnops_edge_attention_v1_backward_workspace_bytes(int64_t N, int64_t H, int64_t C) {
-    return gnnops_edge_attention_backward_workspace_bytes(N, H, C);
-}
-
-extern "C" size_t gnnops_edge_attention_v1_c_backward_workspace_bytes(int64_t N, int64_t H, int64_t C) {
-    return gnnops_edge_attention_backward_workspace_bytes(N, H, C);
-}
-
-extern "C" int gnnops_edge_attention_v1_c_backward(const void* q, int64_t ldq, const void* d, int64_t ldd, const void* att, const void* u,
-                                                   const void* c, const void* edge_scale, const void* out, int64_t ldo,
-                                                   const float* lse, const void* grad_out, int64_t ldg, const int32_t* rowptr,
-                                                   const int32_t* perm, const int64_t* col, void* grad_d, void* gq, void* gc,
-                                                   void* grad_att, int64_t N, int64_t E, int64_t H, int64_t C, int has_row_slope,
-                                                   float row_slope, float negative_slope, int dtype, void* workspace,
-                                                   size_t workspace_bytes, gnnops_stream_t s) {
-    int es = 0;
-    const int rc = check_sizes("edge_attention_v1_backward", N, E, H, C, ldq, H * C, dtype, &es);
-    if (rc != GNNOPS_OK) return rc;
-    GNNOPS_REQUIRE(ldo >= H * C && ldd >= H && (ldg >= H * C || ldg == 0), GNNOPS_EINVAL,
-                   "edge_attention_v1_backward: a row pitch is shorter than the row");
-    GNNOPS_REQUIRE(grad_att, GNNOPS_EINVAL, "edge_attention_v1_backward: null pointer");
-    GNNOPS_REQUIRE(!(u && c), GNNOPS_EUNSUPPORTED,
-                   "edge_attention_v1_backward: a per-edge row u and a per-edge score term c together have no kernel instance");
-    hipStream_t stream = (hipStream_t)s;
-    const int HC = (int)(H * C);
-    if (N == 0) return GNNOPS_OK;   // no destination: nothing is written
-    GNNOPS_REQUIRE(rowptr && out && lse && d && att && grad_out && grad_d && (E == 0 || (q && col && gq)), GNNOPS_EINVAL,
-                   "edge_attention_v1_backward: null pointer");
-    GNNOPS_REQUIRE(E == 0 || !c || gc, GNNOPS_EINVAL, "edge_attention_v1_backward: c without a place for its gradient");
-    const size_t need = gnnops_edge_attention_v1_backward_workspace_bytes(N, H, C);
-    GNNOPS_REQUIRE(workspace && workspace_bytes >= need && (uintptr_t)workspace % 16 == 0, GNNOPS_EWORKSPACE,
-                   "edge_attention_v1_backward: workspace %zu < %zu", workspace_bytes, need);
-    const int max_vec = max_vec_of(es, {{q, ldq}, {att, 0}, {u, HC}, {out, ldo}, {grad_out, ldg}, {gq, HC}});
-    const Geometry geo = geometry((int)H, (int)C, max_vec, es);
-    const int rows = rows_of_partials(N, (int)H, (int)C);
+extern "C" int gnnops_edge_attention_v1_backward(const void* q, int64_t ldq, const void* d, int64_t ldd, const void* att, const void* u,
+                                                 const void* c, const void* edge_scale, const void* out, int64_t ldo, const float* lse,
+                                                 const void* grad_out, int64_t ldg, const int32_t* rowptr, const int32_t* perm,
+                                                 const int64_t* col, void* grad_d, void* gq, void* gc, void* grad_att, int64_t N,
+                                                 int64_t E, int64_t H, int64_t C, int has_row_slope, float row_slope,
+                                                 float negative_slope, int dtype, void* workspace, size_t workspace_bytes,
+                                                 gnnops_stream_t s) {
+    Launch l{};
+    const int rc = backward_prologue("edge_attention_v1_backward", N, E, H, C, ldq, H * C,
+                                     ldo >= H * C && ldd >= H && (ldg >= H * C || ldg == 0), u && c, grad_att,
+                                     rowptr && out && lse && d && att && grad_out && grad_d && (E == 0 || (q && col && gq)),
+                                     E != 0 && c && !gc ? "c" : nullptr, workspace, workspace_bytes, dtype,
+                                     {{q, ldq}, {att, 0}, {u, H * C}, {out, ldo}, {grad_out, ldg}, {gq, H * C}}, &l);
+    if (rc != GNNOPS_OK || !l.grid) return rc;
     GateArgs a{};
     a.q = q; a.d = d; a.att = att; a.u = E ? u : nullptr; a.c = E ? c : nullptr; a.ks = E ? edge_scale : nullptr; a.g = grad_out; a.o = out;
     a.rowptr = rowptr; a.perm = perm; a.col = col;
     a.dd = grad_d; a.gq = gq; a.gc = gc; a.lse = const_cast<float*>(lse); a.partial = (float*)workspace;
     a.N = N; a.ldq = ldq; a.ldd = ldd; a.ldo = ldo; a.ldg = ldg; a.H = (int)H; a.C = (int)C;
     a.slope = negative_slope; a.row_slope = has_row_slope ? row_slope : 1.f;
-    a.gshift = geo.gshift; a.hblocks = geo.hblocks;
-    a.nwaves = rows * geo.hblocks;
-    const int grid = (int)gnnops_cdiv(a.nwaves, 4);
-    gate_launch<true>(a, geo, grid, dtype, stream);
-    const dim3 dgrid((unsigned)gnnops_cdiv(HC, 256));
-    switch (dtype) {
-        case GNNOPS_F32: hipLaunchKernelGGL(attention_datt_kernel<float>, dgrid, dim3(256), 0, stream, a.partial, rows, HC, (float*)grad_att); break;
-        case GNNOPS_F16: hipLaunchKernelGGL(attention_datt_kernel<__half>, dgrid, dim3(256), 0, stream, a.partial, rows, HC, (__half*)grad_att); break;
-        default: hipLaunchKernelGGL(attention_datt_kernel<__hip_bfloat16>, dgrid, dim3(256), 0, stream, a.partial, rows, HC, (__hip_bfloat16*)grad_att); break;
-    }
+    a.gshift = l.geo.gshift; a.hblocks = l.geo.hblocks; a.nwaves = l.nwaves;
+    launch<GateFamily, true>(a, l.geo, l.grid, dtype, (hipStream_t)s);
+    launch_datt(a.partial, l.rows, (int)(H * C), grad_att, dtype, (hipStream_t)s);
     return gnnops_check_launch("edge_attention_v1_backward");
-}
-
-extern "C" int gnnops_edge_attention_v1_backward(const void* q, int64_t ldq, const void* d, int64_t ldd, const void* att, const void* u,
-                                                 const void* edge_scale, const void* out, int64_t ldo, const float* lse,
-                                                 const void* grad_out, int64_t ldg, const int32_t* rowptr, const int32_t* perm,
-                                                 const int64_t* col, void* grad_d, void* gq, void* grad_att, int64_t N, int64_t E,
-                                                 int64_t H, int64_t C, int has_row_slope, float row_slope, float negative_slope,
-                                                 int dtype, void* workspace, size_t workspace_bytes, gnnops_stream_t s) {
-    return gnnops_edge_attention_v1_c_backward(q, ldq, d, ldd, att, u, nullptr, edge_scale, out, ldo, lse, grad_out, ldg, rowptr, perm, col,
-                                               grad_d, gq, nullptr, grad_att, N, E, H, C, has_row_slope, row_slope, negative_slope, dtype,
-                                               workspace, workspace_bytes, s);
 }

@@ -347,7 +347,7 @@ void launch_kernel(const NormArgs& a, int grid, hipStream_t stream) {
 }
 
 template <typename T, bool BW, int VEC>
-void launch_nch(const NormArgs& a, int nch, int grid, hipStream_t stream) {
+void launch_pieces(const NormArgs& a, int nch, int grid, hipStream_t stream) {
     if (nch == 1) launch_kernel<T, BW, VEC, 1>(a, grid, stream);
     else if (nch == 2) launch_kernel<T, BW, VEC, 2>(a, grid, stream);
     else launch_kernel<T, BW, VEC, 4>(a, grid, stream);
@@ -357,11 +357,11 @@ template <typename T, bool BW>
 void launch(const NormArgs& a, const Geometry& geo, int grid, hipStream_t stream) {
     if (geo.nch == 0) return launch_kernel<T, BW, 1, 0>(a, grid, stream);
     if constexpr (Elem<T>::VEC == 8) {
-        if (geo.vec == 8) return launch_nch<T, BW, 8>(a, geo.nch, grid, stream);
+        if (geo.vec == 8) return launch_pieces<T, BW, 8>(a, geo.nch, grid, stream);
     }
-    if (geo.vec == 4) return launch_nch<T, BW, 4>(a, geo.nch, grid, stream);
-    if (geo.vec == 2) return launch_nch<T, BW, 2>(a, geo.nch, grid, stream);
-    return launch_nch<T, BW, 1>(a, geo.nch, grid, stream);
+    if (geo.vec == 4) return launch_pieces<T, BW, 4>(a, geo.nch, grid, stream);
+    if (geo.vec == 2) return launch_pieces<T, BW, 2>(a, geo.nch, grid, stream);
+    return launch_pieces<T, BW, 1>(a, geo.nch, grid, stream);
 }
 
 int check_sizes(const char* what, int64_t N, int64_t H, int64_t C, int64_t lda, int dtype, int* es) {

@@ -10,7 +10,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # GNNOPS_LIB_PATH: another build of the same ABI (A/B timing of two builds on one box: tools/time_partition.py)
 LIB_PATH = os.environ.get("GNNOPS_LIB_PATH") or os.path.join(os.path.dirname(_HERE), "csrc", "libgnnops.so")
 
-ABI_VERSION = 2   # GNNOPS_ABI_VERSION of include/gnnops.h
+ABI_VERSION = 3   # GNNOPS_ABI_VERSION of include/gnnops.h
 F32, F16, BF16 = 0, 1, 2
 SUM, MEAN, MIN, MAX, MUL = 0, 1, 2, 3, 4
 OK, EINVAL, EWORKSPACE, ELAUNCH, EUNSUPPORTED = 0, 1, 2, 3, 4  # status codes of include/gnnops.h
@@ -103,25 +103,15 @@ SIGNATURES = {
     "gnnops_edge_grad": (_ci, [_ci, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _i64, _i64, _ci, _vp]),
     "gnnops_edge_multi_grad": (_ci, [_ci, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _vp, _ci, _vp,
                                      _ci, ctypes.c_float, ctypes.c_float, _ci, _vp]),
-    "gnnops_edge_attention": (_ci, [_vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _i64, _i64, _i64, ctypes.c_float, _ci, _vp]),
+    "gnnops_edge_attention": (_ci, [_vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _i64, _i64, _i64, ctypes.c_float, _ci,
+                                    _vp]),
     "gnnops_edge_attention_backward_workspace_bytes": (_sz, [_i64, _i64, _i64]),
-    "gnnops_edge_attention_backward": (_ci, [_vp, _i64, _vp, _i64, _vp, _vp, _i64, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64,
-                                             _i64, _i64, ctypes.c_float, _ci, _vp, _sz, _vp]),
-    "gnnops_edge_attention_u": (_ci, [_vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _i64, _i64, _i64, ctypes.c_float, _ci,
-                                      _vp]),
-    "gnnops_edge_attention_u_backward_workspace_bytes": (_sz, [_i64, _i64, _i64]),
-    "gnnops_edge_attention_u_backward": (_ci, [_vp, _i64, _vp, _i64, _vp, _vp, _vp, _i64, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
-                                               _i64, _i64, _i64, _i64, ctypes.c_float, _ci, _vp, _sz, _vp]),
-    "gnnops_edge_attention_v1": (_ci, [_vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _i64, _i64, _i64, _ci,
+    "gnnops_edge_attention_backward": (_ci, [_vp, _i64, _vp, _i64, _vp, _vp, _vp, _i64, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                             _i64, _i64, _i64, _i64, ctypes.c_float, _ci, _vp, _sz, _vp]),
+    "gnnops_edge_attention_v1": (_ci, [_vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _i64, _i64, _i64, _ci,
                                        ctypes.c_float, ctypes.c_float, _ci, _vp]),
-    "gnnops_edge_attention_v1_backward_workspace_bytes": (_sz, [_i64, _i64, _i64]),
-    "gnnops_edge_attention_v1_backward": (_ci, [_vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp,
-                                                _i64, _i64, _i64, _i64, _ci, ctypes.c_float, ctypes.c_float, _ci, _vp, _sz, _vp]),
-    "gnnops_edge_attention_v1_c": (_ci, [_vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _i64, _i64, _i64, _ci,
-                                         ctypes.c_float, ctypes.c_float, _ci, _vp]),
-    "gnnops_edge_attention_v1_c_backward_workspace_bytes": (_sz, [_i64, _i64, _i64]),
-    "gnnops_edge_attention_v1_c_backward": (_ci, [_vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp,
-                                                  _vp, _vp, _i64, _i64, _i64, _i64, _ci, ctypes.c_float, ctypes.c_float, _ci, _vp, _sz, _vp]),
+    "gnnops_edge_attention_v1_backward": (_ci, [_vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp,
+                                                _vp, _vp, _i64, _i64, _i64, _i64, _ci, ctypes.c_float, ctypes.c_float, _ci, _vp, _sz, _vp]),
     "gnnops_spline_basis": (_ci, [_vp, _vp, _vp, _i64, _ci, _ci, _vp, _vp, _ci, _vp]),
     "gnnops_spline_weighting": (_ci, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _ci, _vp]),
     "gnnops_spline_conv": (_ci, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _ci, _ci, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _ci, _ci, _vp]),

@@ -667,91 +667,110 @@ class SplineConv(_Layer):
 
 
 # ---- attention: GATv2 (csrc/attention.hip) ---------------------------------------------------------------------------------
-def _attention_operands(q, p, att, edge_index, num_dst, heads, u=None):
-    _require_gpu(q, p, att, edge_index, u)
+def _attention_prepare(op, q, att, edge_index, num_dst, heads, dst, per_edge):
+    """What both attention passes do with their operands before a launch. dst = (tensor, name, width, what it has): the operand with
+    one row per destination; per_edge = [(tensor or None, name, width)]: the operands with one row per edge, in the order of
+    edge_index; a width is "heads * channels" or "heads". Returns (q, ldq, dst, ld_dst, att [H * C], the per-edge operands made
+    contiguous, edge_index, src_rows, the destination plan, col = the source row of each sorted position, E, H * C)."""
     HC = att.numel()
     if heads < 1 or HC == 0 or HC % heads:
-        raise RuntimeError(f"edge_attention: heads = {heads} does not divide the row width {HC} (att has one entry per head and channel)")
-    if q.dtype != p.dtype or q.dtype != att.dtype or (u is not None and u.dtype != q.dtype):
-        raise RuntimeError("edge_attention: operands must have the same dtype")
-    q, ldq = _rows(q, "q", 1, HC, op="edge_attention")
-    p, ldp = _rows(p, "p", 1, HC, op="edge_attention")
-    if p.size(0) != num_dst:
-        raise RuntimeError("edge_attention: p has one row per destination")
+        raise RuntimeError(f"{op}: heads = {heads} does not divide the row width {HC} (att has one entry per head and channel)")
+    widths = {"heads * channels": HC, "heads": heads}
+    t_dst, name, width, has = dst
+    if any(t is not None and t.dtype != q.dtype for t in (t_dst, att, *(t for t, _, _ in per_edge))):
+        raise RuntimeError(f"{op}: operands must have the same dtype")
+    q, ldq = _rows(q, "q", 1, HC, op=op)
+    t_dst, ld_dst = _rows(t_dst, name, 1, widths[width], op=op)
+    if t_dst.size(0) != num_dst:
+        raise RuntimeError(f"{op}: {name} has {has}")
     if q.size(0) >= 2 ** 31:
-        raise NotImplementedError("edge_attention: 2^31 or more source rows")
-    edge_index, src_rows, dst_rows = _coo_rows_cols(edge_index, "edge_attention")
+        raise NotImplementedError(f"{op}: 2^31 or more source rows")
+    edge_index, src_rows, dst_rows = _coo_rows_cols(edge_index, op)
     E = edge_index.size(1)
-    if u is not None:
-        if u.dim() != 2 or tuple(u.shape) != (E, HC):
-            raise RuntimeError(f"edge_attention: u must be [E, heads * channels] = [{E}, {HC}], in the order of edge_index")
-        if u.device != q.device:
-            raise RuntimeError("edge_attention: u must be on the device of q")
-        u = u.contiguous()
+    rows = []
+    for t, name, width in per_edge:
+        if t is not None:
+            if t.dim() != 2 or tuple(t.shape) != (E, widths[width]):
+                raise RuntimeError(f"{op}: {name} must be [E, {width}] = [{E}, {widths[width]}], in the order of edge_index")
+            t = t.contiguous()
+        rows.append(t)
     plan = get_plan(dst_rows, num_dst, owner=edge_index, tag=1, companion=src_rows)   # the plans of edge_reduce: nothing new on a warm call
     if plan.col is not None or E == 0:
         col = plan.col if E else src_rows
     else:
         col, _ = _csr_arrays(plan, src_rows, None, owner=edge_index, tag=0)
-    return q, ldq, p, ldp, att.contiguous().view(-1), u, edge_index, src_rows, plan, col, E, HC
+    return q, ldq, t_dst, ld_dst, att.contiguous().view(-1), rows, edge_index, src_rows, plan, col, E, HC
+
+
+def _grad_rows(grad_out, HC, op):
+    """(g, ldg) for the kernels. autograd hands over whatever layout the consumer made: out.sum() an expanded scalar (strides 0, 0),
+    W @ out.t() a transposed one. Rows of unit column stride are read in place (pitch 0 = one row for all); anything else is copied."""
+    g = grad_out if grad_out.dim() == 2 and (grad_out.stride(1) == 1 or grad_out.size(1) == 1) else grad_out.contiguous()
+    g, ldg = _rows(g, "the output gradient", 1, HC, op=op)
+    if g.size(0) > 1 and g.stride(0) == 0:
+        ldg = 0
+    return g, ldg
+
+
+def _attention_tail(gq, d_dst, src_rows, edge_index, q0, dst0, need_q, need_dst):
+    """(d q, d of the per-destination operand) as autograd wants them: d q = the segment sum of gq over the plan of the source ids,
+    and either one padded with zero columns where the operand was a column block wider than what the pass reads."""
+    d_q = None
+    if need_q:
+        plan_src = get_plan(src_rows, q0.size(0), owner=edge_index, tag=0)
+        d_q = ops.scatter(gq, plan_src, 0, None, None, "sum")
+        if q0.size(1) != gq.size(1):
+            d_q = torch.nn.functional.pad(d_q, (0, q0.size(1) - gq.size(1)))
+    if need_dst and dst0.size(1) != d_dst.size(1):
+        d_dst = torch.nn.functional.pad(d_dst, (0, dst0.size(1) - d_dst.size(1)))
+    return d_q, (d_dst if need_dst else None)
+
+
+def _attention_operands(q, p, att, edge_index, num_dst, heads, u=None):
+    _require_gpu(q, p, att, edge_index, u)
+    if u is not None and u.device != q.device:
+        raise RuntimeError("edge_attention: u must be on the device of q")
+    q, ldq, p, ldp, att, (u,), edge_index, src_rows, plan, col, E, HC = _attention_prepare(
+        "edge_attention", q, att, edge_index, num_dst, heads, (p, "p", "heads * channels", "one row per destination"),
+        [(u, "u", "heads * channels")])
+    return q, ldq, p, ldp, att, u, edge_index, src_rows, plan, col, E, HC
 
 
 def _attention_forward(q, p, att, edge_index, num_dst, heads, negative_slope, u=None, identity_perm=False):
-    """(out [num_dst, H * C], lse fp32 [num_dst, H]) of one launch of gnnops_edge_attention (gnnops_edge_attention_u with u).
+    """(out [num_dst, H * C], lse fp32 [num_dst, H]) of one launch of gnnops_edge_attention.
     identity_perm: the caller knows the edge list to be sorted by destination already, and u is read without the plan's perm."""
     q, ldq, p, ldp, att, u, edge_index, _, plan, col, E, HC = _attention_operands(q, p, att, edge_index, num_dst, heads, u)
     out = torch.empty((num_dst, HC), dtype=q.dtype, device=q.device)
     lse = torch.empty((num_dst, heads), dtype=torch.float32, device=q.device)
-    L = _lib.load()
+    perm = None if identity_perm or u is None else plan.perm.data_ptr()   # only u is read through it
     with _on(q.device):
-        if u is None:
-            check(L.gnnops_edge_attention(q.data_ptr(), ldq, p.data_ptr(), ldp, att.data_ptr(), plan.rowptr.data_ptr(),
-                                          col.data_ptr(), out.data_ptr(), HC, lse.data_ptr(), num_dst, E, heads, HC // heads,
-                                          float(negative_slope), _dtype_code(q, "edge_attention"), _stream()), "edge_attention")
-        else:
-            check(L.gnnops_edge_attention_u(q.data_ptr(), ldq, p.data_ptr(), ldp, att.data_ptr(), u.data_ptr(), plan.rowptr.data_ptr(),
-                                            None if identity_perm else plan.perm.data_ptr(), col.data_ptr(), out.data_ptr(), HC,
-                                            lse.data_ptr(), num_dst, E, heads, HC // heads, float(negative_slope),
-                                            _dtype_code(q, "edge_attention"), _stream()), "edge_attention")
+        check(_lib.load().gnnops_edge_attention(q.data_ptr(), ldq, p.data_ptr(), ldp, att.data_ptr(), _ptr(u), plan.rowptr.data_ptr(), perm,
+                                                col.data_ptr(), out.data_ptr(), HC, lse.data_ptr(), num_dst, E, heads, HC // heads,
+                                                float(negative_slope), _dtype_code(q, "edge_attention"), _stream()), "edge_attention")
     return out, lse
 
 
 def _attention_backward(q0, p0, att0, u0, edge_index, out, lse, grad_out, num_dst, heads, slope, identity_perm=False):
     """(gq [E, H * C] or None, d p [num_dst, H * C], d att [H * C], d u [E, H * C] or None, src_rows, edge_index) of one launch of
-    gnnops_edge_attention_backward (gnnops_edge_attention_u_backward with u); None where there is no edge."""
+    gnnops_edge_attention_backward; None where there is no edge."""
     q, ldq, p, ldp, att, u, edge_index, src_rows, plan, col, E, HC = _attention_operands(q0, p0, att0, edge_index, num_dst, heads, u0)
     if E == 0 or num_dst == 0:
         return None, None, None, None, src_rows, edge_index
-    # autograd hands over whatever layout the consumer made: out.sum() an expanded scalar (strides 0, 0), W @ out.t() a
-    # transposed one. Rows of unit column stride are read in place (pitch 0 = one row for all); anything else is copied.
-    g = grad_out if grad_out.dim() == 2 and (grad_out.stride(1) == 1 or grad_out.size(1) == 1) else grad_out.contiguous()
-    g, ldg = _rows(g, "the output gradient", 1, HC, op="edge_attention")
-    if g.size(0) > 1 and g.stride(0) == 0:
-        ldg = 0
+    g, ldg = _grad_rows(grad_out, HC, "edge_attention")
     d_p = torch.empty((num_dst, HC), dtype=q.dtype, device=q.device)
     gq = torch.empty((E, HC), dtype=q.dtype, device=q.device)
     d_att = torch.empty(HC, dtype=q.dtype, device=q.device)
+    d_u = None if u is None else torch.empty((E, HC), dtype=q.dtype, device=q.device)
     L = _lib.load()
     perm = None if identity_perm else plan.perm.data_ptr()
     with _on(q.device):
-        if u is None:
-            ws_bytes = L.gnnops_edge_attention_backward_workspace_bytes(num_dst, heads, HC // heads)
-            ws = torch.empty(ws_bytes, dtype=torch.uint8, device=q.device)
-            d_u = None
-            check(L.gnnops_edge_attention_backward(q.data_ptr(), ldq, p.data_ptr(), ldp, att.data_ptr(), out.data_ptr(), HC,
-                                                   lse.data_ptr(), g.data_ptr(), ldg, plan.rowptr.data_ptr(), perm,
-                                                   col.data_ptr(), d_p.data_ptr(), gq.data_ptr(), d_att.data_ptr(), num_dst, E, heads,
-                                                   HC // heads, slope, _dtype_code(q, "edge_attention"), ws.data_ptr(), ws_bytes,
-                                                   _stream()), "edge_attention_backward")
-        else:
-            ws_bytes = L.gnnops_edge_attention_u_backward_workspace_bytes(num_dst, heads, HC // heads)
-            ws = torch.empty(ws_bytes, dtype=torch.uint8, device=q.device)
-            d_u = torch.empty((E, HC), dtype=q.dtype, device=q.device)
-            check(L.gnnops_edge_attention_u_backward(q.data_ptr(), ldq, p.data_ptr(), ldp, att.data_ptr(), u.data_ptr(), out.data_ptr(), HC,
-                                                     lse.data_ptr(), g.data_ptr(), ldg, plan.rowptr.data_ptr(), perm,
-                                                     col.data_ptr(), d_p.data_ptr(), gq.data_ptr(), d_u.data_ptr(), d_att.data_ptr(), num_dst,
-                                                     E, heads, HC // heads, slope, _dtype_code(q, "edge_attention"), ws.data_ptr(), ws_bytes,
-                                                     _stream()), "edge_attention_backward")
+        ws_bytes = L.gnnops_edge_attention_backward_workspace_bytes(num_dst, heads, HC // heads)
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=q.device)
+        check(L.gnnops_edge_attention_backward(q.data_ptr(), ldq, p.data_ptr(), ldp, att.data_ptr(), _ptr(u), out.data_ptr(), HC,
+                                               lse.data_ptr(), g.data_ptr(), ldg, plan.rowptr.data_ptr(), perm, col.data_ptr(),
+                                               d_p.data_ptr(), gq.data_ptr(), _ptr(d_u), d_att.data_ptr(), num_dst, E, heads, HC // heads,
+                                               slope, _dtype_code(q, "edge_attention"), ws.data_ptr(), ws_bytes, _stream()),
+              "edge_attention_backward")
     return gq, d_p, d_att, d_u, src_rows, edge_index
 
 
@@ -769,7 +788,7 @@ def edge_attention(q, p, att, edge_index, num_dst, heads, negative_slope=0.2, u=
 class _EdgeAttention(torch.autograd.Function):
     """backward (gnnops_edge_attention_backward, destination-ordered like the forward): d p and d att from the kernel, and one
     per-edge tensor gq [E, H * C] in edge order whose segment sum over the plan of the source ids is d q — as `_EdgeReduce`. With u
-    (gnnops_edge_attention_u_backward) a second per-edge tensor in edge order is d u."""
+    a second per-edge tensor in edge order is d u."""
 
     @staticmethod
     def forward(ctx, q, p, att, u, edge_index, num_dst, heads, negative_slope):
@@ -788,17 +807,8 @@ class _EdgeAttention(torch.autograd.Function):
         if gq is None:
             return (torch.zeros_like(q0) if need_q else None, torch.zeros_like(p0) if need_p else None,
                     torch.zeros_like(att0) if need_att else None, torch.zeros_like(u0) if has_u and need_u else None, None, None, None, None)
-        HC = att0.numel()
-        d_q = None
-        if need_q:
-            plan_src = get_plan(src_rows, q0.size(0), owner=edge_index, tag=0)
-            d_q = ops.scatter(gq, plan_src, 0, None, None, "sum")
-            if q0.size(1) != HC:         # q was a column block wider than the H * C the pass reads
-                d_q = torch.nn.functional.pad(d_q, (0, q0.size(1) - HC))
-        if need_p and p0.size(1) != HC:
-            d_p = torch.nn.functional.pad(d_p, (0, p0.size(1) - HC))
-        return (d_q, (d_p if need_p else None), (d_att.view(att0.shape) if need_att else None), (d_u if has_u and need_u else None),
-                None, None, None, None)
+        d_q, d_p = _attention_tail(gq, d_p, src_rows, edge_index, q0, p0, need_q, need_p)
+        return (d_q, d_p, (d_att.view(att0.shape) if need_att else None), (d_u if has_u and need_u else None), None, None, None, None)
 
 
 def _checked_fill_value(fill_value, who):
@@ -1087,63 +1097,30 @@ class GATv2(torch.nn.Module):
 def _v1_operands(q, d, att, edge_index, num_dst, heads, u, edge_scale, c=None):
     op = "edge_attention_v1"
     _require_gpu(q, d, att, edge_index, u, edge_scale, c)
-    HC = att.numel()
-    if heads < 1 or HC == 0 or HC % heads:
-        raise RuntimeError(f"{op}: heads = {heads} does not divide the row width {HC} (att has one entry per head and channel)")
-    if HC > 8192:
-        raise RuntimeError(f"{op}: heads * channels = {HC} exceeds the row limit of 8192")
-    if any(t is not None and t.dtype != q.dtype for t in (d, att, u, edge_scale, c)):
-        raise RuntimeError(f"{op}: operands must have the same dtype")
-    q, ldq = _rows(q, "q", 1, HC, op=op)
-    d, ldd = _rows(d, "d", 1, heads, op=op)
-    if d.size(0) != num_dst:
-        raise RuntimeError(f"{op}: d has one row per destination and one column per head")
-    if q.size(0) >= 2 ** 31:
-        raise NotImplementedError(f"{op}: 2^31 or more source rows")
-    edge_index, src_rows, dst_rows = _coo_rows_cols(edge_index, op)
-    E = edge_index.size(1)
-    if u is not None:
-        if u.dim() != 2 or tuple(u.shape) != (E, HC):
-            raise RuntimeError(f"{op}: u must be [E, heads * channels] = [{E}, {HC}], in the order of edge_index")
-        u = u.contiguous()
+    if att.numel() > 8192:
+        raise RuntimeError(f"{op}: heads * channels = {att.numel()} exceeds the row limit of 8192")
+    q, ldq, d, ldd, att, (u, edge_scale, c), edge_index, src_rows, plan, col, E, HC = _attention_prepare(
+        op, q, att, edge_index, num_dst, heads, (d, "d", "heads", "one row per destination and one column per head"),
+        [(u, "u", "heads * channels"), (edge_scale, "edge_scale", "heads"), (c, "edge_score", "heads")])
+    if u is not None and c is not None:
+        raise NotImplementedError(f"{op}: u and edge_score together have no kernel instance")
     if edge_scale is not None:
-        if edge_scale.dim() != 2 or tuple(edge_scale.shape) != (E, heads):
-            raise RuntimeError(f"{op}: edge_scale must be [E, heads] = [{E}, {heads}], in the order of edge_index")
-        edge_scale = edge_scale.detach().contiguous()
-    if c is not None:
-        if c.dim() != 2 or tuple(c.shape) != (E, heads):
-            raise RuntimeError(f"{op}: edge_score must be [E, heads] = [{E}, {heads}], in the order of edge_index")
-        if u is not None:
-            raise NotImplementedError(f"{op}: u and edge_score together have no kernel instance")
-        c = c.contiguous()
-    plan = get_plan(dst_rows, num_dst, owner=edge_index, tag=1, companion=src_rows)   # the plans of edge_attention: nothing new on a warm call
-    if plan.col is not None or E == 0:
-        col = plan.col if E else src_rows
-    else:
-        col, _ = _csr_arrays(plan, src_rows, None, owner=edge_index, tag=0)
-    return q, ldq, d, ldd, att.contiguous().view(-1), u, edge_scale, c, edge_index, src_rows, plan, col, E, HC
+        edge_scale = edge_scale.detach()
+    return q, ldq, d, ldd, att, u, edge_scale, c, edge_index, src_rows, plan, col, E, HC
 
 
 def _v1_forward(q, d, att, edge_index, num_dst, heads, u, row_slope, negative_slope, edge_scale, c=None, identity_perm=False):
-    """(out [num_dst, H * C], lse fp32 [num_dst, H]) of one launch of gnnops_edge_attention_v1 (gnnops_edge_attention_v1_c with c).
+    """(out [num_dst, H * C], lse fp32 [num_dst, H]) of one launch of gnnops_edge_attention_v1.
     identity_perm: the caller knows the edge list to be sorted by destination already; the per-edge operands are read without perm."""
     q, ldq, d, ldd, att, u, ks, c, edge_index, _, plan, col, E, HC = _v1_operands(q, d, att, edge_index, num_dst, heads, u, edge_scale, c)
     out = torch.empty((num_dst, HC), dtype=q.dtype, device=q.device)
     lse = torch.empty((num_dst, heads), dtype=torch.float32, device=q.device)
-    ptr = lambda t: t.data_ptr() if t is not None else None   # noqa: E731
     perm = None if identity_perm else plan.perm.data_ptr()
-    L = _lib.load()
     with _on(q.device):
-        if c is None:
-            check(L.gnnops_edge_attention_v1(q.data_ptr(), ldq, d.data_ptr(), ldd, att.data_ptr(), ptr(u), ptr(ks), plan.rowptr.data_ptr(),
-                                             perm, col.data_ptr(), out.data_ptr(), HC, lse.data_ptr(), num_dst, E, heads,
-                                             HC // heads, int(row_slope is not None), float(row_slope or 0.0), float(negative_slope),
-                                             _dtype_code(q, "edge_attention_v1"), _stream()), "edge_attention_v1")
-        else:
-            check(L.gnnops_edge_attention_v1_c(q.data_ptr(), ldq, d.data_ptr(), ldd, att.data_ptr(), ptr(u), c.data_ptr(), ptr(ks),
-                                               plan.rowptr.data_ptr(), perm, col.data_ptr(), out.data_ptr(), HC, lse.data_ptr(), num_dst, E,
-                                               heads, HC // heads, int(row_slope is not None), float(row_slope or 0.0),
-                                               float(negative_slope), _dtype_code(q, "edge_attention_v1"), _stream()), "edge_attention_v1")
+        check(_lib.load().gnnops_edge_attention_v1(q.data_ptr(), ldq, d.data_ptr(), ldd, att.data_ptr(), _ptr(u), _ptr(c), _ptr(ks),
+                                                   plan.rowptr.data_ptr(), perm, col.data_ptr(), out.data_ptr(), HC, lse.data_ptr(), num_dst, E,
+                                                   heads, HC // heads, int(row_slope is not None), float(row_slope or 0.0),
+                                                   float(negative_slope), _dtype_code(q, "edge_attention_v1"), _stream()), "edge_attention_v1")
     return out, lse
 
 
@@ -1163,49 +1140,33 @@ def edge_attention_v1(q, d, att, edge_index, num_dst, heads, u=None, row_slope=N
 
 def _v1_backward(q0, d0, att0, u0, c0, ks0, edge_index, out, lse, grad_out, num_dst, heads, row_slope, slope, identity_perm=False):
     """(gq [E, H * C] or None, d d [num_dst, H], d att [H * C], d edge_score [E, H] or None, src_rows, edge_index) of one launch of
-    gnnops_edge_attention_v1_backward (gnnops_edge_attention_v1_c_backward with c); None where there is no edge."""
+    gnnops_edge_attention_v1_backward; None where there is no edge."""
     q, ldq, d, ldd, att, u, ks, c, edge_index, src_rows, plan, col, E, HC = _v1_operands(q0, d0, att0, edge_index, num_dst, heads, u0, ks0, c0)
     if E == 0 or num_dst == 0:
         return None, None, None, None, src_rows, edge_index
-    # the layouts autograd hands over, as _attention_backward takes them
-    g = grad_out if grad_out.dim() == 2 and (grad_out.stride(1) == 1 or grad_out.size(1) == 1) else grad_out.contiguous()
-    g, ldg = _rows(g, "the output gradient", 1, HC, op="edge_attention_v1")
-    if g.size(0) > 1 and g.stride(0) == 0:
-        ldg = 0
+    g, ldg = _grad_rows(grad_out, HC, "edge_attention_v1")
     d_d = torch.empty((num_dst, heads), dtype=q.dtype, device=q.device)
     gq = torch.empty((E, HC), dtype=q.dtype, device=q.device)
     d_att = torch.empty(HC, dtype=q.dtype, device=q.device)
+    d_c = None if c is None else torch.empty((E, heads), dtype=q.dtype, device=q.device)
     L = _lib.load()
-    ptr = lambda t: t.data_ptr() if t is not None else None   # noqa: E731
     perm = None if identity_perm else plan.perm.data_ptr()
     with _on(q.device):
-        if c is None:
-            ws_bytes = L.gnnops_edge_attention_v1_backward_workspace_bytes(num_dst, heads, HC // heads)
-            ws = torch.empty(ws_bytes, dtype=torch.uint8, device=q.device)
-            d_c = None
-            check(L.gnnops_edge_attention_v1_backward(q.data_ptr(), ldq, d.data_ptr(), ldd, att.data_ptr(), ptr(u), ptr(ks), out.data_ptr(), HC,
-                                                      lse.data_ptr(), g.data_ptr(), ldg, plan.rowptr.data_ptr(), perm,
-                                                      col.data_ptr(), d_d.data_ptr(), gq.data_ptr(), d_att.data_ptr(), num_dst, E, heads,
-                                                      HC // heads, int(row_slope is not None), float(row_slope or 0.0), slope,
-                                                      _dtype_code(q, "edge_attention_v1"), ws.data_ptr(), ws_bytes, _stream()),
-                  "edge_attention_v1_backward")
-        else:
-            ws_bytes = L.gnnops_edge_attention_v1_c_backward_workspace_bytes(num_dst, heads, HC // heads)
-            ws = torch.empty(ws_bytes, dtype=torch.uint8, device=q.device)
-            d_c = torch.empty((E, heads), dtype=q.dtype, device=q.device)
-            check(L.gnnops_edge_attention_v1_c_backward(q.data_ptr(), ldq, d.data_ptr(), ldd, att.data_ptr(), ptr(u), c.data_ptr(), ptr(ks),
-                                                        out.data_ptr(), HC, lse.data_ptr(), g.data_ptr(), ldg, plan.rowptr.data_ptr(), perm,
-                                                        col.data_ptr(), d_d.data_ptr(), gq.data_ptr(), d_c.data_ptr(), d_att.data_ptr(),
-                                                        num_dst, E, heads, HC // heads, int(row_slope is not None), float(row_slope or 0.0),
-                                                        slope, _dtype_code(q, "edge_attention_v1"), ws.data_ptr(), ws_bytes, _stream()),
-                  "edge_attention_v1_backward")
+        ws_bytes = L.gnnops_edge_attention_backward_workspace_bytes(num_dst, heads, HC // heads)
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=q.device)
+        check(L.gnnops_edge_attention_v1_backward(q.data_ptr(), ldq, d.data_ptr(), ldd, att.data_ptr(), _ptr(u), _ptr(c), _ptr(ks),
+                                                  out.data_ptr(), HC, lse.data_ptr(), g.data_ptr(), ldg, plan.rowptr.data_ptr(), perm,
+                                                  col.data_ptr(), d_d.data_ptr(), gq.data_ptr(), _ptr(d_c), d_att.data_ptr(), num_dst, E,
+                                                  heads, HC // heads, int(row_slope is not None), float(row_slope or 0.0), slope,
+                                                  _dtype_code(q, "edge_attention_v1"), ws.data_ptr(), ws_bytes, _stream()),
+              "edge_attention_v1_backward")
     return gq, d_d, d_att, d_c, src_rows, edge_index
 
 
 class _EdgeAttentionV1(torch.autograd.Function):
     """backward (gnnops_edge_attention_v1_backward, destination-ordered like the forward): d d and d att from the kernel, and one
     per-edge tensor gq [E, H * C] in edge order: d u is gq itself, d q its segment sum over the plan of the source ids. With
-    edge_score (gnnops_edge_attention_v1_c_backward) its gradient [E, H] comes from the kernel in edge order too."""
+    edge_score its gradient [E, H] comes from the kernel in edge order too."""
 
     @staticmethod
     def forward(ctx, q, d, att, u, c, edge_scale, edge_index, num_dst, heads, row_slope, negative_slope):
@@ -1229,16 +1190,8 @@ class _EdgeAttentionV1(torch.autograd.Function):
             return (torch.zeros_like(q0) if need_q else None, torch.zeros_like(d0) if need_d else None,
                     torch.zeros_like(att0) if need_att else None, torch.zeros_like(u0) if has_u and need_u else None,
                     torch.zeros_like(c0) if has_c and need_c else None) + tail
-        HC = att0.numel()
-        d_q = None
-        if need_q:
-            plan_src = get_plan(src_rows, q0.size(0), owner=edge_index, tag=0)
-            d_q = ops.scatter(gq, plan_src, 0, None, None, "sum")
-            if q0.size(1) != HC:         # q was a column block wider than the H * C the pass reads
-                d_q = torch.nn.functional.pad(d_q, (0, q0.size(1) - HC))
-        if need_d and d0.size(1) != heads:
-            d_d = torch.nn.functional.pad(d_d, (0, d0.size(1) - heads))
-        return (d_q, d_d if need_d else None, d_att.view(att0.shape) if need_att else None, gq if has_u and need_u else None,
+        d_q, d_d = _attention_tail(gq, d_d, src_rows, edge_index, q0, d0, need_q, need_d)
+        return (d_q, d_d, d_att.view(att0.shape) if need_att else None, gq if has_u and need_u else None,
                 d_c if has_c and need_c else None) + tail
 
 

@@ -30,7 +30,8 @@
 extern "C" {
 #endif
 
-#define GNNOPS_ABI_VERSION 2   /* 2: gnnops_narrow_index takes the id bound; round-2 exports (layers, spline, cluster) */
+#define GNNOPS_ABI_VERSION 3   /* 2: gnnops_narrow_index takes the id bound; round-2 exports (layers, spline, cluster)
+                                * 3: one entry point per attention pass, optional operands NULL (the _u / _v1_c names are gone) */
 
 enum gnnops_status {
     GNNOPS_OK = 0,
@@ -644,93 +645,63 @@ int gnnops_edge_multi_grad(int functor, const void* q, int64_t ldq, const void* 
  * GATv2REG from it (graph_benchmark/models/ptg_models.py:208-236) — in one pass with an online softmax. Operands as
  * gnnops_edge_reduce: destination-sorted plan (rowptr int32 [N+1], col int64 [E] = source row of each sorted position,
  * perm int32 [E] = original edge id of that position, NULL = identity), ld* = row pitches in elements.
- *   z[e,h,c] = p[i,h,c] + q[j,h,c]   s[e,h] = sum_c att[h,c] * leaky_relu(z[e,h,c], negative_slope)      edge e = (j -> i)
+ *   z[e,h,c] = p[i,h,c] + q[j,h,c] + u[e,h,c]   s[e,h] = sum_c att[h,c] * leaky_relu(z[e,h,c], negative_slope)     edge e = (j -> i)
  *   out[i,h,:] = sum_{e into i} exp(s[e,h] - lse[i,h]) * q[j,h,:],   lse[i,h] = log sum_{e into i} exp(s[e,h])
  * q [N_src, >= H*C], p [N, >= H*C], att [H*C], out [N, H*C] (pitch ldo) in `dtype`; lse fp32 [N, H], always written.
  * A destination without edges gets a zero row and lse = -inf. 1 <= H, 1 <= C, H*C <= 8192 (GNNOPS_EINVAL otherwise);
  * N, E, ldq and every value of col (so N_src) below 2^31: the kernels narrow source ids to 32 bits.
  * One launch on `stream`, no allocation, no synchronisation.
+ * u, optional (GATv2Conv with edge features: u = lin_edge(edge_attr)), enters the score only — the message stays q[j,h,:].
+ *   u [E, H*C] is dense, in `dtype`, its rows the ORIGINAL edge ids: the row of sorted position k is perm[k] (perm NULL =
+ *   identity: the edge list is already destination-sorted), at the 64-bit element offset (int64) id * H*C. u NULL = absent
+ *   (the forward then does not read perm: pass NULL); an all-zero u gives the same bits as the call without u.
+ *   E == 0 or N == 0: u is not dereferenced.
  * Backward, given grad_out [N, >= H*C] (pitch ldg; 0 = one row for all), the forward's out and lse:
  *   grad_p [N, H*C] dense; gq [E, H*C] dense, row = ORIGINAL edge id: d q = its segment sum over the plan of the source ids
  *   (gnnops_segment_reduce); grad_att [H*C]. workspace = gnnops_edge_attention_backward_workspace_bytes(N, H, C) bytes of
- *   fp32 partial sums of d att, added in a fixed order (the same bits every run). N == 0: nothing is written.
+ *   fp32 partial sums of d att, added in a fixed order. gu [E, H*C] dense, row = original edge id, = d u
+ *   (gq[e] = a[e] * grad_out[i] + gu[e]): required when u is given and E > 0, ignored otherwise. No atomics: two runs give
+ *   the same bits. N == 0: nothing is written.
  * ------------------------------------------------------------------------------------------- */
-int gnnops_edge_attention(const void* q, int64_t ldq, const void* p, int64_t ldp, const void* att, const int32_t* rowptr,
-                          const int64_t* col, void* out, int64_t ldo, float* lse, int64_t N, int64_t E, int64_t H, int64_t C,
-                          float negative_slope, int dtype, gnnops_stream_t stream);
-size_t gnnops_edge_attention_backward_workspace_bytes(int64_t N, int64_t H, int64_t C);
-int gnnops_edge_attention_backward(const void* q, int64_t ldq, const void* p, int64_t ldp, const void* att, const void* out,
-                                   int64_t ldo, const float* lse, const void* grad_out, int64_t ldg, const int32_t* rowptr,
-                                   const int32_t* perm, const int64_t* col, void* grad_p, void* gq, void* grad_att, int64_t N,
-                                   int64_t E, int64_t H, int64_t C, float negative_slope, int dtype, void* workspace,
-                                   size_t workspace_bytes, gnnops_stream_t stream);
-
-/* The same pass with a per-edge row in the score (GATv2Conv with edge features: u = lin_edge(edge_attr)):
- *   z[e,h,c] = p[i,h,c] + q[j,h,c] + u[e,h,c]; s, lse and out as above — the message stays q[j,h,:], without u.
- * u [E, H*C] is dense, in `dtype`, its rows the ORIGINAL edge ids: the row of sorted position k is perm[k] (perm NULL =
- * identity: the edge list is already destination-sorted), at the 64-bit element offset (int64) id * H*C. u NULL = absent: the
- * call is gnnops_edge_attention, and an all-zero u gives the same bits as that call. E == 0 or N == 0: u is not dereferenced.
- * Backward: operands and workspace (gnnops_edge_attention_u_backward_workspace_bytes, the same size) as
- *   gnnops_edge_attention_backward, and a second per-edge tensor gu [E, H*C] dense, row = original edge id, = d u
- *   (gq[e] = a[e] * grad_out[i] + gu[e]). gu is required when u is given and E > 0, ignored otherwise. No atomics: two runs
- *   give the same bits. */
-int gnnops_edge_attention_u(const void* q, int64_t ldq, const void* p, int64_t ldp, const void* att, const void* u,
-                            const int32_t* rowptr, const int32_t* perm, const int64_t* col, void* out, int64_t ldo, float* lse,
-                            int64_t N, int64_t E, int64_t H, int64_t C, float negative_slope, int dtype, gnnops_stream_t stream);
-size_t gnnops_edge_attention_u_backward_workspace_bytes(int64_t N, int64_t H, int64_t C);
-int gnnops_edge_attention_u_backward(const void* q, int64_t ldq, const void* p, int64_t ldp, const void* att, const void* u,
-                                     const void* out, int64_t ldo, const float* lse, const void* grad_out, int64_t ldg,
-                                     const int32_t* rowptr, const int32_t* perm, const int64_t* col, void* grad_p, void* gq,
-                                     void* gu, void* grad_att, int64_t N, int64_t E, int64_t H, int64_t C, float negative_slope,
-                                     int dtype, void* workspace, size_t workspace_bytes, gnnops_stream_t stream);
+int gnnops_edge_attention(const void* q, int64_t ldq, const void* p, int64_t ldp, const void* att, const void* u,
+                          const int32_t* rowptr, const int32_t* perm, const int64_t* col, void* out, int64_t ldo, float* lse,
+                          int64_t N, int64_t E, int64_t H, int64_t C, float negative_slope, int dtype, gnnops_stream_t stream);
+size_t gnnops_edge_attention_backward_workspace_bytes(int64_t N, int64_t H, int64_t C);   /* host-only; serves both families */
+int gnnops_edge_attention_backward(const void* q, int64_t ldq, const void* p, int64_t ldp, const void* att, const void* u,
+                                   const void* out, int64_t ldo, const float* lse, const void* grad_out, int64_t ldg,
+                                   const int32_t* rowptr, const int32_t* perm, const int64_t* col, void* grad_p, void* gq,
+                                   void* gu, void* grad_att, int64_t N, int64_t E, int64_t H, int64_t C, float negative_slope,
+                                   int dtype, void* workspace, size_t workspace_bytes, gnnops_stream_t stream);
 
 /* The second member of the family (GATConv, the original GAT, and AttentiveFP's GATEConv): the score is a per-edge scalar plus
  * a per-destination scalar, the row may carry a per-edge part u and a leaky ReLU of its own, and a per-edge, per-head scale
  * (the attention dropout mask divided by 1 - p) enters the weighted sum only, never the denominator.
  *   t[e,h,:] = q[j,h,:] + u[e,h,:]            r = has_row_slope ? leaky_relu(t, row_slope) : t              edge e = (j -> i)
- *   s[e,h] = leaky_relu(att[h,:] . r[e,h,:] + d[i,h], negative_slope)       lse[i,h] = log sum_{e into i} exp(s[e,h])
+ *   s[e,h] = leaky_relu(att[h,:] . r[e,h,:] + d[i,h] + c[e,h], negative_slope)   lse[i,h] = log sum_{e into i} exp(s[e,h])
  *   out[i,h,:] = sum_{e into i} exp(s[e,h] - lse[i,h]) * edge_scale[e,h] * r[e,h,:]
  * q [N_src, >= H*C] (pitch ldq), d [N, >= H] (pitch ldd), att [H*C], out [N, H*C] (pitch ldo) in `dtype`; lse fp32 [N, H].
- * u [E, H*C] and edge_scale [E, H] are dense, in `dtype`, their rows the ORIGINAL edge ids (read through perm, offsets in
- * 64 bits); NULL = absent (u = 0, edge_scale = 1). row_slope is read only when has_row_slope != 0. Limits, the plan operands
- * and the empty destination as gnnops_edge_attention. One launch, no allocation, no synchronisation.
+ * u [E, H*C], c [E, H] and edge_scale [E, H] are dense, in `dtype`, their rows the ORIGINAL edge ids (read through perm,
+ * offsets in 64 bits); NULL = absent (u = 0, c = 0, edge_scale = 1). row_slope is read only when has_row_slope != 0. Limits,
+ * the plan operands and the empty destination as gnnops_edge_attention. One launch, no allocation, no synchronisation.
+ * c (GATConv with edge features: c[e,h] = att_edge[h] . lin_edge(edge_attr)[e,h,:], one tiny product with att_edge folded
+ *   into the weight) leaves the message unchanged, and an all-zero c gives the same bits as the call without c. c and u
+ *   together have no kernel instance (GNNOPS_EUNSUPPORTED). E == 0 or N == 0: u, c and edge_scale are not dereferenced.
  * Backward: grad_d [N, H] dense (summed in fp32, stored once per destination); gq [E, H*C] dense, row = original edge id,
- *   = d u, and d q = its segment sum over the plan of the source ids; grad_att [H*C] through the workspace of
- *   gnnops_edge_attention_v1_backward_workspace_bytes(N, H, C) bytes (host-only; fixed-order sum, the same bits every run).
- *   edge_scale is not differentiated. N == 0: nothing is written. */
+ *   = d u, and d q = its segment sum over the plan of the source ids; grad_att [H*C] through a workspace of
+ *   gnnops_edge_attention_backward_workspace_bytes(N, H, C) bytes (fixed-order sum, the same bits every run). gc [E, H] dense,
+ *   row = original edge id, = d c = d pre (one store per edge and head, no atomics): required when c is given and E > 0,
+ *   ignored otherwise. edge_scale is not differentiated. N == 0: nothing is written. */
 int gnnops_edge_attention_v1(const void* q, int64_t ldq, const void* d, int64_t ldd, const void* att, const void* u,
-                             const void* edge_scale, const int32_t* rowptr, const int32_t* perm, const int64_t* col, void* out,
-                             int64_t ldo, float* lse, int64_t N, int64_t E, int64_t H, int64_t C, int has_row_slope,
-                             float row_slope, float negative_slope, int dtype, gnnops_stream_t stream);
-size_t gnnops_edge_attention_v1_backward_workspace_bytes(int64_t N, int64_t H, int64_t C);
+                             const void* c, const void* edge_scale, const int32_t* rowptr, const int32_t* perm,
+                             const int64_t* col, void* out, int64_t ldo, float* lse, int64_t N, int64_t E, int64_t H, int64_t C,
+                             int has_row_slope, float row_slope, float negative_slope, int dtype, gnnops_stream_t stream);
 int gnnops_edge_attention_v1_backward(const void* q, int64_t ldq, const void* d, int64_t ldd, const void* att, const void* u,
-                                      const void* edge_scale, const void* out, int64_t ldo, const float* lse,
+                                      const void* c, const void* edge_scale, const void* out, int64_t ldo, const float* lse,
                                       const void* grad_out, int64_t ldg, const int32_t* rowptr, const int32_t* perm,
-                                      const int64_t* col, void* grad_d, void* gq, void* grad_att, int64_t N, int64_t E,
-                                      int64_t H, int64_t C, int has_row_slope, float row_slope, float negative_slope, int dtype,
-                                      void* workspace, size_t workspace_bytes, gnnops_stream_t stream);
-
-/* The same pass with a per-edge, per-head term in the pre-activation (GATConv with edge features: c[e,h] = att_edge[h] .
- * lin_edge(edge_attr)[e,h,:], one tiny product with att_edge folded into the weight):
- *   s[e,h] = leaky_relu(att[h,:] . r[e,h,:] + d[i,h] + c[e,h], negative_slope); the message is unchanged.
- * c [E, H] is dense, in `dtype`, its rows the ORIGINAL edge ids, read through perm exactly as edge_scale is; NULL = absent: the
- * call is gnnops_edge_attention_v1, and an all-zero c gives the same bits as that call. c and u together have no kernel
- * instance (GNNOPS_EUNSUPPORTED). E == 0 or N == 0: c is not dereferenced.
- * Backward: operands and workspace (gnnops_edge_attention_v1_c_backward_workspace_bytes, the same size) as
- *   gnnops_edge_attention_v1_backward, and gc [E, H] dense, row = original edge id, = d c = d pre (one store per edge and
- *   head, no atomics). gc is required when c is given and E > 0, ignored otherwise. */
-int gnnops_edge_attention_v1_c(const void* q, int64_t ldq, const void* d, int64_t ldd, const void* att, const void* u,
-                               const void* c, const void* edge_scale, const int32_t* rowptr, const int32_t* perm,
-                               const int64_t* col, void* out, int64_t ldo, float* lse, int64_t N, int64_t E, int64_t H, int64_t C,
-                               int has_row_slope, float row_slope, float negative_slope, int dtype, gnnops_stream_t stream);
-size_t gnnops_edge_attention_v1_c_backward_workspace_bytes(int64_t N, int64_t H, int64_t C);
-int gnnops_edge_attention_v1_c_backward(const void* q, int64_t ldq, const void* d, int64_t ldd, const void* att, const void* u,
-                                        const void* c, const void* edge_scale, const void* out, int64_t ldo, const float* lse,
-                                        const void* grad_out, int64_t ldg, const int32_t* rowptr, const int32_t* perm,
-                                        const int64_t* col, void* grad_d, void* gq, void* gc, void* grad_att, int64_t N,
-                                        int64_t E, int64_t H, int64_t C, int has_row_slope, float row_slope,
-                                        float negative_slope, int dtype, void* workspace, size_t workspace_bytes,
-                                        gnnops_stream_t stream);
+                                      const int64_t* col, void* grad_d, void* gq, void* gc, void* grad_att, int64_t N,
+                                      int64_t E, int64_t H, int64_t C, int has_row_slope, float row_slope,
+                                      float negative_slope, int dtype, void* workspace, size_t workspace_bytes,
+                                      gnnops_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
  * The remaining ops of the reference's list (ops.txt:17-19, 29-41) - SURVEY.md 8(f) rank 4. Neither package is in the

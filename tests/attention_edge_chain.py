@@ -60,7 +60,7 @@ def attention_u(q, p, att, u, edge_index, n_dst, H, slope=0.2):
 
 
 def library_backward_u(f, out_r, lse, edge_index, n_dst, H, slope, g, rnd):
-    """The steps of gnnops_edge_attention_u_backward + the segment sum of the autograd function, on float32 operands ``f``."""
+    """The steps of gnnops_edge_attention_backward (with u) + the segment sum of the autograd function, on float32 operands ``f``."""
     src, dst = edge_index[0], edge_index[1]
     q, p, att, u = f["q"], f["p"], f["att"], f["u"]
     C = att.numel() // H
@@ -113,7 +113,7 @@ def attention_c(q, d, att, c, edge_index, n_dst, H, slope=0.2):
 
 
 def library_backward_c(f, out_r, lse, edge_index, n_dst, H, slope, g, rnd):
-    """The steps of gnnops_edge_attention_v1_c_backward + the segment sum of the autograd function, on float32 operands ``f``."""
+    """The steps of gnnops_edge_attention_v1_backward (with c) + the segment sum of the autograd function, on float32 operands ``f``."""
     src, dst = edge_index[0], edge_index[1]
     q, d, att, c = f["q"], f["d"], f["att"], f["c"]
     C = att.numel() // H
