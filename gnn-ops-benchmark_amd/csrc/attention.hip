@@ -787,6 +787,321 @@ __global__ __launch_bounds__(256) void gate_bwd_kernel(const GateArgs a) {
     }
 }
 
+// ---- TransformerConv: scaled dot-product attention ---------------------------------------------------------------------------
+// The third member (gnnops.conv.edge_attention_dot: TransformerConv, Shi et al. 2021). The score is a dot product of the destination's
+// query row with the edge's key row, and the message is a second gathered row, the value:
+//   kk[e,h,:] = k[j,h,:] (+ u[e,h,:])      vv[e,h,:] = v[j,h,:] (+ u[e,h,:])      s[e,h] = scale * qry[i,h,:] . kk[e,h,:]
+//   out[i,h,:] = sum_{e into i} exp(s[e,h] - lse[i,h]) * ks[e,h] * vv[e,h,:]
+// k and v are two pointers into rows of one pitch (two column blocks of one product), so an edge has one row base for both; u
+// [E, H * C] and ks [E, H] (the attention dropout scale, in the weighted sum only) are read through perm as the gate kernels' are.
+// The same layout, id hand-out, group sums and online softmax as above; the qry row of the destination is held as p is. There is
+// no att vector: the backward has no partial sums across destinations, no second kernel and no workspace, and takes the forward's
+// grid. It writes ONE [E, 2 * H * C] tensor gkv, row = original edge id: the k half ds * scale * qry[i], the v half a * ks * g[i]
+// (d k and d v = one segment sum over the source plan), with u also gu = the sum of the halves; d qry is summed in registers.
+struct DotArgs {
+    const void *qry, *k, *v, *u, *ks, *g, *o;   // u [E, H * C], ks [E, H] (edge_scale): rows = ORIGINAL edge ids, either may be null
+    void* gu;                                   // d u [E, H * C], rows = original edge ids (backward with u only)
+    const int32_t *rowptr, *perm;
+    const int64_t* col;
+    void *out, *dq, *gkv;                       // dq: d qry [N, H * C]; gkv [E, 2 * H * C], rows = original edge ids
+    float* lse;
+    int64_t N, ldq, ldkv, ldo, ldg;
+    int H, C, gshift, hblocks, nwaves;
+    float scale;
+};
+
+// edges per step: an edge brings two raw rows, three with u, and every raw row of a step is in flight before the first is consumed.
+// Forward 8 / 12 pieces per lane in flight (AttUnroll holds 8 / 8 + 4); backward, where an edge also stores two or three rows, half.
+template <int NCH, bool HASU> struct DotUnroll {
+    static constexpr int FW = NCH == 1 ? 4 : NCH == 2 ? 2 : 1;
+    static constexpr int BW = HASU ? 1 : (NCH == 1 ? 2 : 1);
+};
+
+template <typename T, int VEC, int NCH, bool HASU>
+__global__ __launch_bounds__(256) void dot_fwd_kernel(const DotArgs a) {
+    constexpr int U = DotUnroll<NCH, HASU>::FW;
+    constexpr bool HOLD = NCH <= 4;   // the qry pieces stay in registers
+    const T* __restrict__ qry = (const T*)a.qry;
+    const T* __restrict__ kp = (const T*)a.k;
+    const T* __restrict__ vp = (const T*)a.v;
+    const T* __restrict__ ue = (const T*)a.u;
+    const T* __restrict__ ks = (const T*)a.ks;
+    const int64_t* __restrict__ col = a.col;
+    const int32_t* __restrict__ perm = a.perm;
+    const int wave = __builtin_amdgcn_readfirstlane((int)(((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6));
+    const int64_t items = a.N * a.hblocks;
+    const int ldkv = (int)a.ldkv;
+    const int HC = a.H * a.C;
+    const float sc = a.scale;
+    const bool by_edge = HASU || ks != nullptr;   // something is read by original edge id
+    const float NEG_INF = -__builtin_huge_valf();
+    for (int64_t it = wave; it < items; it += a.nwaves) {
+        const int i = __builtin_amdgcn_readfirstlane((int)(it / a.hblocks));
+        const int hb = __builtin_amdgcn_readfirstlane((int)(it % a.hblocks));
+        const Place pl(a.gshift, a.H, a.C, hb);
+        const int lane = pl.lane;
+        const int hk = pl.head_ok ? pl.h : 0;
+        const int32_t jb = __builtin_amdgcn_readfirstlane(a.rowptr[i]), je = __builtin_amdgcn_readfirstlane(a.rowptr[i + 1]);
+        float qv[HOLD ? NCH : 1][VEC];
+        if constexpr (HOLD) {
+#pragma unroll
+            for (int k = 0; k < NCH; ++k) att_unpack<T, VEC>(att_load_raw<T, VEC>(qry + (int64_t)i * a.ldq + pl.off<VEC>(k)), qv[k]);
+        }
+        float acc[NCH][VEC];
+#pragma unroll
+        for (int k = 0; k < NCH; ++k)
+#pragma unroll
+            for (int v = 0; v < VEC; ++v) acc[k][v] = 0.f;
+        float m = NEG_INF, l = 0.f;
+        for (int32_t jrun = jb; jrun < je; jrun += 64) {
+            const int32_t jrun_end = min(jrun + 64, je);
+            int cl = 0, el = 0;
+            if (jrun + lane < je) {
+                cl = (int)col[jrun + lane];   // one coalesced load: lane l holds id l of the run
+                if (by_edge) el = perm ? perm[jrun + lane] : jrun + lane;
+            }
+            for (int32_t j = jrun; j < jrun_end; j += U) {
+                int64_t srow[U], erow[HASU ? U : 1], krow[U];
+#pragma unroll
+                for (int u = 0; u < U; ++u) {
+                    srow[u] = (int64_t)__builtin_amdgcn_readlane(cl, (j - jrun + u) & 63) * ldkv;   // one base for the k and the v row
+                    asm volatile("" : "+s"(srow[u]));   // the row bases are computed HERE, ahead of every row load
+                    krow[u] = 0;
+                    if (by_edge) {
+                        const int64_t e = __builtin_amdgcn_readlane(el, (j - jrun + u) & 63);
+                        krow[u] = e * a.H;
+                        if constexpr (HASU) {
+                            erow[u] = e * HC;
+                            asm volatile("" : "+s"(erow[u]));
+                        }
+                    }
+                }
+                u32x4 kr[U][NCH], vr[U][NCH], ur[HASU ? U : 1][HASU ? NCH : 1];
+                float kv[U];
+#pragma unroll
+                for (int u = 0; u < U; ++u) {           // every row load of the step in flight before the first is consumed
+                    kv[u] = 1.f;
+                    if (j + u < jrun_end) {
+#pragma unroll
+                        for (int k = 0; k < NCH; ++k) {
+                            if (!pl.live<VEC>(k)) continue;
+                            kr[u][k] = att_load_raw<T, VEC>(kp + srow[u] + pl.off<VEC>(k));
+                            vr[u][k] = att_load_raw<T, VEC>(vp + srow[u] + pl.off<VEC>(k));
+                            if constexpr (HASU) ur[u][k] = att_load_raw<T, VEC>(ue + erow[HASU ? u : 0] + pl.off<VEC>(k));
+                        }
+                        if (ks) kv[u] = gate_scalar<T>(ks + krow[u] + hk);
+                    }
+                }
+                float s[U];
+#pragma unroll
+                for (int u = 0; u < U; ++u) {
+                    s[u] = 0.f;
+                    if (j + u < jrun_end) {
+                        float part = 0.f;
+#pragma unroll
+                        for (int k = 0; k < NCH; ++k) {
+                            if (!pl.live<VEC>(k)) continue;
+                            float t[VEC], qk[VEC];
+                            gate_row<T, VEC, HASU>(kr[u][k], ur[HASU ? u : 0][HASU ? k : 0], t);
+                            if constexpr (!HOLD) att_unpack<T, VEC>(att_load_raw<T, VEC>(qry + (int64_t)i * a.ldq + pl.off<VEC>(k)), qk);
+                            float sub = 0.f;
+#pragma unroll
+                            for (int v = 0; v < VEC; ++v) sub += (HOLD ? qv[k][v] : qk[v]) * t[v];
+                            part += pl.ok<VEC>(k) ? sub : 0.f;
+                        }
+                        s[u] = sc * group_sum(part, a.gshift, lane);
+                    }
+                }
+                float mn = m;
+#pragma unroll
+                for (int u = 0; u < U; ++u)
+                    if (j + u < jrun_end) mn = fmaxf(mn, s[u]);
+                const float scale = expf(m - mn);   // 0 on the first step (m = -inf): nothing to rescale yet
+                m = mn;
+                l = l * scale;
+#pragma unroll
+                for (int k = 0; k < NCH; ++k)
+#pragma unroll
+                    for (int v = 0; v < VEC; ++v) acc[k][v] = acc[k][v] * scale;
+#pragma unroll
+                for (int u = 0; u < U; ++u) {
+                    if (j + u < jrun_end) {
+                        const float w = expf(s[u] - mn);
+                        l = l + w;                      // the denominator never sees the scale: dropout comes after the softmax
+                        const float wk = w * kv[u];
+#pragma unroll
+                        for (int k = 0; k < NCH; ++k) {
+                            if (!pl.live<VEC>(k)) continue;
+                            float t[VEC];
+                            gate_row<T, VEC, HASU>(vr[u][k], ur[HASU ? u : 0][HASU ? k : 0], t);
+#pragma unroll
+                            for (int v = 0; v < VEC; ++v) acc[k][v] = acc[k][v] + wk * t[v];
+                        }
+                    }
+                }
+            }
+        }
+        const bool any = je > jb;
+#pragma unroll
+        for (int k = 0; k < NCH; ++k) {
+            if (!pl.live<VEC>(k)) continue;
+            float o[VEC];
+#pragma unroll
+            for (int v = 0; v < VEC; ++v) o[v] = any ? acc[k][v] / l : 0.f;
+            if (pl.ok<VEC>(k)) att_store<T, VEC>((T*)a.out + (int64_t)i * a.ldo + pl.off<VEC>(k), o);
+        }
+        if (pl.head_ok && pl.gl == 0) a.lse[(int64_t)i * a.H + pl.h] = any ? m + logf(l) : NEG_INF;
+    }
+}
+
+// Backward: the forward's walk (one wave per destination and head block, any wave any head block: nothing is carried from one
+// destination to the next). Every edge stands alone: s is recomputed, a = exp(s - lse), ds = a * (ks * (g . vv) - D).
+template <typename T, int VEC, int NCH, bool HASU>
+__global__ __launch_bounds__(256) void dot_bwd_kernel(const DotArgs a) {
+    constexpr int U = DotUnroll<NCH, HASU>::BW;
+    constexpr bool HOLD = NCH <= 4;   // the qry and g pieces stay in registers
+    const T* __restrict__ qry = (const T*)a.qry;
+    const T* __restrict__ kp = (const T*)a.k;
+    const T* __restrict__ vp = (const T*)a.v;
+    const T* __restrict__ ue = (const T*)a.u;
+    const T* __restrict__ ks = (const T*)a.ks;
+    const T* __restrict__ g = (const T*)a.g;
+    const T* __restrict__ o = (const T*)a.o;
+    const int64_t* __restrict__ col = a.col;
+    const int32_t* __restrict__ perm = a.perm;
+    const int wave = __builtin_amdgcn_readfirstlane((int)(((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6));
+    const int64_t items = a.N * a.hblocks;
+    const int ldkv = (int)a.ldkv;
+    const int HC = a.H * a.C;
+    const float sc = a.scale;
+    for (int64_t it = wave; it < items; it += a.nwaves) {
+        const int i = __builtin_amdgcn_readfirstlane((int)(it / a.hblocks));
+        const int hb = __builtin_amdgcn_readfirstlane((int)(it % a.hblocks));
+        const Place pl(a.gshift, a.H, a.C, hb);
+        const int lane = pl.lane;
+        const int hk = pl.head_ok ? pl.h : 0;
+        const int32_t jb = __builtin_amdgcn_readfirstlane(a.rowptr[i]), je = __builtin_amdgcn_readfirstlane(a.rowptr[i + 1]);
+        float qv[HOLD ? NCH : 1][VEC], gv[HOLD ? NCH : 1][VEC], dq[NCH][VEC];
+        float dpart = 0.f;
+#pragma unroll
+        for (int k = 0; k < NCH; ++k) {
+#pragma unroll
+            for (int v = 0; v < VEC; ++v) dq[k][v] = 0.f;
+            if (!pl.live<VEC>(k)) continue;
+            float gk[VEC], ok_[VEC];
+            att_unpack<T, VEC>(att_load_raw<T, VEC>(g + (int64_t)i * a.ldg + pl.off<VEC>(k)), gk);
+            att_unpack<T, VEC>(att_load_raw<T, VEC>(o + (int64_t)i * a.ldo + pl.off<VEC>(k)), ok_);
+            float sub = 0.f;
+#pragma unroll
+            for (int v = 0; v < VEC; ++v) sub += gk[v] * ok_[v];
+            dpart += pl.ok<VEC>(k) ? sub : 0.f;
+            if constexpr (HOLD) {
+                att_unpack<T, VEC>(att_load_raw<T, VEC>(qry + (int64_t)i * a.ldq + pl.off<VEC>(k)), qv[k]);
+#pragma unroll
+                for (int v = 0; v < VEC; ++v) gv[k][v] = gk[v];
+            }
+        }
+        const float delta = group_sum(dpart, a.gshift, lane);                    // D = sum_c g * out of this head
+        const float lse = pl.head_ok ? a.lse[(int64_t)i * a.H + pl.h] : 0.f;
+        for (int32_t jrun = jb; jrun < je; jrun += 64) {
+            const int32_t jrun_end = min(jrun + 64, je);
+            int cl = 0, el = 0;
+            if (jrun + lane < je) {
+                cl = (int)col[jrun + lane];
+                el = perm ? perm[jrun + lane] : jrun + lane;
+            }
+            for (int32_t j = jrun; j < jrun_end; j += U) {
+                int64_t srow[U], erow[U], krow[U];
+#pragma unroll
+                for (int u = 0; u < U; ++u) {
+                    srow[u] = (int64_t)__builtin_amdgcn_readlane(cl, (j - jrun + u) & 63) * ldkv;
+                    const int64_t e = __builtin_amdgcn_readlane(el, (j - jrun + u) & 63);
+                    erow[u] = e * HC;                   // always: the row of gkv is 2 * erow
+                    krow[u] = ks ? e * a.H : 0;
+                    asm volatile("" : "+s"(srow[u]));
+                    asm volatile("" : "+s"(erow[u]));
+                }
+                u32x4 kr[U][NCH], vr[U][NCH], ur[HASU ? U : 1][HASU ? NCH : 1];
+                float kv[U];
+#pragma unroll
+                for (int u = 0; u < U; ++u) {
+                    kv[u] = 1.f;
+                    if (j + u < jrun_end) {
+#pragma unroll
+                        for (int k = 0; k < NCH; ++k) {
+                            if (!pl.live<VEC>(k)) continue;
+                            kr[u][k] = att_load_raw<T, VEC>(kp + srow[u] + pl.off<VEC>(k));
+                            vr[u][k] = att_load_raw<T, VEC>(vp + srow[u] + pl.off<VEC>(k));
+                            if constexpr (HASU) ur[u][k] = att_load_raw<T, VEC>(ue + erow[u] + pl.off<VEC>(k));
+                        }
+                        if (ks) kv[u] = gate_scalar<T>(ks + krow[u] + hk);
+                    }
+                }
+#pragma unroll
+                for (int u = 0; u < U; ++u) {
+                    if (j + u >= jrun_end) continue;
+                    float spart = 0.f, dapart = 0.f;
+#pragma unroll
+                    for (int k = 0; k < NCH; ++k) {
+                        if (!pl.live<VEC>(k)) continue;
+                        float tk[VEC], tv[VEC], qk[VEC], gk[VEC];
+                        gate_row<T, VEC, HASU>(kr[u][k], ur[HASU ? u : 0][HASU ? k : 0], tk);
+                        gate_row<T, VEC, HASU>(vr[u][k], ur[HASU ? u : 0][HASU ? k : 0], tv);
+                        if constexpr (!HOLD) {
+                            att_unpack<T, VEC>(att_load_raw<T, VEC>(qry + (int64_t)i * a.ldq + pl.off<VEC>(k)), qk);
+                            att_unpack<T, VEC>(att_load_raw<T, VEC>(g + (int64_t)i * a.ldg + pl.off<VEC>(k)), gk);
+                        }
+                        float s1 = 0.f, s2 = 0.f;
+#pragma unroll
+                        for (int v = 0; v < VEC; ++v) {
+                            s1 += (HOLD ? qv[k][v] : qk[v]) * tk[v];
+                            s2 += (HOLD ? gv[k][v] : gk[v]) * tv[v];
+                        }
+                        const bool ok = pl.ok<VEC>(k);
+                        spart += ok ? s1 : 0.f;
+                        dapart += ok ? s2 : 0.f;
+                    }
+                    const float s = sc * group_sum(spart, a.gshift, lane);
+                    const float da = kv[u] * group_sum(dapart, a.gshift, lane);
+                    const float w = expf(s - lse);
+                    const float ds = w * (da - delta);
+                    const float dss = ds * sc, wk = w * kv[u];
+#pragma unroll
+                    for (int k = 0; k < NCH; ++k) {
+                        if (!pl.live<VEC>(k)) continue;
+                        float tk[VEC], qk[VEC], gk[VEC], rk[VEC], rv[VEC], ru[VEC];
+                        gate_row<T, VEC, HASU>(kr[u][k], ur[HASU ? u : 0][HASU ? k : 0], tk);
+                        if constexpr (!HOLD) {
+                            att_unpack<T, VEC>(att_load_raw<T, VEC>(qry + (int64_t)i * a.ldq + pl.off<VEC>(k)), qk);
+                            att_unpack<T, VEC>(att_load_raw<T, VEC>(g + (int64_t)i * a.ldg + pl.off<VEC>(k)), gk);
+                        }
+#pragma unroll
+                        for (int v = 0; v < VEC; ++v) {
+                            dq[k][v] = dq[k][v] + ds * tk[v];
+                            rk[v] = dss * (HOLD ? qv[k][v] : qk[v]);
+                            rv[v] = wk * (HOLD ? gv[k][v] : gk[v]);
+                            ru[v] = rk[v] + rv[v];
+                        }
+                        if (pl.ok<VEC>(k)) {
+                            att_store<T, VEC>((T*)a.gkv + 2 * erow[u] + pl.off<VEC>(k), rk);
+                            att_store<T, VEC>((T*)a.gkv + 2 * erow[u] + HC + pl.off<VEC>(k), rv);
+                            if constexpr (HASU) att_store<T, VEC>((T*)a.gu + erow[u] + pl.off<VEC>(k), ru);   // d u, row = original edge id
+                        }
+                    }
+                }
+            }
+        }
+#pragma unroll
+        for (int k = 0; k < NCH; ++k) {
+            if (!pl.live<VEC>(k) || !pl.ok<VEC>(k)) continue;
+            float r[VEC];
+#pragma unroll
+            for (int v = 0; v < VEC; ++v) r[v] = sc * dq[k][v];
+            att_store<T, VEC>((T*)a.dq + (int64_t)i * HC + pl.off<VEC>(k), r);
+        }
+    }
+}
+
 struct Geometry { int vec, nch, gshift, hblocks; };
 
 // widest piece the operands allow, narrowed while the heads of a row leave half the wave idle; NCH pieces per lane
@@ -854,6 +1169,20 @@ struct GateFamily {
         if (a.c) run<T, BW, VEC, NCH, false, true>(a, grid, stream);
         else if (a.u) run<T, BW, VEC, NCH, true, false>(a, grid, stream);
         else run<T, BW, VEC, NCH, false, false>(a, grid, stream);
+    }
+};
+
+struct DotFamily {
+    using Args = DotArgs;
+    template <typename T, bool BW, int VEC, int NCH, bool HASU>
+    static void run(const Args& a, int grid, hipStream_t stream) {
+        if constexpr (BW) hipLaunchKernelGGL((dot_bwd_kernel<T, VEC, NCH, HASU>), dim3(grid), dim3(256), 0, stream, a);
+        else hipLaunchKernelGGL((dot_fwd_kernel<T, VEC, NCH, HASU>), dim3(grid), dim3(256), 0, stream, a);
+    }
+    template <typename T, bool BW, int VEC, int NCH>
+    static void launch(const Args& a, int grid, hipStream_t stream) {
+        if (a.u) run<T, BW, VEC, NCH, true>(a, grid, stream);
+        else run<T, BW, VEC, NCH, false>(a, grid, stream);
     }
 };
 
@@ -1048,4 +1377,58 @@ extern "C" int gnnops_edge_attention_v1_backward(const void* q, int64_t ldq, con
     launch<GateFamily, true>(a, l.geo, l.grid, dtype, (hipStream_t)s);
     launch_datt(a.partial, l.rows, (int)(H * C), grad_att, dtype, (hipStream_t)s);
     return gnnops_check_launch("edge_attention_v1_backward");
+}
+
+// The third family has no att vector, hence no d att partials and no workspace: its backward walks the forward's grid, one wave
+// per (destination, head block), and both directions take forward_prologue (the gathered pitch ldkv where the others pass ldq, the
+// pitch of qry where the first family passes ldp). orphan as in backward_prologue.
+namespace {
+int dot_prologue(const char* what, int64_t N, int64_t E, int64_t H, int64_t C, int64_t ldq, int64_t ldkv, bool pitches, bool pointers,
+                 const char* orphan, int dtype, Operands operands, Launch* l) {
+    const int rc = forward_prologue(what, N, E, H, C, ldkv, ldq, pitches, false, pointers, dtype, operands, l);
+    if (rc != GNNOPS_OK || !l->grid) return rc;
+    GNNOPS_REQUIRE(ldq < ((int64_t)1 << 31), GNNOPS_EUNSUPPORTED, "%s: N, E and the row pitch must be < 2^31", what);
+    GNNOPS_REQUIRE(!orphan, GNNOPS_EINVAL, "%s: %s without a place for its gradient", what, orphan);
+    return GNNOPS_OK;
+}
+}  // namespace
+
+extern "C" int gnnops_edge_attention_dot(const void* qry, int64_t ldq, const void* k, const void* v, int64_t ldkv, const void* u,
+                                         const void* edge_scale, const int32_t* rowptr, const int32_t* perm, const int64_t* col,
+                                         void* out, int64_t ldo, float* lse, int64_t N, int64_t E, int64_t H, int64_t C, float scale,
+                                         int dtype, gnnops_stream_t s) {
+    if (E == 0) u = edge_scale = nullptr;   // no edge: neither is read
+    Launch l{};
+    const int rc = dot_prologue("edge_attention_dot", N, E, H, C, ldq, ldkv, ldo >= H * C,
+                                rowptr && out && lse && qry && (E == 0 || (k && v && col)), nullptr, dtype,
+                                {{qry, ldq}, {k, ldkv}, {v, ldkv}, {u, H * C}, {out, ldo}}, &l);
+    if (rc != GNNOPS_OK || !l.grid) return rc;
+    DotArgs a{};
+    a.qry = qry; a.k = k; a.v = v; a.u = u; a.ks = edge_scale; a.rowptr = rowptr; a.perm = perm; a.col = col; a.out = out; a.lse = lse;
+    a.N = N; a.ldq = ldq; a.ldkv = ldkv; a.ldo = ldo; a.H = (int)H; a.C = (int)C; a.scale = scale;
+    a.gshift = l.geo.gshift; a.hblocks = l.geo.hblocks; a.nwaves = l.nwaves;
+    launch<DotFamily, false>(a, l.geo, l.grid, dtype, (hipStream_t)s);
+    return gnnops_check_launch("edge_attention_dot");
+}
+
+extern "C" int gnnops_edge_attention_dot_backward(const void* qry, int64_t ldq, const void* k, const void* v, int64_t ldkv, const void* u,
+                                                  const void* edge_scale, const void* out, int64_t ldo, const float* lse,
+                                                  const void* grad_out, int64_t ldg, const int32_t* rowptr, const int32_t* perm,
+                                                  const int64_t* col, void* grad_qry, void* gkv, void* gu, int64_t N, int64_t E, int64_t H,
+                                                  int64_t C, float scale, int dtype, gnnops_stream_t s) {
+    if (E == 0) u = edge_scale = nullptr;   // no edge: neither is read, gu never written
+    Launch l{};
+    const int rc = dot_prologue("edge_attention_dot_backward", N, E, H, C, ldq, ldkv, ldo >= H * C && (ldg >= H * C || ldg == 0),
+                                rowptr && out && lse && qry && grad_out && grad_qry && (E == 0 || (k && v && col && gkv)),
+                                u && !gu ? "u" : nullptr, dtype,
+                                {{qry, ldq}, {k, ldkv}, {v, ldkv}, {u, H * C}, {out, ldo}, {grad_out, ldg}, {grad_qry, H * C}, {gkv, 2 * H * C},
+                                 {u ? gu : nullptr, H * C}}, &l);
+    if (rc != GNNOPS_OK || !l.grid) return rc;
+    DotArgs a{};
+    a.qry = qry; a.k = k; a.v = v; a.u = u; a.ks = edge_scale; a.g = grad_out; a.o = out; a.rowptr = rowptr; a.perm = perm; a.col = col;
+    a.dq = grad_qry; a.gkv = gkv; a.gu = gu; a.lse = const_cast<float*>(lse);
+    a.N = N; a.ldq = ldq; a.ldkv = ldkv; a.ldo = ldo; a.ldg = ldg; a.H = (int)H; a.C = (int)C; a.scale = scale;
+    a.gshift = l.geo.gshift; a.hblocks = l.geo.hblocks; a.nwaves = l.nwaves;
+    launch<DotFamily, true>(a, l.geo, l.grid, dtype, (hipStream_t)s);
+    return gnnops_check_launch("edge_attention_dot_backward");
 }

@@ -112,6 +112,10 @@ SIGNATURES = {
                                        ctypes.c_float, ctypes.c_float, _ci, _vp]),
     "gnnops_edge_attention_v1_backward": (_ci, [_vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp,
                                                 _vp, _vp, _i64, _i64, _i64, _i64, _ci, ctypes.c_float, ctypes.c_float, _ci, _vp, _sz, _vp]),
+    "gnnops_edge_attention_dot": (_ci, [_vp, _i64, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _i64, _i64, _i64,
+                                        ctypes.c_float, _ci, _vp]),
+    "gnnops_edge_attention_dot_backward": (_ci, [_vp, _i64, _vp, _vp, _i64, _vp, _vp, _vp, _i64, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp,
+                                                 _i64, _i64, _i64, _i64, ctypes.c_float, _ci, _vp]),
     "gnnops_spline_basis": (_ci, [_vp, _vp, _vp, _i64, _ci, _ci, _vp, _vp, _ci, _vp]),
     "gnnops_spline_weighting": (_ci, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _ci, _vp]),
     "gnnops_spline_conv": (_ci, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _ci, _ci, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _ci, _ci, _vp]),

@@ -27,6 +27,8 @@ on the second member of that family, `edge_attention_v1`: per-edge rows, a leaky
 Edge features: `GATv2Conv(edge_dim=)` adds u = lin_edge(edge_attr) to the score's pre-activation (`edge_attention(..., u=)`), `GATConv(edge_dim=)`
 adds the scalar att_edge . lin_edge(edge_attr) per head from one product with the folded weight (`edge_attention_v1(..., edge_score=)`); both
 are compile-time instances of the same two passes and train through them.
+`TransformerConv` (scaled dot-product attention, PyG's layer of UniMP) runs on the third member, `edge_attention_dot`: the score is
+qry[i] . k[j], the message a second gathered row v[j], per-edge rows add to both, attention dropout after the softmax.
 
 The GATv2 MODEL (the reference's GATv2REG) is `GATv2`: per layer the product, the attention pass and ONE `head_act_norm` pass
 (csrc/norm.hip: mean over heads + bias + ReLU + feature-dropout mask + LayerNorm, trainable), then gnnops.pool.global_mean_pool.
@@ -1407,6 +1409,186 @@ class AttentiveFP(torch.nn.Module):
             out = self.mol_gru(h, out).relu()
         out = F.dropout(out, p=self.dropout, training=self.training)
         return self.lin2(out)
+
+
+# ---- attention: TransformerConv (csrc/attention.hip, dot_fwd_kernel / dot_bwd_kernel) ----------------------------------------
+def _dot_operands(qry, k, v, edge_index, num_dst, heads, u, edge_scale):
+    op = "edge_attention_dot"
+    _require_gpu(qry, k, v, edge_index, u, edge_scale)
+    if qry.dim() != 2 or k.dim() != 2 or v.dim() != 2:
+        raise RuntimeError(f"{op}: qry, k and v must be 2-D")
+    HC = qry.size(1)
+    if HC > 8192:
+        raise RuntimeError(f"{op}: heads * channels = {HC} exceeds the row limit of 8192")
+    if v.dtype != k.dtype:
+        raise RuntimeError(f"{op}: operands must have the same dtype")
+    if v.size(0) != k.size(0):
+        raise RuntimeError(f"{op}: k and v must have one row per source each, got {k.size(0)} and {v.size(0)}")
+    width = torch.empty(HC, dtype=k.dtype, device="meta")     # this pass has no att: only its size and type are asked for
+    k, ldkv, qry, ldq, _, (u, edge_scale), edge_index, src_rows, plan, col, E, HC = _attention_prepare(
+        op, k, width, edge_index, num_dst, heads, (qry, "qry", "heads * channels", "one row per destination"),
+        [(u, "u", "heads * channels"), (edge_scale, "edge_scale", "heads")])
+    v, ldv = _rows(v, "v", 1, HC, op=op)
+    if ldv != ldkv:           # the kernel reads both rows of a source from one row base: two blocks of one matrix, or two dense copies
+        k, v, ldkv = k[:, :HC].contiguous(), v[:, :HC].contiguous(), HC
+    if edge_scale is not None:
+        edge_scale = edge_scale.detach()
+    return qry, ldq, k, v, ldkv, u, edge_scale, edge_index, src_rows, plan, col, E, HC
+
+
+def _dot_scale(scale, HC, heads):
+    return float(scale) if scale is not None else 1.0 / float(max(HC // max(heads, 1), 1)) ** 0.5
+
+
+def _dot_forward(qry, k, v, edge_index, num_dst, heads, scale=None, u=None, edge_scale=None, identity_perm=False):
+    """(out [num_dst, H * C], lse fp32 [num_dst, H]) of one launch of gnnops_edge_attention_dot.
+    identity_perm: the caller knows the edge list to be sorted by destination already; the per-edge operands are read without perm."""
+    qry, ldq, k, v, ldkv, u, ks, edge_index, _, plan, col, E, HC = _dot_operands(qry, k, v, edge_index, num_dst, heads, u, edge_scale)
+    out = torch.empty((num_dst, HC), dtype=k.dtype, device=k.device)
+    lse = torch.empty((num_dst, heads), dtype=torch.float32, device=k.device)
+    perm = None if identity_perm or (u is None and ks is None) else plan.perm.data_ptr()   # only u and edge_scale are read through it
+    with _on(k.device):
+        check(_lib.load().gnnops_edge_attention_dot(qry.data_ptr(), ldq, k.data_ptr(), v.data_ptr(), ldkv, _ptr(u), _ptr(ks), plan.rowptr.data_ptr(),
+                                                    perm, col.data_ptr(), out.data_ptr(), HC, lse.data_ptr(), num_dst, E, heads, HC // heads,
+                                                    _dot_scale(scale, HC, heads), _dtype_code(k, "edge_attention_dot"), _stream()),
+              "edge_attention_dot")
+    return out, lse
+
+
+def _dot_backward(qry0, k0, v0, u0, ks0, edge_index, out, lse, grad_out, num_dst, heads, scale, identity_perm=False):
+    """(gkv [E, 2 * H * C] or None, d qry [num_dst, H * C], d u [E, H * C] or None, src_rows, edge_index) of one launch of
+    gnnops_edge_attention_dot_backward; None where there is no edge."""
+    qry, ldq, k, v, ldkv, u, ks, edge_index, src_rows, plan, col, E, HC = _dot_operands(qry0, k0, v0, edge_index, num_dst, heads, u0, ks0)
+    if E == 0 or num_dst == 0:
+        return None, None, None, src_rows, edge_index
+    g, ldg = _grad_rows(grad_out, HC, "edge_attention_dot")
+    d_qry = torch.empty((num_dst, HC), dtype=k.dtype, device=k.device)
+    gkv = torch.empty((E, 2 * HC), dtype=k.dtype, device=k.device)
+    d_u = None if u is None else torch.empty((E, HC), dtype=k.dtype, device=k.device)
+    perm = None if identity_perm else plan.perm.data_ptr()
+    with _on(k.device):
+        check(_lib.load().gnnops_edge_attention_dot_backward(qry.data_ptr(), ldq, k.data_ptr(), v.data_ptr(), ldkv, _ptr(u), _ptr(ks), out.data_ptr(),
+                                                             HC, lse.data_ptr(), g.data_ptr(), ldg, plan.rowptr.data_ptr(), perm, col.data_ptr(),
+                                                             d_qry.data_ptr(), gkv.data_ptr(), _ptr(d_u), num_dst, E, heads, HC // heads,
+                                                             _dot_scale(scale, HC, heads), _dtype_code(k, "edge_attention_dot"), _stream()),
+              "edge_attention_dot_backward")
+    return gkv, d_qry, d_u, src_rows, edge_index
+
+
+def edge_attention_dot(qry, k, v, edge_index, num_dst, heads, scale=None, u=None, edge_scale=None):
+    """out[i, h, :] = sum over the edges e = (j -> i) of softmax_e(s[e, h]) * edge_scale[e, h] * (v[j, h] + u[e, h]), with
+    s[e, h] = scale * qry[i, h] . (k[j, h] + u[e, h]): scaled dot-product attention over the edges of a destination, TransformerConv's
+    message and aggregation in one pass with an online softmax (csrc/attention.hip). qry [num_dst, H * C], k and v [N_src, H * C] may be
+    column blocks of wider products and are read in place (k and v of different pitches are copied: the kernel reads both from one
+    row base); scale defaults to 1 / sqrt(C); u [E, H * C] and edge_scale [E, H] follow the order of edge_index. edge_scale (the
+    attention dropout mask divided by 1 - p) multiplies the weighted sum only, never the softmax denominator, and is not
+    differentiated. A destination without edges gets a zero row. Differentiable in qry, k, v and u."""
+    if _wants_grad(qry, k, v, u):
+        return _EdgeAttentionDot.apply(qry, k, v, u, edge_scale, edge_index, num_dst, heads, scale)
+    return _dot_forward(qry, k, v, edge_index, num_dst, heads, scale, u, edge_scale)[0]
+
+
+class _EdgeAttentionDot(torch.autograd.Function):
+    """backward (gnnops_edge_attention_dot_backward, destination-ordered like the forward): d qry from the kernel, and one per-edge
+    tensor gkv [E, 2 * H * C] in edge order whose ONE segment sum over the plan of the source ids is [d k | d v]. With u a second
+    per-edge tensor in edge order is d u."""
+
+    @staticmethod
+    def forward(ctx, qry, k, v, u, edge_scale, edge_index, num_dst, heads, scale):
+        out, lse = _dot_forward(qry, k, v, edge_index, num_dst, heads, scale, u, edge_scale)
+        ctx.meta = (num_dst, heads, scale, u is not None, edge_scale is not None)
+        ctx.save_for_backward(qry, k, v, edge_index, out, lse, *(t for t in (u, edge_scale) if t is not None))
+        return out
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        qry0, k0, v0, edge_index, out, lse, *rest = ctx.saved_tensors
+        num_dst, heads, scale, has_u, has_ks = ctx.meta
+        u0 = rest.pop(0) if has_u else None
+        ks0 = rest.pop(0) if has_ks else None
+        need_qry, need_k, need_v, need_u = ctx.needs_input_grad[:4]
+        tail = (None,) * 5
+        gkv, d_qry, d_u, src_rows, edge_index = _dot_backward(qry0, k0, v0, u0, ks0, edge_index, out, lse, grad_out, num_dst, heads, scale)
+        if gkv is None:
+            return (torch.zeros_like(qry0) if need_qry else None, torch.zeros_like(k0) if need_k else None,
+                    torch.zeros_like(v0) if need_v else None, torch.zeros_like(u0) if has_u and need_u else None) + tail
+        HC = d_qry.size(1)
+        both = torch.empty((k0.size(0), 2 * HC), device="meta")     # the shape of [d k | d v]: one segment sum, no padding
+        d_kv, d_qry = _attention_tail(gkv, d_qry, src_rows, edge_index, both, qry0, need_k or need_v, need_qry)
+        pad = lambda d, t: d if t.size(1) == HC else torch.nn.functional.pad(d, (0, t.size(1) - HC))   # noqa: E731
+        return (d_qry, pad(d_kv[:, :HC], k0) if need_k else None, pad(d_kv[:, HC:], v0) if need_v else None,
+                d_u if has_u and need_u else None) + tail
+
+
+class TransformerConv(_Layer):
+    """x'_i = W_skip x_i + sum_j alpha_ij (W_v x_j + W_e e_ij),  alpha_ij = softmax_j((W_q x_i) . (W_k x_j + W_e e_ij) / sqrt(C))  per head
+    (torch_geometric TransformerConv; UniMP, Shi et al. 2021). With one node set, ONE product x @ [W_k^T | W_v^T | W_q^T | W_skip^T]
+    whose column blocks reach the kernel in place; with a bipartite pair (x_src, x_dst), one product per side. Then one attention pass
+    (`edge_attention_dot`), the mean over heads (concat=False) and the skip: out + x_r, or with beta=True
+    beta * x_r + (1 - beta) * out, beta = sigmoid(lin_beta([out, x_r, out - x_r])), composed from torch ops (not fused). Edge features
+    (edge_dim set): lin_edge(edge_attr), without a bias, is one more product, added to the key AND to the value by the pass. Attention
+    dropout in training: a Bernoulli mask [E, H] drawn with torch, scaled by 1 / (1 - p), applied after the softmax (edge_scale); eval
+    ignores it. Parameter names and shapes follow PyG (lin_key, lin_query, lin_value, lin_edge, lin_skip, lin_beta), so a state_dict
+    moves across; parity unpinned. No self loops are added, as in PyG. `return_attention_weights` is not implemented: the argument
+    is absent, because the pass never writes the [E, H] weights."""
+
+    def __init__(self, in_channels, out_channels, heads=1, concat=True, beta=False, dropout=0.0, edge_dim=None, bias=True, root_weight=True):
+        super().__init__()
+        self.in_channels, self.out_channels, self.heads, self.concat = in_channels, out_channels, heads, concat
+        self.beta, self.dropout, self.edge_dim, self.root_weight = beta and root_weight, dropout, edge_dim, root_weight
+        in_src, in_dst = _pair(in_channels)
+        HC = heads * out_channels
+        self.lin_key = torch.nn.Linear(in_src, HC, bias=bias)
+        self.lin_query = torch.nn.Linear(in_dst, HC, bias=bias)
+        self.lin_value = torch.nn.Linear(in_src, HC, bias=bias)
+        if edge_dim is not None:       # present only with edge features, so that a state_dict without them keeps PyG's keys
+            self.lin_edge = torch.nn.Linear(edge_dim, HC, bias=False)
+        if root_weight:
+            width = HC if concat else out_channels
+            self.lin_skip = torch.nn.Linear(in_dst, width, bias=bias)
+            if self.beta:
+                self.lin_beta = torch.nn.Linear(3 * width, 1, bias=False)
+        self._pk_all, self._pk_src, self._pk_dst, self._pk_e = _Packed(), _Packed(), _Packed(), _Packed()
+
+    _edge_rows = GATv2Conv._edge_rows
+
+    def forward(self, x, edge_index, edge_attr=None):
+        H, C = self.heads, self.out_channels
+        HC = H * C
+        kv = [self.lin_key, self.lin_value]
+        qs = [self.lin_query] + ([self.lin_skip] if self.root_weight else [])
+        pack = lambda cache, lins: cache.get([m.weight for m in lins] + [m.bias for m in lins], [(m.weight, m.bias) for m in lins])   # noqa: E731
+        if isinstance(x, (tuple, list)):
+            x_src, x_dst = x
+            _require_gpu(x_src, x_dst, edge_index)
+            left = _dense(x_src.contiguous(), pack(self._pk_src, kv))
+            right = _dense(x_dst.contiguous(), pack(self._pk_dst, qs))
+            n_dst = x_dst.size(0)
+        else:       # [key | value | query | skip] = x @ [W_k^T | W_v^T | W_q^T | W_skip^T]: the projections reach the kernel as column blocks
+            _require_gpu(x, edge_index)
+            both = _dense(x.contiguous(), pack(self._pk_all, kv + qs))
+            left, right = both[:, :2 * HC], both[:, 2 * HC:]
+            n_dst = x.size(0)
+        k, v, qry = left[:, :HC], left[:, HC:], right[:, :HC]
+        rows = self._edge_rows(edge_attr, edge_index, n_dst, False)
+        u = None
+        if rows is not None:            # u = lin_edge(edge_attr): one product
+            we = self.lin_edge.weight
+            u = _edge_dense(rows, self._pk_e.get([we], [(we, None)]))
+        scale = None
+        if self.dropout > 0.0 and self.training:
+            scale = _dropout_scale(edge_index.size(1), H, self.dropout, k.dtype, k.device)
+        out = edge_attention_dot(qry, k, v, edge_index, n_dst, H, u=u, edge_scale=scale)
+        if not self.concat:
+            out = out.view(n_dst, H, C).mean(dim=1)
+        if self.root_weight:
+            x_r = right[:, HC:]
+            if self.beta:
+                beta = torch.sigmoid(torch.nn.functional.linear(torch.cat([out, x_r, out - x_r], dim=-1), self.lin_beta.weight))
+                out = beta * x_r + (1.0 - beta) * out
+            else:
+                out = out + x_r
+        return out
 
 
 # ---- GCNConv, TopKPooling and GraphUNet (csrc/gcn.hip, csrc/pool.hip) -------------------------------------------------------

@@ -703,6 +703,35 @@ int gnnops_edge_attention_v1_backward(const void* q, int64_t ldq, const void* d,
                                       float negative_slope, int dtype, void* workspace, size_t workspace_bytes,
                                       gnnops_stream_t stream);
 
+/* The third member (TransformerConv, Shi et al. 2021): scaled dot-product attention. The score is the dot product of the
+ * destination's query row with the edge's key row, the message a second gathered row, the value; all arithmetic in fp32.
+ *   kk[e,h,:] = k[j,h,:] + u[e,h,:]           vv[e,h,:] = v[j,h,:] + u[e,h,:]                               edge e = (j -> i)
+ *   s[e,h] = scale * qry[i,h,:] . kk[e,h,:]                                      lse[i,h] = log sum_{e into i} exp(s[e,h])
+ *   out[i,h,:] = sum_{e into i} exp(s[e,h] - lse[i,h]) * edge_scale[e,h] * vv[e,h,:]
+ * qry [N, >= H*C] (pitch ldq); k and v [N_src, >= H*C], two pointers into rows of ONE pitch ldkv (two column blocks of one
+ * product); out [N, H*C] (pitch ldo) in `dtype`; lse fp32 [N, H]. u [E, H*C] and edge_scale [E, H] (the attention dropout
+ * mask divided by 1 - p: in the weighted sum only, never in lse) are dense, in `dtype`, their rows the ORIGINAL edge ids (read
+ * through perm, offsets in 64 bits); NULL = absent (u = 0, edge_scale = 1), and an all-ones edge_scale gives the same bits as
+ * the call without it. Limits (H*C <= 8192; N, E and the pitches < 2^31), the plan operands and the empty destination (a zero
+ * row, lse = -inf) as gnnops_edge_attention. E == 0 or N == 0: u and edge_scale are not dereferenced. One launch, no
+ * allocation, no synchronisation, no atomics.
+ * Backward (one launch, destination-ordered, no workspace: there is no att vector to sum over destinations): grad_qry [N, H*C]
+ *   dense (summed in fp32, stored once per destination); gkv [E, 2*H*C] dense, row = original edge id: columns [0, H*C) =
+ *   ds * scale * qry[i], columns [H*C, 2*H*C) = a * edge_scale * grad_out[i], with a = exp(s - lse) and
+ *   ds = a * (edge_scale * (grad_out[i,h,:] . vv) - grad_out[i,h,:] . out[i,h,:]); [d k | d v] = its segment sum over the plan of
+ *   the source ids. gu [E, H*C] dense, row = original edge id, = d u = the sum of the two halves: required when u is given and
+ *   E > 0 (GNNOPS_EINVAL otherwise), ignored without u. ldg == 0: one gradient row for all destinations. edge_scale is not
+ *   differentiated. N == 0: nothing is written. */
+int gnnops_edge_attention_dot(const void* qry, int64_t ldq, const void* k, const void* v, int64_t ldkv, const void* u,
+                              const void* edge_scale, const int32_t* rowptr, const int32_t* perm, const int64_t* col, void* out,
+                              int64_t ldo, float* lse, int64_t N, int64_t E, int64_t H, int64_t C, float scale, int dtype,
+                              gnnops_stream_t stream);
+int gnnops_edge_attention_dot_backward(const void* qry, int64_t ldq, const void* k, const void* v, int64_t ldkv, const void* u,
+                                       const void* edge_scale, const void* out, int64_t ldo, const float* lse,
+                                       const void* grad_out, int64_t ldg, const int32_t* rowptr, const int32_t* perm,
+                                       const int64_t* col, void* grad_qry, void* gkv, void* gu, int64_t N, int64_t E, int64_t H,
+                                       int64_t C, float scale, int dtype, gnnops_stream_t stream);
+
 /* ---------------------------------------------------------------------------------------------
  * The remaining ops of the reference's list (ops.txt:17-19, 29-41) - SURVEY.md 8(f) rank 4. Neither package is in the
  * reference tree (torch-spline-conv 1.2.1, torch-cluster 1.5.9: requirements.txt:214, :210) and the reference has no
