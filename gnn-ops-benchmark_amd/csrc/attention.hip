@@ -1,51 +1,57 @@
-// attention.hip — the softmax-weighted aggregation of a GATv2 layer in ONE pass over the destination-sorted edge list, and its
-// backward (gnnops.conv.edge_attention / GATv2Conv; the reference's model zoo builds GATv2REG from GATv2Conv,
-// graph_benchmark/models/ptg_models.py:208-236, and trains it, OpProfiler.py:97-112).
-//
-//   z[e,h,c]   = p[i,h,c] + q[j,h,c]                          edge e = (j -> i)
-//   s[e,h]     = sum_c att[h,c] * leaky_relu(z[e,h,c], slope)
+// attention.hip — softmax-weighted aggregation over the destination-sorted edge list in ONE pass, and its backward, for three ways
+// of scoring an edge e = (j -> i) per head h. Common to all three:
 //   a[e,h]     = exp(s[e,h] - lse[i,h]),   lse[i,h] = log sum_{e into i} exp(s[e,h])
-//   out[i,h,:] = sum_{e into i} a[e,h] * q[j,h,:]
-//
+//   out[i,h,:] = sum_{e into i} a[e,h] * message[e,h,:]
 // The weight of an edge depends on ALL the edges of its destination, which the elementwise messages of conv.hip cannot say.
-// The forward keeps, per (destination, head), a running maximum m, a denominator l and the accumulators (online softmax):
-// a step of U edges may raise the maximum, l and the accumulators are then rescaled by exp(m_old - m_new). Each gathered q row
-// is read once and serves the score and the weighted sum; no [E, H] score and no [E, H, C] message is written.
 //
-// Layout: ONE WAVE per (destination, block of 64 / G heads), one group of G = 2^gshift lanes per head, lane gl of a group on
-// the columns (k * G + gl) * VEC .. + VEC of its head, k < NCH. The whole wave walks the same edges, so the edge loop, its
-// bounds and the row base addresses are scalar, the ids of a run of 64 edges are one coalesced load handed out by
-// v_readlane (as conv.hip's WAVE_ROW form), and the per-head dot product is a butterfly of DPP moves inside the group with every
-// lane active (quad_perm, row_half_mirror, row_mirror; groups of 32 / 64 lanes add the four row sums read by v_readlane).
+// THE WALK (its helpers stand once, next to Place; a kernel adds its score, message and gradient arithmetic).
+// Layout: ONE WAVE per (destination, block of 64 / G heads) = one item (item_of), one group of G = 2^gshift lanes per head, lane gl of
+// a group on the columns (k * G + gl) * VEC .. + VEC of its head, k < NCH (Place). The whole wave walks the same edges, so the edge
+// loop, its bounds and the row base addresses are scalar: the ids of a run of 64 edges are one coalesced load (run_ids) handed out
+// by v_readlane (run_id, as conv.hip's WAVE_ROW form), every row base of a step is taken and pinned ahead of its row loads, and
+// every raw row of a step is in flight before the first is consumed (fetch_row). The per-head dot product is a butterfly of DPP moves
+// inside the group with every lane active (group_sum of lane_group.h: quad_perm, row_half_mirror, row_mirror; groups of 32 / 64
+// lanes add the four row sums read by v_readlane). Per-edge operands (u, edge_scale, c) and per-edge results are rows of the ORIGINAL
+// edge id, read and written through perm (perm == NULL = identity) with int64 offsets.
+// Forward: per (destination, head) a running maximum m, a denominator l and the accumulators (online softmax): a step of U edges may
+// raise the maximum, l and the accumulators are then rescaled by exp(m_old - m_new) (softmax_raise); the end of a destination
+// writes acc / l and lse (store_destination). Each gathered row is read once and serves the score and the weighted sum; no [E, H]
+// score and no [E, H, C] message is written.
+// Backward (destination-ordered too, no atomics): delta = sum_c g * out per head, s recomputed from the same rows,
+// a = exp(s - lse), ds = a * (g . message - delta); per-edge gradient rows are written once, per-destination sums stay in registers.
+// A family with an att vector sums d att per wave in fp32 across its destinations and a second small kernel adds the [waves, H * C]
+// partials in a fixed order. The three backward kernels share run_ids (attention_bwd_kernel and dot_bwd_kernel also item_of and
+// run_id) with the forward ones and keep the rest of their walk inline (the delta sweep, the row fetch, the zeroing and the
+// partial-row store): as helpers those changed the register allocation of single instances enough to cost a wave per SIMD. The two
+// gate kernels take wave_of_grid and run_ids only and compile to the instructions they had: with more, the plain instances of
+// gate_fwd_kernel ran about 1 % slower and GATConv's forward + backward read above its earlier time (profiles/attention_walk.txt).
 // Rows of more than 256 pieces per head (C > 256 * VEC) take the NCH = 128, VEC = 1 instance: correct at any C <= 8192, its
-// operand rows of p and att re-read per edge (cache hits) and its accumulators wherever the compiler finds room.
+// operand rows re-read per edge (cache hits) and its accumulators wherever the compiler finds room.
 // Heavy destinations are walked by their one wave (no piecewise pass yet: the (m, l, accumulator) triple merges across
 // pieces, so the cure of hub.h applies).
+// No atomics anywhere: two runs give the same bits.
 //
+// FIRST FAMILY, GATv2 (gnnops.conv.edge_attention / GATv2Conv; the reference's model zoo builds GATv2REG from GATv2Conv,
+// graph_benchmark/models/ptg_models.py:208-236, and trains it, OpProfiler.py:97-112):
+//   z[e,h,c] = p[i,h,c] + q[j,h,c] (+ u[e,h,c])      s[e,h] = sum_c att[h,c] * leaky_relu(z[e,h,c], slope)      message = q[j,h,:]
 // Algorithmic bytes per launch, forward: E * H * (C * elem + 8 / heads-per-wave-block) gathered + N * (p row + out row + 4 H);
 // the unfused chain on this package's ops moves at least three [E, H, C] tensors and two [E, H] ones, each written and read.
-// Backward (destination-ordered too, no atomics): s is recomputed from the same rows, a = exp(s - lse); one [E, H * C] tensor gq
-// is written (d q = its segment sum over the source plan), d p is summed in registers and stored once per destination, d att is
-// summed per wave in fp32 and the [waves, H * C] partials are added in a fixed order by a second small kernel.
+// Backward: one [E, H * C] tensor gq is written (d q = its segment sum over the source plan), d p is summed in registers and
+// stored once per destination. HASU (u = lin_edge(edge_attr), GATv2Conv with edge_dim; compile-time instances beside the ones
+// without, which compile as before): forward, the online softmax keeps its steps of Unroll<NCH>::U edges — the same maxima and
+// rescalings, so u = 0 gives the bits of the pass without u — and fetches the raw rows of a step in two halves (AttUnroll::FWL),
+// holding the first half's q rows for the weighted sum. Backward, where an edge stands alone, the step halves (2 / 1 / 1 / 1);
+// t = ds * att * leaky'(z) is stored twice: inside gq[e] = a * g[i] + t[e], and alone as gu[e] = d u.
 //
-// The second member of the family (gnnops.conv.edge_attention_v1: GATConv, the original GAT, and AttentiveFP's GATEConv) scores
-// an edge from a per-edge scalar and a per-destination scalar, and may take a per-edge row u and a per-edge, per-head scale k
-// (the attention dropout mask, in the weighted sum only):
-//   t[e,h,:] = q[j,h,:] + u[e,h,:]      r = t, or leaky_relu(t, row_slope)      s[e,h] = leaky_relu(att[h,:] . r[e,h,:] + d[i,h], slope)
-//   out[i,h,:] = sum_{e into i} exp(s[e,h] - lse[i,h]) * k[e,h] * r[e,h,:]
-// gate_fwd_kernel / gate_bwd_kernel below: the same layout, group sums, id hand-out, online softmax and d att partials; u and k
-// are read through perm (row = original edge id, int64 offsets). With u a step holds two raw rows per edge, so its unroll halves.
+// SECOND FAMILY, GAT (v1) and GATE (gnnops.conv.edge_attention_v1: GATConv, the original GAT, and AttentiveFP's GATEConv): the score
+// comes from a per-edge scalar and a per-destination scalar, with an optional per-edge row u and per-edge, per-head scale k (the
+// attention dropout mask, in the weighted sum only):
+//   t[e,h,:] = q[j,h,:] + u[e,h,:]      r = t, or leaky_relu(t, row_slope)      message = k[e,h] * r[e,h,:]
+//   s[e,h] = leaky_relu(att[h,:] . r[e,h,:] + d[i,h] (+ c[e,h]), slope)
+// With u a step holds two raw rows per edge, so its unroll halves. HASC (c = att_edge . lin_edge(edge_attr), [E, H], GATConv with
+// edge_dim; read exactly as edge_scale is): backward writes gc[e,h] = d pre, one store per edge and head. Instantiated without u only.
 //
-// Edge features (GATv2Conv / GATConv with edge_dim), compile-time instances beside the ones above, which compile as before:
-//   first family, HASU:   z[e,h,c] = p[i,h,c] + q[j,h,c] + u[e,h,c]   (u = lin_edge(edge_attr), [E, H * C], read through perm like the
-//       gate kernels' u: row = ORIGINAL edge id, offset (int64) id * H * C, perm == NULL = identity); the message stays q[j]. Forward, the
-//       online softmax keeps its steps of Unroll<NCH>::U edges — the same maxima and rescalings, so u = 0 gives the bits of the pass
-//       without u — and fetches the raw rows of a step in two halves (AttUnroll::FWL), holding the first half's q rows for the weighted
-//       sum. Backward, where an edge stands alone, the step halves (2 / 1 / 1 / 1); t = ds * att * leaky'(z) is stored twice: inside
-//       gq[e] = a * g[i] + t[e] as before, and alone as gu[e] = d u, [E, H * C], row = original edge id. d p and d att as before.
-//   second family, HASC:  pre[e,h] = att[h,:] . r[e,h,:] + d[i,h] + c[e,h]   (c = att_edge . lin_edge(edge_attr), [E, H], read through
-//       perm exactly as edge_scale is); backward writes gc[e,h] = d pre, one store per edge and head. Instantiated without u only.
-// No atomics anywhere: two runs give the same bits.
+// THIRD FAMILY, scaled dot product (gnnops.conv.edge_attention_dot: TransformerConv): see the comment above DotArgs.
 #include <initializer_list>
 #include <utility>
 #include "common.h"
@@ -120,14 +126,6 @@ template <int NCH, bool HASU> struct AttUnroll {
 struct Place {
     int lane, gl, G, h, C;
     bool head_ok;
-    __device__ inline Place(const AttArgs& a, int hb) {
-        lane = threadIdx.x & 63;
-        G = 1 << a.gshift;
-        gl = lane & (G - 1);
-        h = hb * (64 >> a.gshift) + (lane >> a.gshift);
-        C = a.C;
-        head_ok = h < a.H;
-    }
     __device__ inline Place(int gshift, int H, int C_, int hb) {
         lane = threadIdx.x & 63;
         G = 1 << gshift;
@@ -141,6 +139,94 @@ struct Place {
     template <int VEC> __device__ inline int off(int k) const { return ok<VEC>(k) ? h * C + (k * G + gl) * VEC : 0; }
 };
 
+// ---- the walk, once: what the kernels below do alike, whatever they score. wave_of_grid and run_ids serve all six, item_of and run_id
+// the attention_* and dot_* kernels, the helpers after them attention_fwd_kernel and dot_fwd_kernel (why: see the head comment) --
+__device__ inline int wave_of_grid() {
+    return __builtin_amdgcn_readfirstlane((int)(((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6));
+}
+
+// item it = (destination i, head block hb) and the scalar bounds [jb, je) of the edges into i
+struct Item { int i, hb; int32_t jb, je; };
+__device__ inline Item item_of(int64_t it, int hblocks, const int32_t* rowptr) {
+    Item t;
+    t.i = __builtin_amdgcn_readfirstlane((int)(it / hblocks));
+    t.hb = __builtin_amdgcn_readfirstlane((int)(it % hblocks));
+    t.jb = __builtin_amdgcn_readfirstlane(rowptr[t.i]);
+    t.je = __builtin_amdgcn_readfirstlane(rowptr[t.i + 1]);
+    return t;
+}
+
+// the ids of the run of (at most) 64 edges from jrun: one coalesced load each, lane l holds id l of the run. cl = the source,
+// el = the ORIGINAL edge id (perm == NULL = identity), fetched only where something is read or written by it
+struct RunIds { int cl, el; };
+__device__ inline RunIds run_ids(const int64_t* col, const int32_t* perm, int32_t jrun, int32_t je, int lane, bool by_edge) {
+    RunIds r{0, 0};
+    if (jrun + lane < je) {
+        r.cl = (int)col[jrun + lane];
+        if (by_edge) r.el = perm ? perm[jrun + lane] : jrun + lane;
+    }
+    return r;
+}
+// id k of the run as a scalar (v_readlane). A kernel multiplies it into the row bases of a step and pins them (asm volatile, "+s") at
+// the top of the step, ahead of every row load (conv.hip:209-224)
+__device__ inline int64_t run_id(int ids, int32_t k) { return __builtin_amdgcn_readlane(ids, k & 63); }
+
+// the NCH raw pieces of one row (q, k, v, u); a kernel puts every row of a step in flight before it consumes the first
+template <typename T, int VEC, int NCH>
+__device__ inline void fetch_row(const T* row, const Place& pl, u32x4 (&r)[NCH]) {
+#pragma unroll
+    for (int k = 0; k < NCH; ++k) {
+        if (!pl.live<VEC>(k)) continue;
+        r[k] = att_load_raw<T, VEC>(row + pl.off<VEC>(k));
+    }
+}
+// a row that stays in registers (HOLD), unpacked; a piece that no lane has reads offset 0
+template <typename T, int VEC, int NCH>
+__device__ inline void hold_row(const T* row, const Place& pl, float (&f)[NCH][VEC]) {
+#pragma unroll
+    for (int k = 0; k < NCH; ++k) att_unpack<T, VEC>(att_load_raw<T, VEC>(row + pl.off<VEC>(k)), f[k]);
+}
+
+template <int NCH, int VEC>
+__device__ inline void zero_pieces(float (&x)[NCH][VEC]) {
+#pragma unroll
+    for (int k = 0; k < NCH; ++k)
+#pragma unroll
+        for (int v = 0; v < VEC; ++v) x[k][v] = 0.f;
+}
+
+// Online softmax, the raise: the step's scores s[u] (of the edges j + u < end) may lift the running maximum m; the denominator l and
+// the accumulators are rescaled by exp(m_old - m_new). The kernel then adds the step's exp(s[u] - m) to l and its messages to acc.
+template <int U, int NCH, int VEC>
+__device__ inline void softmax_raise(const float (&s)[U], int32_t j, int32_t end, float& m, float& l, float (&acc)[NCH][VEC]) {
+    float mn = m;
+#pragma unroll
+    for (int u = 0; u < U; ++u)
+        if (j + u < end) mn = fmaxf(mn, s[u]);
+    const float scale = expf(m - mn);   // 0 on the first step (m = -inf): nothing to rescale yet
+    m = mn;
+    l = l * scale;
+#pragma unroll
+    for (int k = 0; k < NCH; ++k)
+#pragma unroll
+        for (int v = 0; v < VEC; ++v) acc[k][v] = acc[k][v] * scale;
+}
+
+// the end of a destination: out = acc / l and lse = m + log l; a destination without an edge (any == false) gets a zero row and -inf
+template <typename T, int VEC, int NCH>
+__device__ inline void store_destination(const Place& pl, bool any, float m, float l, const float (&acc)[NCH][VEC], T* out_row, float* lse_row,
+                                         float neg_inf) {
+#pragma unroll
+    for (int k = 0; k < NCH; ++k) {
+        if (!pl.live<VEC>(k)) continue;
+        float o[VEC];
+#pragma unroll
+        for (int v = 0; v < VEC; ++v) o[v] = any ? acc[k][v] / l : 0.f;
+        if (pl.ok<VEC>(k)) att_store<T, VEC>(out_row + pl.off<VEC>(k), o);
+    }
+    if (pl.head_ok && pl.gl == 0) lse_row[pl.h] = any ? m + logf(l) : neg_inf;
+}
+
 template <typename T, int VEC, int NCH, bool HASU>
 __global__ __launch_bounds__(256) void attention_fwd_kernel(const AttArgs a) {
     constexpr int U = Unroll<NCH>::U;
@@ -150,49 +236,36 @@ __global__ __launch_bounds__(256) void attention_fwd_kernel(const AttArgs a) {
     const T* __restrict__ p = (const T*)a.p;
     const T* __restrict__ att = (const T*)a.att;
     const T* __restrict__ ue = (const T*)a.u;
-    const int32_t* __restrict__ perm = a.perm;
-    const int64_t* __restrict__ col = a.col;
-    const int wave = __builtin_amdgcn_readfirstlane((int)(((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6));
+    const int wave = wave_of_grid();
     const int64_t items = a.N * a.hblocks;
     const int ldq = (int)a.ldq;
     const int HC = a.H * a.C;
     const float slope = a.slope;
     const float NEG_INF = -__builtin_huge_valf();
     for (int64_t it = wave; it < items; it += a.nwaves) {
-        const int i = __builtin_amdgcn_readfirstlane((int)(it / a.hblocks));
-        const int hb = __builtin_amdgcn_readfirstlane((int)(it % a.hblocks));
-        const Place pl(a, hb);
+        const Item t = item_of(it, a.hblocks, a.rowptr);
+        const int i = t.i;
+        const Place pl(a.gshift, a.H, a.C, t.hb);
         const int lane = pl.lane;
-        const int32_t jb = __builtin_amdgcn_readfirstlane(a.rowptr[i]), je = __builtin_amdgcn_readfirstlane(a.rowptr[i + 1]);
         float pv[HOLD ? NCH : 1][VEC], av[HOLD ? NCH : 1][VEC];
         if constexpr (HOLD) {
-#pragma unroll
-            for (int k = 0; k < NCH; ++k) {
-                att_unpack<T, VEC>(att_load_raw<T, VEC>(p + (int64_t)i * a.ldp + pl.off<VEC>(k)), pv[k]);
-                att_unpack<T, VEC>(att_load_raw<T, VEC>(att + pl.off<VEC>(k)), av[k]);
-            }
+            hold_row<T, VEC>(p + (int64_t)i * a.ldp, pl, pv);
+            hold_row<T, VEC>(att, pl, av);
         }
         float acc[NCH][VEC];
-#pragma unroll
-        for (int k = 0; k < NCH; ++k)
-#pragma unroll
-            for (int v = 0; v < VEC; ++v) acc[k][v] = 0.f;
+        zero_pieces(acc);
         float m = NEG_INF, l = 0.f;
-        for (int32_t jrun = jb; jrun < je; jrun += 64) {
-            const int32_t jrun_end = min(jrun + 64, je);
-            int cl = 0, el = 0;
-            if (jrun + lane < je) {
-                cl = (int)col[jrun + lane];   // one coalesced load: lane l holds id l of the run
-                if constexpr (HASU) el = perm ? perm[jrun + lane] : jrun + lane;
-            }
+        for (int32_t jrun = t.jb; jrun < t.je; jrun += 64) {
+            const int32_t jrun_end = min(jrun + 64, t.je);
+            const RunIds ids = run_ids(a.col, a.perm, jrun, t.je, lane, HASU);
             for (int32_t j = jrun; j < jrun_end; j += U) {
                 int64_t qrow[U], erow[HASU ? U : 1];
 #pragma unroll
                 for (int u = 0; u < U; ++u) {
-                    qrow[u] = (int64_t)__builtin_amdgcn_readlane(cl, (j - jrun + u) & 63) * ldq;
+                    qrow[u] = run_id(ids.cl, j - jrun + u) * ldq;
                     asm volatile("" : "+s"(qrow[u]));   // the row bases are computed HERE, ahead of every row load (conv.hip:209-224)
                     if constexpr (HASU) {
-                        erow[u] = (int64_t)__builtin_amdgcn_readlane(el, (j - jrun + u) & 63) * HC;
+                        erow[u] = run_id(ids.el, j - jrun + u) * HC;
                         asm volatile("" : "+s"(erow[u]));
                     }
                 }
@@ -204,12 +277,8 @@ __global__ __launch_bounds__(256) void attention_fwd_kernel(const AttArgs a) {
 #pragma unroll
                     for (int u = u0; u < u0 + UL; ++u) {    // every row load of the round in flight before the first is consumed
                         if (j + u < jrun_end) {
-#pragma unroll
-                            for (int k = 0; k < NCH; ++k) {
-                                if (!pl.live<VEC>(k)) continue;
-                                qr[u][k] = att_load_raw<T, VEC>(q + qrow[u] + pl.off<VEC>(k));
-                                if constexpr (HASU) ur[u - u0][k] = att_load_raw<T, VEC>(ue + erow[u] + pl.off<VEC>(k));
-                            }
+                            fetch_row<T, VEC>(q + qrow[u], pl, qr[u]);
+                            if constexpr (HASU) fetch_row<T, VEC>(ue + erow[u], pl, ur[u - u0]);
                         }
                     }
 #pragma unroll
@@ -240,21 +309,11 @@ __global__ __launch_bounds__(256) void attention_fwd_kernel(const AttArgs a) {
                         }
                     }
                 }
-                float mn = m;
-#pragma unroll
-                for (int u = 0; u < U; ++u)
-                    if (j + u < jrun_end) mn = fmaxf(mn, s[u]);
-                const float scale = expf(m - mn);   // 0 on the first step (m = -inf): nothing to rescale yet
-                m = mn;
-                l = l * scale;
-#pragma unroll
-                for (int k = 0; k < NCH; ++k)
-#pragma unroll
-                    for (int v = 0; v < VEC; ++v) acc[k][v] = acc[k][v] * scale;
+                softmax_raise(s, j, jrun_end, m, l, acc);
 #pragma unroll
                 for (int u = 0; u < U; ++u) {
                     if (j + u < jrun_end) {
-                        const float w = expf(s[u] - mn);
+                        const float w = expf(s[u] - m);
                         l = l + w;
 #pragma unroll
                         for (int k = 0; k < NCH; ++k) {
@@ -268,16 +327,7 @@ __global__ __launch_bounds__(256) void attention_fwd_kernel(const AttArgs a) {
                 }
             }
         }
-        const bool any = je > jb;
-#pragma unroll
-        for (int k = 0; k < NCH; ++k) {
-            if (!pl.live<VEC>(k)) continue;
-            float o[VEC];
-#pragma unroll
-            for (int v = 0; v < VEC; ++v) o[v] = any ? acc[k][v] / l : 0.f;
-            if (pl.ok<VEC>(k)) att_store<T, VEC>((T*)a.out + (int64_t)i * a.ldo + pl.off<VEC>(k), o);
-        }
-        if (pl.head_ok && pl.gl == 0) a.lse[(int64_t)i * a.H + pl.h] = any ? m + logf(l) : NEG_INF;
+        store_destination<T, VEC>(pl, t.je > t.jb, m, l, acc, (T*)a.out + (int64_t)i * a.ldo, a.lse + (int64_t)i * a.H, NEG_INF);
     }
 }
 
@@ -295,14 +345,14 @@ __global__ __launch_bounds__(256) void attention_bwd_kernel(const AttArgs a) {
     const T* __restrict__ ue = (const T*)a.u;
     const int64_t* __restrict__ col = a.col;
     const int32_t* __restrict__ perm = a.perm;
-    const int wave = __builtin_amdgcn_readfirstlane((int)(((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6));
+    const int wave = wave_of_grid();
     if (wave >= a.nwaves) return;
     const int64_t items = a.N * a.hblocks;
     const int ldq = (int)a.ldq;
     const int HC = a.H * a.C;
     const float slope = a.slope;
     const int hb = __builtin_amdgcn_readfirstlane(wave % a.hblocks);
-    const Place pl(a, hb);
+    const Place pl(a.gshift, a.H, a.C, hb);
     const int lane = pl.lane;
     float datt[NCH][VEC];
 #pragma unroll
@@ -315,8 +365,9 @@ __global__ __launch_bounds__(256) void attention_bwd_kernel(const AttArgs a) {
         for (int k = 0; k < NCH; ++k) att_unpack<T, VEC>(att_load_raw<T, VEC>(att + pl.off<VEC>(k)), av[k]);
     }
     for (int64_t it = wave; it < items; it += a.nwaves) {
-        const int i = __builtin_amdgcn_readfirstlane((int)(it / a.hblocks));
-        const int32_t jb = __builtin_amdgcn_readfirstlane(a.rowptr[i]), je = __builtin_amdgcn_readfirstlane(a.rowptr[i + 1]);
+        const Item t = item_of(it, a.hblocks, a.rowptr);
+        const int i = t.i;
+        const int32_t jb = t.jb, je = t.je;
         float pv[HOLD ? NCH : 1][VEC], gv[HOLD ? NCH : 1][VEC], dp[NCH][VEC];
         float dpart = 0.f;
 #pragma unroll
@@ -341,17 +392,14 @@ __global__ __launch_bounds__(256) void attention_bwd_kernel(const AttArgs a) {
         const float lse = pl.head_ok ? a.lse[(int64_t)i * a.H + pl.h] : 0.f;
         for (int32_t jrun = jb; jrun < je; jrun += 64) {
             const int32_t jrun_end = min(jrun + 64, je);
-            int cl = 0, el = 0;
-            if (jrun + lane < je) {
-                cl = (int)col[jrun + lane];
-                el = perm ? perm[jrun + lane] : jrun + lane;
-            }
+            const RunIds ids = run_ids(col, perm, jrun, je, lane, true);
+            const int cl = ids.cl, el = ids.el;   // under the names the inline steps below use: their text, and so their schedule, stays as it was
             for (int32_t j = jrun; j < jrun_end; j += U) {
                 int64_t qrow[U], erow[U];
 #pragma unroll
                 for (int u = 0; u < U; ++u) {
-                    qrow[u] = (int64_t)__builtin_amdgcn_readlane(cl, (j - jrun + u) & 63) * ldq;
-                    erow[u] = (int64_t)__builtin_amdgcn_readlane(el, (j - jrun + u) & 63) * HC;
+                    qrow[u] = run_id(cl, j - jrun + u) * ldq;
+                    erow[u] = run_id(el, j - jrun + u) * HC;
                     asm volatile("" : "+s"(qrow[u]));
                     asm volatile("" : "+s"(erow[u]));
                 }
@@ -487,6 +535,9 @@ __device__ inline void gate_row(const u32x4& qr, const u32x4& ur, float* t) {
     }
 }
 
+// This kernel takes wave_of_grid and run_ids only, and keeps the rest of its walk and its softmax step inline: with them it compiles
+// to the instructions it had, and with the forward helpers its plain instances (GATConv without u and c) ran about 1 % slower
+// (profiles/attention_walk.txt).
 template <typename T, int VEC, int NCH, bool HASU, bool HASC>
 __global__ __launch_bounds__(256) void gate_fwd_kernel(const GateArgs a) {
     constexpr int U = GateUnroll<NCH, HASU>::FW;
@@ -499,7 +550,7 @@ __global__ __launch_bounds__(256) void gate_fwd_kernel(const GateArgs a) {
     const T* __restrict__ ce = (const T*)a.c;
     const int64_t* __restrict__ col = a.col;
     const int32_t* __restrict__ perm = a.perm;
-    const int wave = __builtin_amdgcn_readfirstlane((int)(((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6));
+    const int wave = wave_of_grid();
     const int64_t items = a.N * a.hblocks;
     const int ldq = (int)a.ldq;
     const int HC = a.H * a.C;
@@ -527,11 +578,8 @@ __global__ __launch_bounds__(256) void gate_fwd_kernel(const GateArgs a) {
         float m = NEG_INF, l = 0.f;
         for (int32_t jrun = jb; jrun < je; jrun += 64) {
             const int32_t jrun_end = min(jrun + 64, je);
-            int cl = 0, el = 0;
-            if (jrun + lane < je) {
-                cl = (int)col[jrun + lane];   // one coalesced load: lane l holds id l of the run
-                if (by_edge) el = perm ? perm[jrun + lane] : jrun + lane;
-            }
+            const RunIds ids = run_ids(col, perm, jrun, je, lane, by_edge);
+            const int cl = ids.cl, el = ids.el;   // under the names the inline steps below use: their text, and so their schedule, stays as it was
             for (int32_t j = jrun; j < jrun_end; j += U) {
                 int64_t qrow[U], erow[HASU ? U : 1], krow[U];
 #pragma unroll
@@ -630,6 +678,7 @@ __global__ __launch_bounds__(256) void gate_fwd_kernel(const GateArgs a) {
 
 // Backward: as attention_bwd_kernel (one head block per wave, d att in registers across its destinations); d d[i, h] is the sum
 // of dpre over the edges of i, in a register, stored once.
+// As gate_fwd_kernel, this kernel takes wave_of_grid and run_ids only: so it compiles to the instructions it had.
 template <typename T, int VEC, int NCH, bool HASU, bool HASC>
 __global__ __launch_bounds__(256) void gate_bwd_kernel(const GateArgs a) {
     constexpr int U = GateUnroll<NCH, HASU>::BW;
@@ -644,7 +693,7 @@ __global__ __launch_bounds__(256) void gate_bwd_kernel(const GateArgs a) {
     const T* __restrict__ o = (const T*)a.o;
     const int64_t* __restrict__ col = a.col;
     const int32_t* __restrict__ perm = a.perm;
-    const int wave = __builtin_amdgcn_readfirstlane((int)(((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6));
+    const int wave = wave_of_grid();
     if (wave >= a.nwaves) return;
     const int64_t items = a.N * a.hblocks;
     const int ldq = (int)a.ldq;
@@ -690,11 +739,8 @@ __global__ __launch_bounds__(256) void gate_bwd_kernel(const GateArgs a) {
         float dd = 0.f;
         for (int32_t jrun = jb; jrun < je; jrun += 64) {
             const int32_t jrun_end = min(jrun + 64, je);
-            int cl = 0, el = 0;
-            if (jrun + lane < je) {
-                cl = (int)col[jrun + lane];
-                el = perm ? perm[jrun + lane] : jrun + lane;
-            }
+            const RunIds ids = run_ids(col, perm, jrun, je, lane, true);   // always: erow is the row of gq
+            const int cl = ids.cl, el = ids.el;   // under the names the inline steps below use: their text, and so their schedule, stays as it was
             for (int32_t j = jrun; j < jrun_end; j += U) {
                 int64_t qrow[U], erow[U], krow[U];
 #pragma unroll
@@ -826,9 +872,7 @@ __global__ __launch_bounds__(256) void dot_fwd_kernel(const DotArgs a) {
     const T* __restrict__ vp = (const T*)a.v;
     const T* __restrict__ ue = (const T*)a.u;
     const T* __restrict__ ks = (const T*)a.ks;
-    const int64_t* __restrict__ col = a.col;
-    const int32_t* __restrict__ perm = a.perm;
-    const int wave = __builtin_amdgcn_readfirstlane((int)(((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6));
+    const int wave = wave_of_grid();
     const int64_t items = a.N * a.hblocks;
     const int ldkv = (int)a.ldkv;
     const int HC = a.H * a.C;
@@ -836,39 +880,28 @@ __global__ __launch_bounds__(256) void dot_fwd_kernel(const DotArgs a) {
     const bool by_edge = HASU || ks != nullptr;   // something is read by original edge id
     const float NEG_INF = -__builtin_huge_valf();
     for (int64_t it = wave; it < items; it += a.nwaves) {
-        const int i = __builtin_amdgcn_readfirstlane((int)(it / a.hblocks));
-        const int hb = __builtin_amdgcn_readfirstlane((int)(it % a.hblocks));
-        const Place pl(a.gshift, a.H, a.C, hb);
+        const Item t = item_of(it, a.hblocks, a.rowptr);
+        const int i = t.i;
+        const Place pl(a.gshift, a.H, a.C, t.hb);
         const int lane = pl.lane;
         const int hk = pl.head_ok ? pl.h : 0;
-        const int32_t jb = __builtin_amdgcn_readfirstlane(a.rowptr[i]), je = __builtin_amdgcn_readfirstlane(a.rowptr[i + 1]);
         float qv[HOLD ? NCH : 1][VEC];
-        if constexpr (HOLD) {
-#pragma unroll
-            for (int k = 0; k < NCH; ++k) att_unpack<T, VEC>(att_load_raw<T, VEC>(qry + (int64_t)i * a.ldq + pl.off<VEC>(k)), qv[k]);
-        }
+        if constexpr (HOLD) hold_row<T, VEC>(qry + (int64_t)i * a.ldq, pl, qv);
         float acc[NCH][VEC];
-#pragma unroll
-        for (int k = 0; k < NCH; ++k)
-#pragma unroll
-            for (int v = 0; v < VEC; ++v) acc[k][v] = 0.f;
+        zero_pieces(acc);
         float m = NEG_INF, l = 0.f;
-        for (int32_t jrun = jb; jrun < je; jrun += 64) {
-            const int32_t jrun_end = min(jrun + 64, je);
-            int cl = 0, el = 0;
-            if (jrun + lane < je) {
-                cl = (int)col[jrun + lane];   // one coalesced load: lane l holds id l of the run
-                if (by_edge) el = perm ? perm[jrun + lane] : jrun + lane;
-            }
+        for (int32_t jrun = t.jb; jrun < t.je; jrun += 64) {
+            const int32_t jrun_end = min(jrun + 64, t.je);
+            const RunIds ids = run_ids(a.col, a.perm, jrun, t.je, lane, by_edge);
             for (int32_t j = jrun; j < jrun_end; j += U) {
                 int64_t srow[U], erow[HASU ? U : 1], krow[U];
 #pragma unroll
                 for (int u = 0; u < U; ++u) {
-                    srow[u] = (int64_t)__builtin_amdgcn_readlane(cl, (j - jrun + u) & 63) * ldkv;   // one base for the k and the v row
+                    srow[u] = run_id(ids.cl, j - jrun + u) * ldkv;   // one base for the k and the v row
                     asm volatile("" : "+s"(srow[u]));   // the row bases are computed HERE, ahead of every row load
                     krow[u] = 0;
                     if (by_edge) {
-                        const int64_t e = __builtin_amdgcn_readlane(el, (j - jrun + u) & 63);
+                        const int64_t e = run_id(ids.el, j - jrun + u);
                         krow[u] = e * a.H;
                         if constexpr (HASU) {
                             erow[u] = e * HC;
@@ -882,13 +915,9 @@ __global__ __launch_bounds__(256) void dot_fwd_kernel(const DotArgs a) {
                 for (int u = 0; u < U; ++u) {           // every row load of the step in flight before the first is consumed
                     kv[u] = 1.f;
                     if (j + u < jrun_end) {
-#pragma unroll
-                        for (int k = 0; k < NCH; ++k) {
-                            if (!pl.live<VEC>(k)) continue;
-                            kr[u][k] = att_load_raw<T, VEC>(kp + srow[u] + pl.off<VEC>(k));
-                            vr[u][k] = att_load_raw<T, VEC>(vp + srow[u] + pl.off<VEC>(k));
-                            if constexpr (HASU) ur[u][k] = att_load_raw<T, VEC>(ue + erow[HASU ? u : 0] + pl.off<VEC>(k));
-                        }
+                        fetch_row<T, VEC>(kp + srow[u], pl, kr[u]);
+                        fetch_row<T, VEC>(vp + srow[u], pl, vr[u]);
+                        if constexpr (HASU) fetch_row<T, VEC>(ue + erow[u], pl, ur[u]);
                         if (ks) kv[u] = gate_scalar<T>(ks + krow[u] + hk);
                     }
                 }
@@ -912,21 +941,11 @@ __global__ __launch_bounds__(256) void dot_fwd_kernel(const DotArgs a) {
                         s[u] = sc * group_sum(part, a.gshift, lane);
                     }
                 }
-                float mn = m;
-#pragma unroll
-                for (int u = 0; u < U; ++u)
-                    if (j + u < jrun_end) mn = fmaxf(mn, s[u]);
-                const float scale = expf(m - mn);   // 0 on the first step (m = -inf): nothing to rescale yet
-                m = mn;
-                l = l * scale;
-#pragma unroll
-                for (int k = 0; k < NCH; ++k)
-#pragma unroll
-                    for (int v = 0; v < VEC; ++v) acc[k][v] = acc[k][v] * scale;
+                softmax_raise(s, j, jrun_end, m, l, acc);
 #pragma unroll
                 for (int u = 0; u < U; ++u) {
                     if (j + u < jrun_end) {
-                        const float w = expf(s[u] - mn);
+                        const float w = expf(s[u] - m);
                         l = l + w;                      // the denominator never sees the scale: dropout comes after the softmax
                         const float wk = w * kv[u];
 #pragma unroll
@@ -941,16 +960,7 @@ __global__ __launch_bounds__(256) void dot_fwd_kernel(const DotArgs a) {
                 }
             }
         }
-        const bool any = je > jb;
-#pragma unroll
-        for (int k = 0; k < NCH; ++k) {
-            if (!pl.live<VEC>(k)) continue;
-            float o[VEC];
-#pragma unroll
-            for (int v = 0; v < VEC; ++v) o[v] = any ? acc[k][v] / l : 0.f;
-            if (pl.ok<VEC>(k)) att_store<T, VEC>((T*)a.out + (int64_t)i * a.ldo + pl.off<VEC>(k), o);
-        }
-        if (pl.head_ok && pl.gl == 0) a.lse[(int64_t)i * a.H + pl.h] = any ? m + logf(l) : NEG_INF;
+        store_destination<T, VEC>(pl, t.je > t.jb, m, l, acc, (T*)a.out + (int64_t)i * a.ldo, a.lse + (int64_t)i * a.H, NEG_INF);
     }
 }
 
@@ -969,18 +979,18 @@ __global__ __launch_bounds__(256) void dot_bwd_kernel(const DotArgs a) {
     const T* __restrict__ o = (const T*)a.o;
     const int64_t* __restrict__ col = a.col;
     const int32_t* __restrict__ perm = a.perm;
-    const int wave = __builtin_amdgcn_readfirstlane((int)(((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6));
+    const int wave = wave_of_grid();
     const int64_t items = a.N * a.hblocks;
     const int ldkv = (int)a.ldkv;
     const int HC = a.H * a.C;
     const float sc = a.scale;
     for (int64_t it = wave; it < items; it += a.nwaves) {
-        const int i = __builtin_amdgcn_readfirstlane((int)(it / a.hblocks));
-        const int hb = __builtin_amdgcn_readfirstlane((int)(it % a.hblocks));
+        const Item t = item_of(it, a.hblocks, a.rowptr);
+        const int i = t.i, hb = t.hb;
         const Place pl(a.gshift, a.H, a.C, hb);
         const int lane = pl.lane;
         const int hk = pl.head_ok ? pl.h : 0;
-        const int32_t jb = __builtin_amdgcn_readfirstlane(a.rowptr[i]), je = __builtin_amdgcn_readfirstlane(a.rowptr[i + 1]);
+        const int32_t jb = t.jb, je = t.je;
         float qv[HOLD ? NCH : 1][VEC], gv[HOLD ? NCH : 1][VEC], dq[NCH][VEC];
         float dpart = 0.f;
 #pragma unroll
@@ -1005,17 +1015,14 @@ __global__ __launch_bounds__(256) void dot_bwd_kernel(const DotArgs a) {
         const float lse = pl.head_ok ? a.lse[(int64_t)i * a.H + pl.h] : 0.f;
         for (int32_t jrun = jb; jrun < je; jrun += 64) {
             const int32_t jrun_end = min(jrun + 64, je);
-            int cl = 0, el = 0;
-            if (jrun + lane < je) {
-                cl = (int)col[jrun + lane];
-                el = perm ? perm[jrun + lane] : jrun + lane;
-            }
+            const RunIds ids = run_ids(col, perm, jrun, je, lane, true);
+            const int cl = ids.cl, el = ids.el;   // under the names the inline steps below use: their text, and so their schedule, stays as it was
             for (int32_t j = jrun; j < jrun_end; j += U) {
                 int64_t srow[U], erow[U], krow[U];
 #pragma unroll
                 for (int u = 0; u < U; ++u) {
-                    srow[u] = (int64_t)__builtin_amdgcn_readlane(cl, (j - jrun + u) & 63) * ldkv;
-                    const int64_t e = __builtin_amdgcn_readlane(el, (j - jrun + u) & 63);
+                    srow[u] = run_id(cl, j - jrun + u) * ldkv;
+                    const int64_t e = run_id(el, j - jrun + u);
                     erow[u] = e * HC;                   // always: the row of gkv is 2 * erow
                     krow[u] = ks ? e * a.H : 0;
                     asm volatile("" : "+s"(srow[u]));
@@ -1140,49 +1147,39 @@ inline int max_vec_of(int es, Operands operands) {
     return max_vec;
 }
 
-// A family names its Args and launches its forward or backward kernel for one <T, VEC, NCH>; which of its compile-time flags
-// an operand turns on is the only choice a family makes itself.
+// the forward or the backward kernel of one instance, whatever the family
+template <bool BW, typename Args>
+void run(void (*fwd)(Args), void (*bwd)(Args), const Args& a, int grid, hipStream_t stream) {
+    hipLaunchKernelGGL(BW ? bwd : fwd, dim3(grid), dim3(256), 0, stream, a);
+}
+
+// A family names its Args and, for one <T, VEC, NCH>, the instance an operand turns on: the only choice a family makes itself.
 struct AttFamily {
     using Args = AttArgs;
-    template <typename T, bool BW, int VEC, int NCH, bool HASU>
-    static void run(const Args& a, int grid, hipStream_t stream) {
-        if constexpr (BW) hipLaunchKernelGGL((attention_bwd_kernel<T, VEC, NCH, HASU>), dim3(grid), dim3(256), 0, stream, a);
-        else hipLaunchKernelGGL((attention_fwd_kernel<T, VEC, NCH, HASU>), dim3(grid), dim3(256), 0, stream, a);
-    }
     template <typename T, bool BW, int VEC, int NCH>
     static void launch(const Args& a, int grid, hipStream_t stream) {
-        if (a.u) run<T, BW, VEC, NCH, true>(a, grid, stream);
-        else run<T, BW, VEC, NCH, false>(a, grid, stream);
+        if (a.u) run<BW>(attention_fwd_kernel<T, VEC, NCH, true>, attention_bwd_kernel<T, VEC, NCH, true>, a, grid, stream);
+        else run<BW>(attention_fwd_kernel<T, VEC, NCH, false>, attention_bwd_kernel<T, VEC, NCH, false>, a, grid, stream);
     }
 };
 
 struct GateFamily {
     using Args = GateArgs;
-    template <typename T, bool BW, int VEC, int NCH, bool HASU, bool HASC>
-    static void run(const Args& a, int grid, hipStream_t stream) {
-        if constexpr (BW) hipLaunchKernelGGL((gate_bwd_kernel<T, VEC, NCH, HASU, HASC>), dim3(grid), dim3(256), 0, stream, a);
-        else hipLaunchKernelGGL((gate_fwd_kernel<T, VEC, NCH, HASU, HASC>), dim3(grid), dim3(256), 0, stream, a);
-    }
     // the instances with the per-edge score term c are those of GATConv(edge_dim): no per-edge row beside it
     template <typename T, bool BW, int VEC, int NCH>
     static void launch(const Args& a, int grid, hipStream_t stream) {
-        if (a.c) run<T, BW, VEC, NCH, false, true>(a, grid, stream);
-        else if (a.u) run<T, BW, VEC, NCH, true, false>(a, grid, stream);
-        else run<T, BW, VEC, NCH, false, false>(a, grid, stream);
+        if (a.c) run<BW>(gate_fwd_kernel<T, VEC, NCH, false, true>, gate_bwd_kernel<T, VEC, NCH, false, true>, a, grid, stream);
+        else if (a.u) run<BW>(gate_fwd_kernel<T, VEC, NCH, true, false>, gate_bwd_kernel<T, VEC, NCH, true, false>, a, grid, stream);
+        else run<BW>(gate_fwd_kernel<T, VEC, NCH, false, false>, gate_bwd_kernel<T, VEC, NCH, false, false>, a, grid, stream);
     }
 };
 
 struct DotFamily {
     using Args = DotArgs;
-    template <typename T, bool BW, int VEC, int NCH, bool HASU>
-    static void run(const Args& a, int grid, hipStream_t stream) {
-        if constexpr (BW) hipLaunchKernelGGL((dot_bwd_kernel<T, VEC, NCH, HASU>), dim3(grid), dim3(256), 0, stream, a);
-        else hipLaunchKernelGGL((dot_fwd_kernel<T, VEC, NCH, HASU>), dim3(grid), dim3(256), 0, stream, a);
-    }
     template <typename T, bool BW, int VEC, int NCH>
     static void launch(const Args& a, int grid, hipStream_t stream) {
-        if (a.u) run<T, BW, VEC, NCH, true>(a, grid, stream);
-        else run<T, BW, VEC, NCH, false>(a, grid, stream);
+        if (a.u) run<BW>(dot_fwd_kernel<T, VEC, NCH, true>, dot_bwd_kernel<T, VEC, NCH, true>, a, grid, stream);
+        else run<BW>(dot_fwd_kernel<T, VEC, NCH, false>, dot_bwd_kernel<T, VEC, NCH, false>, a, grid, stream);
     }
 };
 
@@ -1243,6 +1240,13 @@ int check_sizes(const char* what, int64_t N, int64_t E, int64_t H, int64_t C, in
 }
 
 struct Launch { Geometry geo; int rows, grid, nwaves; };   // grid == 0: a valid call with nothing to launch
+
+template <typename Args>
+void set_geometry(Args& a, const Launch& l) {
+    a.gshift = l.geo.gshift;
+    a.hblocks = l.geo.hblocks;
+    a.nwaves = l.nwaves;
+}
 
 // What the two forward entry points check and choose before they launch. The caller says what only it knows: its name, whether
 // its other pitches hold a row, whether it was given the u and c that no instance takes together, whether the pointers it needs
@@ -1305,7 +1309,7 @@ extern "C" int gnnops_edge_attention(const void* q, int64_t ldq, const void* p, 
     AttArgs a{};
     a.q = q; a.p = p; a.att = att; a.u = u; a.rowptr = rowptr; a.perm = perm; a.col = col; a.out = out; a.lse = lse;
     a.N = N; a.ldq = ldq; a.ldp = ldp; a.ldo = ldo; a.H = (int)H; a.C = (int)C; a.slope = negative_slope;
-    a.gshift = l.geo.gshift; a.hblocks = l.geo.hblocks; a.nwaves = l.nwaves;
+    set_geometry(a, l);
     launch<AttFamily, false>(a, l.geo, l.grid, dtype, (hipStream_t)s);
     return gnnops_check_launch("edge_attention");
 }
@@ -1327,7 +1331,7 @@ extern "C" int gnnops_edge_attention_backward(const void* q, int64_t ldq, const 
     a.q = q; a.p = p; a.att = att; a.u = u; a.g = grad_out; a.o = out; a.rowptr = rowptr; a.perm = perm; a.col = col;
     a.dp = grad_p; a.gq = gq; a.gu = gu; a.lse = const_cast<float*>(lse); a.partial = (float*)workspace;
     a.N = N; a.ldq = ldq; a.ldp = ldp; a.ldo = ldo; a.ldg = ldg; a.H = (int)H; a.C = (int)C; a.slope = negative_slope;
-    a.gshift = l.geo.gshift; a.hblocks = l.geo.hblocks; a.nwaves = l.nwaves;
+    set_geometry(a, l);
     launch<AttFamily, true>(a, l.geo, l.grid, dtype, (hipStream_t)s);
     launch_datt(a.partial, l.rows, (int)(H * C), grad_att, dtype, (hipStream_t)s);
     return gnnops_check_launch("edge_attention_backward");
@@ -1348,7 +1352,7 @@ extern "C" int gnnops_edge_attention_v1(const void* q, int64_t ldq, const void* 
     a.out = out; a.lse = lse;
     a.N = N; a.ldq = ldq; a.ldd = ldd; a.ldo = ldo; a.H = (int)H; a.C = (int)C;
     a.slope = negative_slope; a.row_slope = has_row_slope ? row_slope : 1.f;
-    a.gshift = l.geo.gshift; a.hblocks = l.geo.hblocks; a.nwaves = l.nwaves;
+    set_geometry(a, l);
     launch<GateFamily, false>(a, l.geo, l.grid, dtype, (hipStream_t)s);
     return gnnops_check_launch("edge_attention_v1");
 }
@@ -1373,7 +1377,7 @@ extern "C" int gnnops_edge_attention_v1_backward(const void* q, int64_t ldq, con
     a.dd = grad_d; a.gq = gq; a.gc = gc; a.lse = const_cast<float*>(lse); a.partial = (float*)workspace;
     a.N = N; a.ldq = ldq; a.ldd = ldd; a.ldo = ldo; a.ldg = ldg; a.H = (int)H; a.C = (int)C;
     a.slope = negative_slope; a.row_slope = has_row_slope ? row_slope : 1.f;
-    a.gshift = l.geo.gshift; a.hblocks = l.geo.hblocks; a.nwaves = l.nwaves;
+    set_geometry(a, l);
     launch<GateFamily, true>(a, l.geo, l.grid, dtype, (hipStream_t)s);
     launch_datt(a.partial, l.rows, (int)(H * C), grad_att, dtype, (hipStream_t)s);
     return gnnops_check_launch("edge_attention_v1_backward");
@@ -1406,7 +1410,7 @@ extern "C" int gnnops_edge_attention_dot(const void* qry, int64_t ldq, const voi
     DotArgs a{};
     a.qry = qry; a.k = k; a.v = v; a.u = u; a.ks = edge_scale; a.rowptr = rowptr; a.perm = perm; a.col = col; a.out = out; a.lse = lse;
     a.N = N; a.ldq = ldq; a.ldkv = ldkv; a.ldo = ldo; a.H = (int)H; a.C = (int)C; a.scale = scale;
-    a.gshift = l.geo.gshift; a.hblocks = l.geo.hblocks; a.nwaves = l.nwaves;
+    set_geometry(a, l);
     launch<DotFamily, false>(a, l.geo, l.grid, dtype, (hipStream_t)s);
     return gnnops_check_launch("edge_attention_dot");
 }
@@ -1428,7 +1432,7 @@ extern "C" int gnnops_edge_attention_dot_backward(const void* qry, int64_t ldq, 
     a.qry = qry; a.k = k; a.v = v; a.u = u; a.ks = edge_scale; a.g = grad_out; a.o = out; a.rowptr = rowptr; a.perm = perm; a.col = col;
     a.dq = grad_qry; a.gkv = gkv; a.gu = gu; a.lse = const_cast<float*>(lse);
     a.N = N; a.ldq = ldq; a.ldkv = ldkv; a.ldo = ldo; a.ldg = ldg; a.H = (int)H; a.C = (int)C; a.scale = scale;
-    a.gshift = l.geo.gshift; a.hblocks = l.geo.hblocks; a.nwaves = l.nwaves;
+    set_geometry(a, l);
     launch<DotFamily, true>(a, l.geo, l.grid, dtype, (hipStream_t)s);
     return gnnops_check_launch("edge_attention_dot_backward");
 }
