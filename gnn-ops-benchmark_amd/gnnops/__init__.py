@@ -21,14 +21,14 @@ from .ops import (
     set_plan_cache,
 )
 # the differentiable front ends (they ARE the raw ops when nothing requires grad; gnnops.ops.* are the raw forms)
-from .autograd import (addmm, gather, index_select, matmul, matmul_tn, scatter, scatter_add, scatter_max, scatter_mean, scatter_min,
+from .autograd import (addmm, gather, index_select, matmul, matmul_tn, segment_matmul, scatter, scatter_add, scatter_max, scatter_mean, scatter_min,
                        scatter_mul, scatter_sum)
 from .sparse import (SpmmTiles, coalesce, coalesce_sparse_tensor, sddmm, sort, sparse_mm, spgemm_hash_max_row, spgemm_max_span, spmm, spmm_csr, spmm_reduce, spmm_t, spmm_tiles,
                      spspmm, transpose, transpose_contiguous)
 from .segment import (expand_rowptr, gather_coo, gather_csr, rowptr_from_sorted, scatter_log_softmax, scatter_logsumexp, scatter_softmax,
                       scatter_std, segment_coo, segment_csr)
 from . import autograd, layers
-from .conv import (AttentiveFP, GATConv, GATEConv, GATv2, GATv2Conv, GCNConv, GraphUNet, TopKPooling, edge_attention, edge_attention_v1, gcn_propagate,
+from .conv import (AttentiveFP, GATConv, GATEConv, GATv2, GATv2Conv, GCNConv, GraphUNet, HeteroLinear, RGCNConv, TopKPooling, edge_attention, edge_attention_v1, gcn_propagate,
                    head_act_norm)
 from .pool import filter_adj, global_add_pool, global_max_pool, global_mean_pool, remove_self_loops, topk
 from . import pool
@@ -44,4 +44,5 @@ __all__ = [
     "rowptr_from_sorted", "scatter_softmax", "scatter_log_softmax", "scatter_logsumexp", "scatter_std", "autograd", "layers", "GATv2Conv", "edge_attention", "GATConv", "GATEConv", "AttentiveFP", "edge_attention_v1",
     "GCNConv", "TopKPooling", "GraphUNet", "gcn_propagate", "pool", "topk", "filter_adj", "remove_self_loops",
     "GATv2", "head_act_norm", "global_add_pool", "global_mean_pool", "global_max_pool", "spmm_reduce", "SparseTensor",
+    "segment_matmul", "HeteroLinear", "RGCNConv",
 ]

@@ -142,6 +142,9 @@ SIGNATURES = {
     "gnnops_gemm_tn": (_ci, [_vp, _vp, _vp, _i64, _i64, _i64, _ci, _vp, _sz, _vp]),
     "gnnops_gemm_tn_geometry": (_ci, [_i64, _i64, _i64, _ci, ctypes.POINTER(_i64), ctypes.POINTER(_i64), ctypes.POINTER(_i64),
                                       ctypes.POINTER(_i64)]),
+    "gnnops_segment_matmul_workspace_bytes": (_sz, [_i64]),
+    "gnnops_segment_matmul": (_ci, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _ci, _vp, _sz, _vp]),
+    "gnnops_segment_matmul_geometry": (_ci, [_ci, ctypes.POINTER(_i64), ctypes.POINTER(_i64), ctypes.POINTER(_i64)]),
     "gnnops_fused_index_add_select_sum_workspace_bytes": (_sz, [_i64, _i64]),
     "gnnops_fused_index_add_select_sum": (_ci, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _ci, _vp, _sz, _vp]),
     "gnnops_segment_topk_max_len": (_i64, []),

@@ -495,6 +495,62 @@ def matmul_tn(a, b):
     return _MatMulTN.apply(a, b) if _needs_grad(a) or _needs_grad(b) else ops.matmul_tn(a, b)
 
 
+class _SegmentMatmul(torch.autograd.Function):
+    """segment_matmul on the grouped MFMA kernel. With g the gradient of the output:
+      d x        = segment_matmul(g, ptr, W^T per type): the same kernel over the batched transpose of the weight;
+      d W[t]     = x_t^T @ g_t: one product per non-empty type on row slices, by the route of every other weight gradient
+                   (ops.matmul_tn where ops.matmul_tn_preferred holds, else transpose + GEMM); an empty type gets zeros;
+      d bias[t]  = the sum of g over segment t: `sum(0)` of the same row slice, like the bias gradient of addmm (a tree sum; the
+                   package's segment_csr adds a segment's rows one after the other in fp32, which over 10^4 rows and more loses
+                   digits that a bias gradient should keep).
+    The slices need ptr on the host: a GPU ptr is read back once in forward, a CPU ptr costs nothing."""
+
+    @staticmethod
+    def forward(ctx, x, ptr, weight, bias):
+        out = ops.segment_matmul(x, ptr, weight, bias)      # a CPU ptr is checked there
+        ptr_dev = ptr.to(x.device)
+        ctx.bounds = [min(max(v, 0), x.size(0)) for v in ptr.tolist()]   # the kernels' clamp (csrc/segment_matmul.hip seg_bounds)
+        ctx.has_bias = bias is not None
+        ctx.save_for_backward(x, ptr_dev, weight)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        from .sparse import _transpose_batched, transpose_contiguous
+
+        x, ptr, weight = ctx.saved_tensors
+        g = g.contiguous()
+        d_x = d_w = d_b = None
+        if ctx.needs_input_grad[0]:
+            d_x = ops.segment_matmul(g, ptr, _transpose_batched(weight.contiguous()))
+        if ctx.needs_input_grad[2]:
+            x = x.contiguous()
+            K, N = weight.size(1), weight.size(2)
+            d_w = torch.zeros_like(weight, memory_format=torch.contiguous_format)
+            for t in range(weight.size(0)):
+                a, b = ctx.bounds[t], ctx.bounds[t + 1]
+                if b <= a or K * N == 0:
+                    continue
+                xt, gt = x[a:b], g[a:b]
+                if ops.matmul_tn_preferred(b - a, K, N, g.dtype):
+                    d_w[t] = ops.matmul_tn(xt, gt)
+                else:
+                    d_w[t] = ops.matmul(transpose_contiguous(xt), gt)
+        if ctx.has_bias and ctx.needs_input_grad[3]:
+            d_b = g.new_zeros((weight.size(0), weight.size(2)))
+            for t in range(weight.size(0)):
+                a, b = ctx.bounds[t], ctx.bounds[t + 1]
+                if b > a:
+                    d_b[t] = g[a:b].sum(0)
+        return d_x, None, d_w, d_b
+
+
+def segment_matmul(x, ptr, weight, bias=None):
+    if _needs_grad(x) or _needs_grad(weight) or (bias is not None and _needs_grad(bias)):
+        return _SegmentMatmul.apply(x, ptr, weight, bias)
+    return ops.segment_matmul(x, ptr, weight, bias)
+
+
 # ---- torch_spline_conv (gnnops/spatial.py; kernels csrc/spline.hip forward, csrc/spline_bw.hip backward) ----------------
 class _SplineBasis(torch.autograd.Function):
     """spline_basis, differentiable in pseudo [E, D]: d pseudo[e, d] = sum_s d basis[e, s] * d b[e, s] / d pseudo[e, d]

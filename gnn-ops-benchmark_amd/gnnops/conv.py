@@ -1814,3 +1814,110 @@ class GraphUNet(torch.nn.Module):
             if i < self.depth - 1:
                 x = self.act(x)
         return (x, perms) if return_perms else x
+
+
+# ---- per-type weights: HeteroLinear and RGCNConv on the grouped product (csrc/segment_matmul.hip) --------------------------------
+def _sorted_by_type(type_vec, num_types, is_sorted):
+    """(sorted types, the stable permutation that sorts them or None, int64 ptr [num_types + 1] on the device)."""
+    from . import segment, sparse
+
+    if type_vec.dtype != torch.int64 or type_vec.dim() != 1:
+        raise RuntimeError(f"expected a 1-D int64 type vector, got {type_vec.dtype} with {type_vec.dim()} dims")
+    perm = None
+    if not is_sorted:
+        type_vec, perm = sparse.sort(type_vec, stable=True)
+    return type_vec, perm, segment.rowptr_from_sorted(type_vec, num_types).to(torch.int64)
+
+
+class HeteroLinear(_Layer):
+    """torch_geometric HeteroLinear: out_i = x_i @ weight[type_i] + bias[type_i]. ``weight`` [num_types, in, out], ``bias``
+    [num_types, out], ``forward(x, type_vec)`` as in PyG (glorot / zeros). Rows are brought into type order by a stable sort
+    (skipped with ``is_sorted=True``), multiplied by one grouped launch (`gnnops.segment_matmul`) and put back; the inverse
+    permutation is the sort of the permutation. torch_geometric is not available to compare against: parity unpinned."""
+
+    def __init__(self, in_channels, out_channels, num_types, is_sorted=False, bias=True):
+        super().__init__()
+        self.in_channels, self.out_channels, self.num_types, self.is_sorted = in_channels, out_channels, num_types, is_sorted
+        self.weight = torch.nn.Parameter(torch.empty(num_types, in_channels, out_channels))
+        self.bias = torch.nn.Parameter(torch.zeros(num_types, out_channels)) if bias else None
+        for w in self.weight:
+            torch.nn.init.xavier_uniform_(w)
+
+    def forward(self, x, type_vec):
+        from . import autograd, sparse
+
+        _require_gpu(x, type_vec)
+        if type_vec.numel() != x.size(0):
+            raise RuntimeError(f"HeteroLinear: {x.size(0)} rows but {type_vec.numel()} types")
+        _, perm, ptr = _sorted_by_type(type_vec, self.num_types, self.is_sorted)
+        if perm is not None:
+            x = autograd.index_select(x, 0, perm)
+        out = autograd.segment_matmul(x.contiguous(), ptr, self.weight, self.bias)
+        if perm is not None:
+            out = autograd.index_select(out, 0, sparse.sort(perm)[1])
+        return out
+
+
+class RGCNConv(_Layer):
+    """torch_geometric RGCNConv (Schlichtkrull et al. 2018): out_i = x_i @ root + bias + sum_r aggr_{j in N_r(i)} x_j @ W_r, with
+    aggr = "mean" (the sum over the edges of relation r into i divided by their number) or "sum". Parameters as in PyG:
+    ``weight`` [num_relations, in, out] — with ``num_bases``: ``weight`` [num_bases, in, out] and ``comp`` [num_relations,
+    num_bases], W = comp @ weight (a torch op) — ``root`` [in, out], ``bias`` [out]; glorot / zeros.
+
+    One pass of each kind: the edges are sorted by relation (stable; skipped with ``is_sorted=True``), the source rows gathered
+    (`index_select`), multiplied by their relation's weight in one grouped launch (`segment_matmul`), and summed into their
+    destinations by one sparse product whose values are the factors 1 / |N_r(i)| (`spmm`; the counts come from a scatter over
+    the key dst * R + r). The root weight is one more relation whose edges are the self-loops i -> i, with ``bias`` as that
+    type's bias row: x @ root + bias goes through the same three launches and no partial result is rounded on the way.
+    ``num_blocks`` is not implemented. torch_geometric is not available to compare against: parity unpinned."""
+
+    def __init__(self, in_channels, out_channels, num_relations, num_bases=None, aggr="mean", root_weight=True, is_sorted=False,
+                 bias=True):
+        super().__init__()
+        if aggr not in ("mean", "sum", "add"):
+            raise NotImplementedError(f"gnnops.conv.RGCNConv: aggr={aggr!r} is not implemented (mean, sum)")
+        self.in_channels, self.out_channels, self.num_relations, self.num_bases = in_channels, out_channels, num_relations, num_bases
+        self.aggr, self.is_sorted = "sum" if aggr == "add" else aggr, is_sorted
+        self.weight = torch.nn.Parameter(torch.empty(num_bases if num_bases else num_relations, in_channels, out_channels))
+        self.comp = torch.nn.Parameter(torch.empty(num_relations, num_bases)) if num_bases else None
+        self.root = torch.nn.Parameter(torch.empty(in_channels, out_channels)) if root_weight else None
+        self.bias = torch.nn.Parameter(torch.zeros(out_channels)) if bias else None
+        for w in self.weight:
+            torch.nn.init.xavier_uniform_(w)
+        for w in (self.comp, self.root):
+            if w is not None:
+                torch.nn.init.xavier_uniform_(w)
+
+    def forward(self, x, edge_index, edge_type):
+        from . import autograd
+
+        _require_gpu(x, edge_index, edge_type)
+        if edge_index.dim() != 2 or edge_index.size(0) != 2 or edge_type.numel() != edge_index.size(1):
+            raise RuntimeError("RGCNConv: edge_index must be [2, E] and edge_type [E]")
+        R, N, E, dev = self.num_relations, x.size(0), edge_index.size(1), x.device
+        et, perm, ptr = _sorted_by_type(edge_type, R, self.is_sorted)
+        src, dst = (edge_index[0], edge_index[1]) if perm is None else (edge_index[0][perm], edge_index[1][perm])
+        weight = self.weight
+        if self.comp is not None:
+            weight = (self.comp @ weight.reshape(self.num_bases, -1)).view(R, self.in_channels, self.out_channels)
+        factor = None
+        if self.aggr == "mean":
+            key = dst * R + et
+            count = ops.scatter(torch.ones(E, dtype=torch.float32, device=dev), key, 0, None, N * R, "sum")
+            factor = ops.index_select(count, 0, key).reciprocal_().to(x.dtype)
+        bias = None
+        if self.root is not None:      # relation R: the self-loops, weight `root`, bias row `bias`
+            loops = torch.arange(N, dtype=torch.int64, device=dev)
+            src, dst = torch.cat([src, loops]), torch.cat([dst, loops])
+            ptr = torch.cat([ptr, ptr.new_full((1,), E + N)])
+            weight = torch.cat([weight, self.root.unsqueeze(0)])
+            if self.bias is not None:
+                bias = torch.cat([self.bias.new_zeros(R, self.out_channels), self.bias.unsqueeze(0)])
+            if factor is not None:
+                factor = torch.cat([factor, factor.new_ones(N)])
+        msg = autograd.segment_matmul(autograd.index_select(x.contiguous(), 0, src), ptr, weight, bias)
+        index = torch.stack([dst, torch.arange(msg.size(0), dtype=torch.int64, device=dev)])
+        out = autograd.spmm(index, factor, N, msg.size(0), msg)
+        if self.root is None and self.bias is not None:
+            out = out + self.bias
+        return out

@@ -917,3 +917,70 @@ def matmul_tn_preferred(R, P, Q, dtype):
     if dtype == torch.float32 or R >= 100_000:
         return True
     return P <= 64 and Q <= 256
+
+
+def segment_matmul_geometry(dtype):
+    """The tile of gnnops_segment_matmul for this dtype: {'tile_m', 'tile_n', 'k_step'}. Host only."""
+    import ctypes
+
+    try:
+        dt = _DT[dtype]
+    except KeyError:
+        raise NotImplementedError(f"gnnops.segment_matmul: dtype {dtype} is not supported (float32/float16/bfloat16)")
+    v = [ctypes.c_int64() for _ in range(3)]
+    check(_lib.load().gnnops_segment_matmul_geometry(dt, *[ctypes.byref(x) for x in v]), "segment_matmul_geometry")
+    return {"tile_m": v[0].value, "tile_n": v[1].value, "k_step": v[2].value}
+
+
+def _check_host_ptr(ptr, M, T, what):
+    """A CPU ptr is checked in full: T + 1 entries from 0 to M that never decrease."""
+    if ptr.numel() != T + 1:
+        raise RuntimeError(f"{what}: ptr must have {T + 1} entries (one more than weight has types), got {ptr.numel()}")
+    if int(ptr[0]) != 0:
+        raise RuntimeError(f"{what}: ptr must start at 0, got {int(ptr[0])}")
+    if int(ptr[-1]) != M:
+        raise RuntimeError(f"{what}: ptr must end at the number of rows {M}, got {int(ptr[-1])}")
+    if T > 0 and bool((ptr[1:] < ptr[:-1]).any()):
+        raise RuntimeError(f"{what}: ptr must not decrease")
+
+
+def segment_matmul(x, ptr, weight, bias=None):
+    """pyg_lib.ops.segment_matmul: out[ptr[t] : ptr[t+1]] = x[ptr[t] : ptr[t+1]] @ weight[t] (+ bias[t]). x [M, K], weight
+    [T, K, N], bias [T, N], ptr int64 [T + 1] on the CPU (checked, then copied to the device) or on the GPU (used as it is: the
+    kernels clamp it into [0, M], csrc/segment_matmul.hip). One grouped launch on the MFMA tile of addmm; fp32 sums, one rounding."""
+    _refuse_grad("segment_matmul", x, weight, bias)
+    # the arguments are checked before the device is: what is wrong with a call is the same on any device
+    if x.dim() != 2 or weight.dim() != 3:
+        raise RuntimeError("segment_matmul: x must be [M, K] and weight [T, K, N]")
+    if x.size(1) != weight.size(1):
+        raise RuntimeError(f"segment_matmul: x has {x.size(1)} columns but weight takes {weight.size(1)}")
+    if x.dtype != weight.dtype or (bias is not None and bias.dtype != x.dtype):
+        raise RuntimeError("segment_matmul: operands must have the same dtype")
+    if x.device != weight.device or (bias is not None and bias.device != x.device):
+        raise RuntimeError("segment_matmul: operands must be on the same device")
+    dt = _dtype_code(x, "segment_matmul")
+    M, K = x.shape
+    T, _, N = weight.shape
+    if bias is not None and tuple(bias.shape) != (T, N):
+        raise RuntimeError(f"segment_matmul: bias must be [{T}, {N}], got {tuple(bias.shape)}")
+    if ptr.dtype != torch.int64 or ptr.dim() != 1:
+        raise RuntimeError(f"segment_matmul: ptr must be a 1-D int64 tensor, got {ptr.dtype} with {ptr.dim()} dims")
+    if not ptr.is_cuda:
+        _check_host_ptr(ptr, M, T, "segment_matmul")
+    elif ptr.numel() != T + 1:
+        raise RuntimeError(f"segment_matmul: ptr must have {T + 1} entries (one more than weight has types), got {ptr.numel()}")
+    _require_gpu(x, weight, bias)
+    if ptr.is_cuda and ptr.device != x.device:
+        raise RuntimeError("segment_matmul: operands must be on the same device")
+    ptr = ptr.to(x.device)
+    x, weight, ptr = x.contiguous(), weight.contiguous(), ptr.contiguous()
+    bias = bias.contiguous() if bias is not None else None
+    out = torch.empty((M, N), dtype=x.dtype, device=x.device)
+    L = _lib.load()
+    ws_bytes = L.gnnops_segment_matmul_workspace_bytes(T)
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=x.device)
+    with _on(x.device):
+        rc = L.gnnops_segment_matmul(x.data_ptr(), ptr.data_ptr(), weight.data_ptr(), bias.data_ptr() if bias is not None else None,
+                                     out.data_ptr(), M, K, N, T, dt, ws.data_ptr(), ws_bytes, _stream())
+    check(rc, "segment_matmul")
+    return out

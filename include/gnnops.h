@@ -460,6 +460,22 @@ int gnnops_gemm_tn_geometry(int64_t R, int64_t P, int64_t Q, int dtype, int64_t*
                             int64_t* slab_rows, int64_t* slabs);
 
 /* ---------------------------------------------------------------------------------------------
+ * Grouped product (csrc/segment_matmul.hip), pyg_lib.ops.segment_matmul: out[ptr[t] : ptr[t+1], :] = x[ptr[t] : ptr[t+1], :] @
+ * w[t] (+ bias[t]) for t < T, the per-type weight of HeteroLinear / RGCNConv. x [M, K], w [T, K, N], ptr int64 [T + 1] in
+ * DEVICE memory, bias [T, N] or NULL, out [M, N]; contiguous row-major, one dtype (F32 / F16 / BF16), fp32 accumulation and
+ * one rounding: a row gets the bits gnnops_addmm's register-staged kernel gives it. ptr is expected to start at 0, end at M
+ * and never decrease; the kernels clamp every entry into [0, M] and take a decreasing pair as an empty segment, so no ptr
+ * can make them touch a row outside [0, M) (rows no segment covers are left as they were). Two launches on the stream, no
+ * host synchronisation, no atomics; the workspace holds the int32 tile map and needs no clearing.
+ * ------------------------------------------------------------------------------------------- */
+size_t gnnops_segment_matmul_workspace_bytes(int64_t T);   /* 0 for a negative T */
+int gnnops_segment_matmul(const void* x, const int64_t* ptr, const void* w, const void* bias, void* out, int64_t M, int64_t K,
+                          int64_t N, int64_t T, int dtype, void* workspace, size_t workspace_bytes, gnnops_stream_t stream);
+/* Host only: the tile of one workgroup (a segment is cut into tile_m-row tiles from its first row on) and the K-step of
+ * the main loop; any output pointer may be NULL. */
+int gnnops_segment_matmul_geometry(int dtype, int64_t* tile_m, int64_t* tile_n, int64_t* k_step);
+
+/* ---------------------------------------------------------------------------------------------
  * Fused index_select(index_add(input, dim, index, other), dim, index).sum(dim)
  * (benchmark_fused_index_add_reduce.py:12-20). input [B,N,K], other [B,E,K], plan of index over N.
  * out_f32 [B,K] (fp32: the reference's fp16 result overflows at its own sizes). Nothing of size [B,N,K]
