@@ -30,14 +30,15 @@ the stored out or a first loop over the edges — does not move these figures: b
 The layer restatement follows torch_geometric 2.0.2's GATv2Conv (x_l = lin_l(x) is the source side and the message, x_r = lin_r(x)
 the destination side; existing self loops removed, one added per node; mean over heads when concat=False; bias last). PyG is not
 available to compare against: parity unpinned."""
-import json
+import functools
 import os
 from dataclasses import dataclass
 
 import torch
 
-from conv_chain import (BF16, DNAME, DTYPES, F16, F32, PROJECT_BAR, _lin, _q, _r, _rand, _straight_through, place, rel_err,  # noqa: F401
-                        small_plan_fits)
+import chain_harness as ch
+from chain_harness import BF16, DNAME, DTYPES, F16, F32, PROJECT_BAR, rel_err  # noqa: F401
+from conv_chain import _lin, _q, _r, _rand, _straight_through, place, small_plan_fits  # noqa: F401
 
 T_HUB = 8192          # csrc/hub.h: the degree past which the other edge passes go piecewise (this one does not yet)
 GOLDEN_FILE = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "attention_self_error.json")
@@ -149,7 +150,7 @@ class _LibraryAttention(torch.autograd.Function):
 
 # ---- cases ------------------------------------------------------------------------------------------------------------------
 @dataclass(frozen=True)
-class Case:
+class Case(ch.CaseBars):
     table: str
     name: str
     H: int
@@ -162,15 +163,6 @@ class Case:
     bar: str = "project"         # project: PROJECT_BAR for fp32 / fp16, 4 x self error for bf16; self: 4 x self error for all
     dtypes: tuple = tuple(DTYPES)
     slope: float = 0.2
-
-    def id(self, dtype):
-        return f"{self.name}-{DNAME[dtype]}"
-
-    def key(self, dtype, tensor):
-        return f"{self.table}/{self.name}/{DNAME[dtype]}/{tensor}"
-
-    def self_bar(self, dtype):
-        return self.bar == "self" or dtype == BF16
 
 
 SHAPES = [Case("shape", f"H{H}-C{C}", H, C) for H in (1, 3, 4) for C in (1, 5, 8, 64, 136)] + [Case("shape", "H4-C8-dense", 4, 8, layout="plain")]
@@ -250,17 +242,11 @@ def case_grads(case, dtype, rnd=None):
     return attention_grads(ops, ei, case.n_dst, case.H, case.slope, R, rnd=rnd)
 
 
-def self_error(case, dtype):
-    out, grads = case_grads(case, dtype)
-    out_r, grads_r = case_grads(case, dtype, rnd=dtype)
-    err = {"out": rel_err(out_r, out)}
-    for k in grads:
-        err[k] = rel_err(grads_r[k], grads[k])
-    return err
+self_error = functools.partial(ch.self_error, case_grads)
 
 
 def self_error_cases():
-    return [(c, d) for t in TABLES.values() for c in t for d in c.dtypes if c.self_bar(d)]
+    return ch.self_bar_cases(TABLES)
 
 
 # ---- the layer ----------------------------------------------------------------------------------------------------------------
@@ -344,25 +330,14 @@ PYG_STATE = {"att": (1, 4, 32), "bias": (32,), "lin_l.weight": (128, 16), "lin_l
 
 
 # ---- the table ----------------------------------------------------------------------------------------------------------------
-def self_error_table(progress=None):
-    table = {}
-    for c, d in self_error_cases():
-        for k, v in self_error(c, d).items():
-            table[c.key(d, k)] = v
-        if progress:
-            progress(c.id(d))
-    return table
+def self_error_table():
+    return ch.build_table(self_error_cases(), self_error)
 
 
 def write_self_error_table(path=GOLDEN_FILE):
     """Regenerates tests/golden/attention_self_error.json (python -c "import attention_chain as ac; ac.write_self_error_table()")."""
-    table = self_error_table()
-    with open(path, "w") as f:
-        json.dump(table, f, indent=0, sort_keys=True)
-        f.write("\n")
-    return table
+    return ch.write_table(self_error_table(), path)
 
 
 def load_self_error():
-    with open(GOLDEN_FILE) as f:
-        return json.load(f)
+    return ch.load_table(GOLDEN_FILE)

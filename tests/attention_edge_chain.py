@@ -22,15 +22,17 @@ adds the edge operand to their inputs (its own generator, so the older operands 
 torch_geometric's GATv2Conv / GATConv with edge_dim: lin_edge without a bias, remove_self_loops then add_self_loops with fill_value
 ("mean": the mean of the attributes of a node's remaining in-edges, zero for a node without any). PyG is not available to compare
 against: parity unpinned."""
-import json
+import functools
 import os
 
 import torch
 
 import attention_chain as ac
+import chain_harness as ch
 import gate_chain as gc
 from attention_chain import SPECIAL, _amax, _dot, _exp, _log, with_self_loops  # noqa: F401
-from conv_chain import BF16, DNAME, DTYPES, F16, F32, PROJECT_BAR, _q, _rand, _straight_through, place, rel_err  # noqa: F401
+from chain_harness import BF16, DNAME, DTYPES, F16, F32, PROJECT_BAR, rel_err  # noqa: F401
+from conv_chain import _q, _rand, _straight_through, place  # noqa: F401
 
 GOLDEN_FILE = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "attention_edge_self_error.json")
 SEAM_DEGREES = gc.SEAM_DEGREES      # 0, 1, 2, 3, 4, 5, 7, 8, 9, 63, 64, 65, 129: every step of the halved unrolls, and the run of 64 ids
@@ -219,41 +221,25 @@ def key(family, case, dtype, tensor):
 
 
 def self_error(family, case, dtype):
-    out, grads = case_grads(family, case, dtype)
-    out_r, grads_r = case_grads(family, case, dtype, rnd=dtype)
-    err = {"out": rel_err(out_r, out)}
-    for k in grads:
-        err[k] = rel_err(grads_r[k], grads[k])
-    return err
+    return ch.self_error(functools.partial(case_grads, family), case, dtype)
 
 
 def self_error_cases():
-    return [(f, c, d) for f, tables in FAMILIES.items() for t in tables.values() for c in t for d in c.dtypes if c.self_bar(d) and c.E > 0]
+    return [(f, c, d) for f, tables in FAMILIES.items() for c, d in ch.self_bar_cases(tables) if c.E > 0]
 
 
-def self_error_table(progress=None):
-    table = {}
-    for f, c, d in self_error_cases():
-        for k, v in self_error(f, c, d).items():
-            table[key(f, c, d, k)] = v
-        if progress:
-            progress(f"{f} {c.id(d)}")
-    return table
+def self_error_table():
+    return ch.build_table(self_error_cases(), self_error, key)
 
 
 def write_self_error_table(path=GOLDEN_FILE):
     """Regenerates tests/golden/attention_edge_self_error.json
     (python -c "import attention_edge_chain as ec; ec.write_self_error_table()")."""
-    table = self_error_table()
-    with open(path, "w") as f:
-        json.dump(table, f, indent=0, sort_keys=True)
-        f.write("\n")
-    return table
+    return ch.write_table(self_error_table(), path)
 
 
 def load_self_error():
-    with open(GOLDEN_FILE) as f:
-        return json.load(f)
+    return ch.load_table(GOLDEN_FILE)
 
 
 # ---- the layers -----------------------------------------------------------------------------------------------------------------

@@ -24,20 +24,19 @@ continuous inputs one gate in ~1e7 would flip on rounding and move a whole gradi
 
 The four layer restatements of test_conv_train_gpu.py (CGConv follows the reference's layer text, groq_script.py:91-109; GIN /
 SAGE / FiLM restate PyG 2.0.2: parity unpinned) and its comparison helpers live here too, with the same ``rnd`` option."""
-import json
 import os
 from dataclasses import dataclass
 
 import torch
 
-F32, F16, BF16 = DTYPES = [torch.float32, torch.float16, torch.bfloat16]
-DNAME = {F32: "f32", F16: "f16", BF16: "bf16"}
+import chain_harness as ch
+from chain_harness import BF16, DNAME, DTYPES, F16, F32, PROJECT_BAR, rel_err  # noqa: F401  (these names were first defined here, and stay importable from here)
+
 VEC = {F32: 4, F16: 8, BF16: 8}            # Elem<T>::VEC: elements of a 16-byte piece
 T_HUB = 8192                               # csrc/hub.h: more edges than this and a row is reduced piecewise
 GRID_PIECES = 8192 * 256                   # edge_grad_kernel: 8192 workgroups of 256 pieces; more pieces and the grid-stride loop iterates
 SMALL_MAX_E, SMALL_MAX_N = 24576, 40000    # gnnops_plan_small_fits (include/gnnops.h)
 SOFTPLUS_SEAM = 6.907755278982137          # exp(-|z|) = 1e-3: the series / log seam of softplus_f
-PROJECT_BAR = {F32: 3e-5, F16: 1e-2}       # test_conv_train_gpu.py
 FILM_F16_BAR = 3e-2
 FUNCTORS = ("copy", "cgconv", "cgconv_w", "film")
 PARTS = {"copy": (1, 0, 0), "cgconv": (2, 2, 0), "cgconv_w": (2, 2, 2), "film": (1, 2, 0)}   # K-wide parts of q, p, w
@@ -164,19 +163,13 @@ def mean_scales(edge_index, n_src, n_dst):
     return {"p": deg.unsqueeze(1), "w": deg[dst].unsqueeze(1), "q": sq.unsqueeze(1)}
 
 
-def rel_err(got, want):
-    if want.numel() == 0:
-        return 0.0
-    return float((got - want).abs().max()) / max(float(want.abs().max()), 1e-6)
-
-
 def scaled(name, t, scales):
     return t * scales[name] if scales is not None and name in scales else t
 
 
 # ---- case tables ----------------------------------------------------------------------------------------------------------
 @dataclass(frozen=True)
-class Case:
+class Case(ch.CaseBars):
     table: str
     name: str
     functor: str
@@ -193,15 +186,6 @@ class Case:
     dtypes: tuple = tuple(DTYPES)
     bar: str = "project"         # project: PROJECT_BAR for fp32 / fp16, 4 x self error for bf16; self: 4 x self error for all
     ones: bool = False           # the functional is out.sum(): an expanded gradient of stride 0
-
-    def id(self, dtype):
-        return f"{self.name}-{DNAME[dtype]}"
-
-    def key(self, dtype, tensor):
-        return f"{self.table}/{self.name}/{DNAME[dtype]}/{tensor}"
-
-    def self_bar(self, dtype):
-        return self.bar == "self" or dtype == BF16
 
     def project_bar(self, dtype):
         return FILM_F16_BAR if (self.functor == "film" and dtype == F16) else PROJECT_BAR[dtype]
@@ -350,32 +334,20 @@ def self_error(case, dtype):
 
 
 def self_error_cases():
-    return [(c, d) for t in TABLES.values() for c in t for d in c.dtypes if c.self_bar(d)]
+    return ch.self_bar_cases(TABLES)
 
 
-def self_error_table(progress=None):
-    table = {}
-    for c, d in self_error_cases():
-        for k, v in self_error(c, d).items():
-            table[c.key(d, k)] = v
-        if progress:
-            progress(c.id(d))
-    table.update(layer_self_error_table())
-    return table
+def self_error_table():
+    return {**ch.build_table(self_error_cases(), self_error), **layer_self_error_table()}
 
 
 def write_self_error_table(path=GOLDEN_FILE):
     """Regenerates tests/golden/conv_self_error.json (python -c "import conv_chain; conv_chain.write_self_error_table()")."""
-    table = self_error_table()
-    with open(path, "w") as f:
-        json.dump(table, f, indent=0, sort_keys=True)
-        f.write("\n")
-    return table
+    return ch.write_table(self_error_table(), path)
 
 
 def load_self_error():
-    with open(GOLDEN_FILE) as f:
-        return json.load(f)
+    return ch.load_table(GOLDEN_FILE)
 
 
 def place(t, layout, device="cuda"):

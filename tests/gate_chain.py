@@ -22,15 +22,17 @@ tensor, for bf16 and for the range, heavy and mask tables — the rule of test_a
 The layer restatements follow torch_geometric 2.0.x (GATConv: lin_src / lin_dst / att_src / att_dst; models.attentive_fp: GATEConv
 and AttentiveFP). Where the device stores a tensor in 16 bits that a leaky ReLU then gates on (q, d, u), the float64 chain rounds it
 straight-through, for the reason attention_chain.py gives. PyG is not available to compare against: parity unpinned."""
-import json
+import functools
 import os
 from dataclasses import dataclass
 
 import torch
 
 import attention_chain as ac
+import chain_harness as ch
 from attention_chain import HEAVY_DEGREES, RANGE_ROWS, SPECIAL, T_HUB, _amax, _dot, _exp, _log, with_self_loops  # noqa: F401
-from conv_chain import BF16, DNAME, DTYPES, F16, F32, PROJECT_BAR, _q, _rand, _straight_through, place, rel_err, small_plan_fits  # noqa: F401
+from chain_harness import BF16, DNAME, DTYPES, F16, F32, PROJECT_BAR, rel_err  # noqa: F401
+from conv_chain import _q, _rand, _straight_through, place, small_plan_fits  # noqa: F401
 
 GOLDEN_FILE = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "gate_attention_self_error.json")
 # the unrolls of the new kernels are 8, 4, 2, 1 forward and 4, 2, 1 backward (halved with u): U - 1, U, U + 1 of each, and the id run of 64
@@ -120,7 +122,7 @@ def attention_grads(ops, edge_index, n_dst, H, row_slope, slope, edge_scale, R, 
 
 # ---- cases ------------------------------------------------------------------------------------------------------------------
 @dataclass(frozen=True)
-class Case:
+class Case(ch.CaseBars):
     table: str
     name: str
     H: int
@@ -143,15 +145,6 @@ class Case:
     @property
     def row_slope(self):
         return VARIANTS[self.variant][1]
-
-    def id(self, dtype):
-        return f"{self.name}-{DNAME[dtype]}"
-
-    def key(self, dtype, tensor):
-        return f"{self.table}/{self.name}/{DNAME[dtype]}/{tensor}"
-
-    def self_bar(self, dtype):
-        return self.bar == "self" or dtype == BF16
 
 
 def _both(table, shapes, **kw):
@@ -242,41 +235,24 @@ def case_grads(case, dtype, rnd=None):
     return attention_grads(ops, ei, case.n_dst, case.H, case.row_slope, case.slope, ks, R, rnd=rnd)
 
 
-def self_error(case, dtype):
-    out, grads = case_grads(case, dtype)
-    out_r, grads_r = case_grads(case, dtype, rnd=dtype)
-    err = {"out": rel_err(out_r, out)}
-    for k in grads:
-        err[k] = rel_err(grads_r[k], grads[k])
-    return err
+self_error = functools.partial(ch.self_error, case_grads)
 
 
 def self_error_cases():
-    return [(c, d) for t in TABLES.values() for c in t for d in c.dtypes if c.self_bar(d) and c.E > 0]
+    return [(c, d) for c, d in ch.self_bar_cases(TABLES) if c.E > 0]
 
 
-def self_error_table(progress=None):
-    table = {}
-    for c, d in self_error_cases():
-        for k, v in self_error(c, d).items():
-            table[c.key(d, k)] = v
-        if progress:
-            progress(c.id(d))
-    return table
+def self_error_table():
+    return ch.build_table(self_error_cases(), self_error)
 
 
 def write_self_error_table(path=GOLDEN_FILE):
     """Regenerates tests/golden/gate_attention_self_error.json (python -c "import gate_chain as gc; gc.write_self_error_table()")."""
-    table = self_error_table()
-    with open(path, "w") as f:
-        json.dump(table, f, indent=0, sort_keys=True)
-        f.write("\n")
-    return table
+    return ch.write_table(self_error_table(), path)
 
 
 def load_self_error():
-    with open(GOLDEN_FILE) as f:
-        return json.load(f)
+    return ch.load_table(GOLDEN_FILE)
 
 
 # ---- the layers ---------------------------------------------------------------------------------------------------------------

@@ -17,14 +17,16 @@ keep their pre-activations off the kink of leaky_relu: float32 and float64 must 
 
 The model (gnnops.conv.GATv2, the reference's GATv2REG) restated in float64: per layer the GATv2 attention of attention_chain
 (imported, not edited), this file's epilogue, then the mean over each graph's nodes and a Linear."""
-import json
+import functools
 import os
 from dataclasses import dataclass
 
 import torch
 
 import attention_chain as ac
-from conv_chain import BF16, DNAME, DTYPES, F16, F32, PROJECT_BAR, _lin, _q, _r, _rand, _straight_through, place, rel_err  # noqa: F401
+import chain_harness as ch
+from chain_harness import BF16, DNAME, DTYPES, F16, F32, PROJECT_BAR, rel_err  # noqa: F401
+from conv_chain import _lin, _q, _r, _rand, _straight_through, place  # noqa: F401
 
 GOLDEN_FILE = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "head_act_norm_self_error.json")
 EPS = 1e-5
@@ -170,7 +172,7 @@ def norm_grads(ops, H, relu, R, rnd=None, eps=EPS):
 
 # ---- cases ------------------------------------------------------------------------------------------------------------------
 @dataclass(frozen=True)
-class Case:
+class Case(ch.CaseBars):
     table: str
     name: str
     H: int
@@ -184,15 +186,6 @@ class Case:
     values: str = "random"       # random | constant | dropped | gamma_zero | big_mean | negative
     bar: str = "project"         # project: PROJECT_BAR for fp32 / fp16, 4 x self error for bf16; self: 4 x self error for all
     dtypes: tuple = tuple(DTYPES)
-
-    def id(self, dtype):
-        return f"{self.name}-{DNAME[dtype]}"
-
-    def key(self, dtype, tensor):
-        return f"{self.table}/{self.name}/{DNAME[dtype]}/{tensor}"
-
-    def self_bar(self, dtype):
-        return self.bar == "self" or dtype == BF16
 
 
 SHAPES = [Case("shape", f"H{H}-C{C}", H, C) for H in (1, 3, 4) for C in (1, 5, 8, 64, 136, 1024)]
@@ -251,17 +244,11 @@ def case_grads(case, dtype, rnd=None, ones=False):
     return norm_grads(ops, case.H, case.relu, torch.ones_like(R) if ones else R, rnd=rnd)
 
 
-def self_error(case, dtype):
-    out, grads = case_grads(case, dtype)
-    out_r, grads_r = case_grads(case, dtype, rnd=dtype)
-    err = {"out": rel_err(out_r, out)}
-    for n in grads:
-        err[n] = rel_err(grads_r[n], grads[n])
-    return err
+self_error = functools.partial(ch.self_error, case_grads)
 
 
 def self_error_cases():
-    return [(c, d) for t in TABLES.values() for c in t for d in c.dtypes if c.self_bar(d)]
+    return ch.self_bar_cases(TABLES)
 
 
 # ---- the model ----------------------------------------------------------------------------------------------------------------
@@ -384,13 +371,8 @@ def model_key(mode, dtype, tensor):
 
 
 # ---- the table ----------------------------------------------------------------------------------------------------------------
-def self_error_table(progress=None):
-    table = {}
-    for c, d in self_error_cases():
-        for k, v in self_error(c, d).items():
-            table[c.key(d, k)] = v
-        if progress:
-            progress(c.id(d))
+def self_error_table():
+    table = ch.build_table(self_error_cases(), self_error)
     for mode, train in (("eval", False), ("train", True)):
         for k, v in model_self_error(BF16, train).items():
             table[model_key(mode, BF16, k)] = v
@@ -399,13 +381,8 @@ def self_error_table(progress=None):
 
 def write_self_error_table(path=GOLDEN_FILE):
     """Regenerates tests/golden/head_act_norm_self_error.json (python -c "import norm_chain as nc; nc.write_self_error_table()")."""
-    table = self_error_table()
-    with open(path, "w") as f:
-        json.dump(table, f, indent=0, sort_keys=True)
-        f.write("\n")
-    return table
+    return ch.write_table(self_error_table(), path)
 
 
 def load_self_error():
-    with open(GOLDEN_FILE) as f:
-        return json.load(f)
+    return ch.load_table(GOLDEN_FILE)

@@ -19,13 +19,14 @@ attention_chain.py.
 Inputs lie on a grid of 1 / 1024 in [-1, 1] before they are rounded to the storage type: a product of two such numbers is exact in
 float32 and in float64, so both chains and the kernel compare the SAME numbers and pick the same winner; with continuous fp32 inputs two
 products within an ulp would now and then order differently in float64 and move a whole gradient term."""
-import json
 import os
 from dataclasses import dataclass
 
 import torch
 
-from conv_chain import BF16, DNAME, DTYPES, F16, F32, PROJECT_BAR, _q, rel_err  # noqa: F401
+import chain_harness as ch
+from chain_harness import BF16, DNAME, DTYPES, F16, F32, PROJECT_BAR, rel_err  # noqa: F401
+from conv_chain import _q
 
 GOLDEN_FILE = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "spmm_reduce_self_error.json")
 REDUCES = ("sum", "mean", "min", "max")
@@ -233,30 +234,14 @@ def self_error_cases():
 
 
 def self_error_table():
-    table = {}
-    for c, d, r in self_error_cases():
-        for k, v in self_error(c, d, r).items():
-            table[c.key(d, r, k)] = v
-    return table
+    return ch.build_table(self_error_cases(), self_error, lambda case, dtype, reduce, tensor: case.key(dtype, reduce, tensor))
 
 
 def write_self_error_table(path=GOLDEN_FILE):
     """Regenerates tests/golden/spmm_reduce_self_error.json
     (python -c "import spmm_reduce_chain as sc; sc.write_self_error_table()")."""
-    table = self_error_table()
-    with open(path, "w") as f:
-        json.dump(table, f, indent=0, sort_keys=True)
-        f.write("\n")
-    return table
+    return ch.write_table(self_error_table(), path)
 
 
 def load_self_error():
-    with open(GOLDEN_FILE) as f:
-        return json.load(f)
-
-
-def bar(case, dtype, reduce, tensor, table=None):
-    """PROJECT_BAR for fp32 / fp16; bf16: 4 x the chain's recorded self error (attention_chain.py's rule)."""
-    if dtype != BF16:
-        return PROJECT_BAR[dtype]
-    return 4 * (table or load_self_error())[case.key(dtype, reduce, tensor)]
+    return ch.load_table(GOLDEN_FILE)

@@ -8,6 +8,7 @@ import pytest
 import torch
 
 import attention_chain as ac
+import chain_harness as ch
 
 F64 = torch.float64
 
@@ -144,17 +145,4 @@ def test_case_tables_have_their_edges():
 
 def test_self_error_table(capsys):
     """The numbers the bars of the GPU tests are 4 x of: recomputed from the chain alone, equal to the committed JSON."""
-    recorded = ac.load_self_error()
-    table = ac.self_error_table()
-    with capsys.disabled():
-        worst = {}
-        for k, v in table.items():
-            t, _, d = k.split("/")[:3]
-            worst[(t, d)] = max(worst.get((t, d), (0.0, "")), (v, k))
-        print("\nself error of tests/attention_chain.py (library-order float32 chain against the float64 chain)")
-        for (t, d), (v, k) in sorted(worst.items()):
-            print(f"  worst of {t:6s} {d:4s} {v:.3e}  ({k})")
-    assert set(recorded) == set(table)
-    for k, v in table.items():
-        assert v == v and 0 <= v < 5e-2, (k, v)
-        assert v == recorded[k], (k, v, recorded[k])
+    ch.check_self_error_table(ac, 5e-2, capsys)

@@ -6,6 +6,7 @@ import torch
 
 import attention_chain as ac
 import attention_edge_chain as ec
+import chain_harness as ch
 import gate_chain as gc
 
 F64 = torch.float64
@@ -189,17 +190,4 @@ def test_case_tables_have_their_edges():
 
 def test_self_error_table(capsys):
     """The numbers the bars of the GPU tests are 4 x of: recomputed from the chain alone, equal to the committed JSON."""
-    recorded = ec.load_self_error()
-    table = ec.self_error_table()
-    with capsys.disabled():
-        worst = {}
-        for k, v in table.items():
-            f, t, _, d = k.split("/")[:4]
-            worst[(f, t, d)] = max(worst.get((f, t, d), (0.0, "")), (v, k))
-        print("\nself error of tests/attention_edge_chain.py (library-order float32 chain against the float64 chain)")
-        for (f, t, d), (v, k) in sorted(worst.items()):
-            print(f"  worst of {f} {t:6s} {d:4s} {v:.3e}  ({k})")
-    assert set(recorded) == set(table)
-    for k, v in table.items():
-        assert v == v and 0 <= v < 0.25, (k, v)      # a bar of 4 x this must stay below 1, or it would admit a zero gradient
-        assert v == recorded[k], (k, v, recorded[k])
+    ch.check_self_error_table(ec, 0.25, capsys)      # a bar of 4 x this must stay below 1, or it would admit a zero gradient

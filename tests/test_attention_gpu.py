@@ -17,33 +17,17 @@ import pytest
 import torch
 
 import attention_chain as ac
+import chain_harness as ch
 
 pytestmark = pytest.mark.gpu
 
 SELF_ERROR = ac.load_self_error()
-_REFERENCE = {}
+_reference = ch.Reference(ac.case_grads)
 
 
 @pytest.fixture(scope="module")
 def conv():
-    import gnnops
-    from gnnops import conv as c
-
-    gnnops.load_library()
-    return c
-
-
-def _params(table):
-    pairs = [(c, d) for c in table for d in c.dtypes]
-    return {"argvalues": pairs, "ids": [c.id(d) for c, d in pairs]}
-
-
-def _reference(case, dtype):
-    """The float64 chain of a case, computed once and shared."""
-    key = (case.table, case.name, dtype)
-    if key not in _REFERENCE:
-        _REFERENCE[key] = ac.case_grads(case, dtype)
-    return _REFERENCE[key]
+    return ch.load_conv()
 
 
 def _device_run(conv, case, dtype, edge_index=None):
@@ -58,57 +42,42 @@ def _device_run(conv, case, dtype, edge_index=None):
     return out, leaf
 
 
-def _judge(case, dtype, name, got, want):
-    assert got is not None, f"{name}: no gradient"
-    got = got.detach().double().cpu()
-    assert got.shape == want.shape, (name, got.shape, want.shape)
-    assert bool(torch.isfinite(got).all()), f"{case.id(dtype)} {name}: not finite"
-    err = ac.rel_err(got, want)
-    if case.self_bar(dtype):
-        key = case.key(dtype, name)
-        bar, why = 4 * SELF_ERROR[key], f"4 x self error, {key}"
-    else:
-        bar, why = ac.PROJECT_BAR[dtype], "the project's bar"
-    print(f"{case.id(dtype)} {name}: {err:.3e} (bar {bar:.3e}: {why})")
-    assert err <= bar, f"{case.id(dtype)} {name}: error {err:.3e} of scale exceeds {bar:.3e} ({why})"
-
-
 def _run_case(conv, case, dtype):
     want_out, want = _reference(case, dtype)
     out, leaf = _device_run(conv, case, dtype)
-    _judge(case, dtype, "out", out, want_out)
+    ch.judge_case(case, dtype, "out", out, want_out, SELF_ERROR)
     for k, w in want.items():
-        _judge(case, dtype, k, leaf[k].grad, w)
+        ch.judge_case(case, dtype, k, leaf[k].grad, w, SELF_ERROR)
     return out
 
 
-@pytest.mark.parametrize("case,dtype", **_params(ac.SHAPES))
+@pytest.mark.parametrize("case,dtype", **ch.params(ac.SHAPES))
 def test_shapes(conv, case, dtype):
     _run_case(conv, case, dtype)
 
 
-@pytest.mark.parametrize("case,dtype", **_params(ac.SEAMS))
+@pytest.mark.parametrize("case,dtype", **ch.params(ac.SEAMS))
 def test_degree_seams(conv, case, dtype):
     out = _run_case(conv, case, dtype)
     assert float(out[0].detach().abs().max()) == 0.0   # the destination without an edge
 
 
-@pytest.mark.parametrize("case,dtype", **_params(ac.RANGE))
+@pytest.mark.parametrize("case,dtype", **ch.params(ac.RANGE))
 def test_online_rescale(conv, case, dtype):
     _run_case(conv, case, dtype)
 
 
-@pytest.mark.parametrize("case,dtype", **_params(ac.HEAVY))
+@pytest.mark.parametrize("case,dtype", **ch.params(ac.HEAVY))
 def test_heavy_destinations(conv, case, dtype):
     _run_case(conv, case, dtype)
 
 
-@pytest.mark.parametrize("case,dtype", **_params(ac.PLAN))
+@pytest.mark.parametrize("case,dtype", **ch.params(ac.PLAN))
 def test_both_sides_of_the_one_launch_plan(conv, case, dtype):
     _run_case(conv, case, dtype)
 
 
-@pytest.mark.parametrize("case,dtype", **_params(ac.EDGES[:1]))
+@pytest.mark.parametrize("case,dtype", **ch.params(ac.EDGES[:1]))
 def test_repeated_edges_and_self_loops(conv, case, dtype):
     _run_case(conv, case, dtype)
 

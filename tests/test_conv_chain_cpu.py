@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 import torch
 
+import chain_harness as ch
 import conv_chain as cc
 from oracle import conv_oracle
 
@@ -276,17 +277,7 @@ def test_saturation_table_has_its_values():
 
 def test_self_error_table_is_the_recording(capsys):
     """The numbers the bars of the GPU tests are 4 x of: recomputed from the chain alone, equal to tests/golden/conv_self_error.json."""
-    recorded = cc.load_self_error()
-    table = cc.self_error_table()
-    with capsys.disabled():
-        print("\nself error of tests/conv_chain.py (library-order float32 chain against the float64 chain, relative to max |reference|)")
-        worst = {}
-        for k, v in table.items():
-            t, _, d, _ = k.split("/")[:4]
-            worst[(t, d)] = max(worst.get((t, d), (0.0, "")), (v, k))
-        for (t, d), (v, k) in sorted(worst.items()):
-            print(f"  worst of {t:10s} {d:4s} {v:.3e}  ({k})")
-    assert set(recorded) == set(table)
+    table, recorded = ch.recomputed_table(cc, capsys, "library-order float32 chain against the float64 chain, relative to max |reference|")
     for k, v in table.items():
         assert v == v and 0 <= v < 2e-2, (k, v)
         if k.startswith("layer/"):       # the layers' float32 products go through the host's BLAS, which is not bit-reproducible

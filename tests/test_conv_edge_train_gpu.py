@@ -18,6 +18,7 @@ The plan-cache test runs a copy and a cgconv backward over one edge_index object
 import pytest
 import torch
 
+import chain_harness as ch
 import conv_chain as cc
 
 pytestmark = pytest.mark.gpu
@@ -27,20 +28,7 @@ SELF_ERROR = cc.load_self_error()
 
 @pytest.fixture(scope="module")
 def conv():
-    import gnnops
-    from gnnops import conv as c
-
-    gnnops.load_library()
-    return c
-
-
-def _ids(table):
-    return [(c, d) for c in table for d in c.dtypes]
-
-
-def _params(table):
-    pairs = _ids(table)
-    return {"argvalues": pairs, "ids": [c.id(d) for c, d in pairs]}
+    return ch.load_conv()
 
 
 def _device_run(conv, case, dtype, ops, ei, R, edge_index=None):
@@ -64,52 +52,37 @@ def _device_run(conv, case, dtype, ops, ei, R, edge_index=None):
     return out, leaf
 
 
-def _judge(case, dtype, name, got, want, scales):
-    assert got is not None, f"{name}: no gradient"
-    got = got.detach().double().cpu()
-    assert got.shape == want.shape, (name, got.shape, want.shape)
-    assert bool(torch.isfinite(got).all()), f"{case.id(dtype)} {name}: not finite"
-    err = cc.rel_err(cc.scaled(name, got, scales), cc.scaled(name, want, scales))
-    if case.self_bar(dtype):
-        key = case.key(dtype, name)
-        bar, why = 4 * SELF_ERROR[key], f"4 x self error, {key}"
-    else:
-        bar, why = case.project_bar(dtype), "the project's bar"
-    print(f"{case.id(dtype)} {name}: {err:.3e} (bar {bar:.3e}: {why})")
-    assert err <= bar, f"{case.id(dtype)} {name}: error {err:.3e} of scale exceeds {bar:.3e} ({why})"
-
-
 def _run_case(conv, case, dtype):
     ops, ei, R = cc.inputs(case, dtype)
     want_out, want, scales = cc.case_grads(case, dtype)
     out, leaf = _device_run(conv, case, dtype, ops, ei, R)
-    _judge(case, dtype, "out", out, want_out, None)
-    for k, w in want.items():
-        _judge(case, dtype, k, leaf[k].grad, w, scales)
+    ch.judge_case(case, dtype, "out", out, want_out, SELF_ERROR)
+    for k, w in want.items():       # a mean's gradients are compared degree-scaled
+        ch.judge_case(case, dtype, k, leaf[k].grad, w, SELF_ERROR, transform=lambda t, k=k: cc.scaled(k, t, scales))
 
 
-@pytest.mark.parametrize("case,dtype", **_params(cc.DISPATCH))
+@pytest.mark.parametrize("case,dtype", **ch.params(cc.DISPATCH))
 def test_dispatch(conv, case, dtype):
     _run_case(conv, case, dtype)
 
 
-@pytest.mark.parametrize("case,dtype", **_params(cc.SHAPES))
+@pytest.mark.parametrize("case,dtype", **ch.params(cc.SHAPES))
 def test_shape_edges(conv, case, dtype):
     _run_case(conv, case, dtype)
 
 
-@pytest.mark.parametrize("case,dtype", **_params(cc.GRIDWRAP))
+@pytest.mark.parametrize("case,dtype", **ch.params(cc.GRIDWRAP))
 def test_grid_wrap(conv, case, dtype):
     assert case.pieces(dtype) > cc.GRID_PIECES
     _run_case(conv, case, dtype)
 
 
-@pytest.mark.parametrize("case,dtype", **_params(cc.HUBS))
+@pytest.mark.parametrize("case,dtype", **ch.params(cc.HUBS))
 def test_hubs(conv, case, dtype):
     _run_case(conv, case, dtype)
 
 
-@pytest.mark.parametrize("case,dtype", **_params(cc.SATURATION))
+@pytest.mark.parametrize("case,dtype", **ch.params(cc.SATURATION))
 def test_saturation(conv, case, dtype):
     _run_case(conv, case, dtype)
 

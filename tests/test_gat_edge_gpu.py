@@ -7,35 +7,19 @@ import pytest
 import torch
 
 import attention_edge_chain as ec
+import chain_harness as ch
 import gate_chain as gc
 
 pytestmark = pytest.mark.gpu
 
 SELF_ERROR = ec.load_self_error()
-_REFERENCE = {}
 FAMILY = "v1"
+_reference = ch.Reference(lambda case, dtype, sorted_edges: ec.case_grads(FAMILY, case, dtype, sorted_edges=sorted_edges))
 
 
 @pytest.fixture(scope="module")
 def conv():
-    import gnnops
-    from gnnops import conv as c
-
-    gnnops.load_library()
-    return c
-
-
-def _params(table):
-    pairs = [(c, d) for c in table for d in c.dtypes]
-    return {"argvalues": pairs, "ids": [c.id(d) for c, d in pairs]}
-
-
-def _reference(case, dtype, sorted_edges=False):
-    """The float64 chain of a case, computed once and shared."""
-    key = (case.table, case.name, dtype, sorted_edges)
-    if key not in _REFERENCE:
-        _REFERENCE[key] = ec.case_grads(FAMILY, case, dtype, sorted_edges=sorted_edges)
-    return _REFERENCE[key]
+    return ch.load_conv()
 
 
 def _device_run(conv, case, dtype, sorted_edges=False, c="case"):
@@ -52,43 +36,28 @@ def _device_run(conv, case, dtype, sorted_edges=False, c="case"):
     return out, leaf
 
 
-def _judge(case, dtype, name, got, want):
-    assert got is not None, f"{name}: no gradient"
-    got = got.detach().double().cpu()
-    assert got.shape == want.shape, (name, got.shape, want.shape)
-    assert bool(torch.isfinite(got).all()), f"{case.id(dtype)} {name}: not finite"
-    err = ec.rel_err(got, want)
-    if case.self_bar(dtype):
-        key = ec.key(FAMILY, case, dtype, name)
-        bar, why = 4 * SELF_ERROR[key], f"4 x self error, {key}"
-    else:
-        bar, why = ec.PROJECT_BAR[dtype], "the project's bar"
-    print(f"{case.id(dtype)} {name}: {err:.3e} (bar {bar:.3e}: {why})")
-    assert err <= bar, f"{case.id(dtype)} {name}: error {err:.3e} of scale exceeds {bar:.3e} ({why})"
-
-
 def _run_case(conv, case, dtype, sorted_edges=False):
     want_out, want = _reference(case, dtype, sorted_edges)
     out, leaf = _device_run(conv, case, dtype, sorted_edges)
     assert set(leaf) == set(want) == {"q", "d", "att", "c"}
-    _judge(case, dtype, "out", out, want_out)
+    ch.judge_case(case, dtype, "out", out, want_out, SELF_ERROR, key=ec.key(FAMILY, case, dtype, "out"))
     for k, w in want.items():
-        _judge(case, dtype, k, leaf[k].grad, w)
+        ch.judge_case(case, dtype, k, leaf[k].grad, w, SELF_ERROR, key=ec.key(FAMILY, case, dtype, k))
     return out, leaf
 
 
-@pytest.mark.parametrize("case,dtype", **_params(ec.V1["shape"]))
+@pytest.mark.parametrize("case,dtype", **ch.params(ec.V1["shape"]))
 def test_shapes(conv, case, dtype):
     _run_case(conv, case, dtype)
 
 
-@pytest.mark.parametrize("case,dtype", **_params(ec.V1["seams"]))
+@pytest.mark.parametrize("case,dtype", **ch.params(ec.V1["seams"]))
 def test_degree_seams(conv, case, dtype):
     out, _ = _run_case(conv, case, dtype)
     assert float(out[0].detach().abs().max()) == 0.0   # the destination without an edge
 
 
-@pytest.mark.parametrize("case,dtype", **_params(ec.V1["seams"]))
+@pytest.mark.parametrize("case,dtype", **ch.params(ec.V1["seams"]))
 def test_degree_seams_sorted_by_destination(conv, case, dtype):
     """The same edges sorted by destination, through the plan and through the raw launches with perm = NULL: the same bits."""
     out, leaf = _run_case(conv, case, dtype, sorted_edges=True)
@@ -104,17 +73,17 @@ def test_degree_seams_sorted_by_destination(conv, case, dtype):
     assert torch.equal(d_d, leaf["d"].grad) and torch.equal(d_att, leaf["att"].grad) and torch.equal(d_c, leaf["c"].grad)
 
 
-@pytest.mark.parametrize("case,dtype", **_params(ec.V1["range"]))
+@pytest.mark.parametrize("case,dtype", **ch.params(ec.V1["range"]))
 def test_online_rescale(conv, case, dtype):
     _run_case(conv, case, dtype)
 
 
-@pytest.mark.parametrize("case,dtype", **_params(ec.V1["heavy"]))
+@pytest.mark.parametrize("case,dtype", **ch.params(ec.V1["heavy"]))
 def test_heavy_destinations(conv, case, dtype):
     _run_case(conv, case, dtype)
 
 
-@pytest.mark.parametrize("case,dtype", **_params(ec.V1["edges"][:1]))
+@pytest.mark.parametrize("case,dtype", **ch.params(ec.V1["edges"][:1]))
 def test_repeated_edges_and_self_loops(conv, case, dtype):
     out, _ = _run_case(conv, case, dtype)
     assert float(out[3].detach().abs().max()) == 0.0   # destination 3 has no edge: a zero row
@@ -155,7 +124,7 @@ def test_widest_row(conv):
 ZERO_CASES = [ec.V1["shape"][7], ec.V1["shape"][4], ec.V1["seams"][2], ec.V1["shape"][-1], ec.V1["heavy"][0]]
 
 
-@pytest.mark.parametrize("case,dtype", **_params(ZERO_CASES))
+@pytest.mark.parametrize("case,dtype", **ch.params(ZERO_CASES))
 def test_zero_edge_score_is_the_call_without_it(conv, case, dtype):
     a_out, a = _device_run(conv, case, dtype, c=None)
     b_out, b = _device_run(conv, case, dtype, c="zero")
@@ -182,7 +151,7 @@ def test_edge_score_alone_requiring_grad_goes_through_autograd(conv):
     out = conv.edge_attention_v1(dev["q"], dev["d"], dev["att"], ei.cuda(), case.n_dst, case.H, negative_slope=case.slope, edge_score=c)
     assert out.requires_grad
     (out * R.float().cuda()).sum().backward()
-    _, want = _reference(case, torch.float32)
+    _, want = _reference(case, torch.float32, False)
     assert ec.rel_err(c.grad.double().cpu(), want["c"]) <= ec.PROJECT_BAR[torch.float32]
 
 

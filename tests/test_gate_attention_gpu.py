@@ -16,34 +16,18 @@ distance from itself (tests/golden/gate_attention_self_error.json) for bf16 and 
 import pytest
 import torch
 
+import chain_harness as ch
 import gate_chain as gc
 
 pytestmark = pytest.mark.gpu
 
 SELF_ERROR = gc.load_self_error()
-_REFERENCE = {}
+_reference = ch.Reference(gc.case_grads)
 
 
 @pytest.fixture(scope="module")
 def conv():
-    import gnnops
-    from gnnops import conv as c
-
-    gnnops.load_library()
-    return c
-
-
-def _params(table):
-    pairs = [(c, d) for c in table for d in c.dtypes]
-    return {"argvalues": pairs, "ids": [c.id(d) for c, d in pairs]}
-
-
-def _reference(case, dtype):
-    """The float64 chain of a case, computed once and shared."""
-    key = (case.table, case.name, dtype)
-    if key not in _REFERENCE:
-        _REFERENCE[key] = gc.case_grads(case, dtype)
-    return _REFERENCE[key]
+    return ch.load_conv()
 
 
 def _call(conv, case, leaf, ei, ks, layout=None):
@@ -64,60 +48,45 @@ def _device_run(conv, case, dtype, edge_index=None, edge_scale="case"):
     return out, leaf
 
 
-def _judge(case, dtype, name, got, want):
-    assert got is not None, f"{name}: no gradient"
-    got = got.detach().double().cpu()
-    assert got.shape == want.shape, (name, got.shape, want.shape)
-    assert bool(torch.isfinite(got).all()), f"{case.id(dtype)} {name}: not finite"
-    err = gc.rel_err(got, want)
-    if case.self_bar(dtype):
-        key = case.key(dtype, name)
-        bar, why = 4 * SELF_ERROR[key], f"4 x self error, {key}"
-    else:
-        bar, why = gc.PROJECT_BAR[dtype], "the project's bar"
-    print(f"{case.id(dtype)} {name}: {err:.3e} (bar {bar:.3e}: {why})")
-    assert err <= bar, f"{case.id(dtype)} {name}: error {err:.3e} of scale exceeds {bar:.3e} ({why})"
-
-
 def _run_case(conv, case, dtype):
     want_out, want = _reference(case, dtype)
     out, leaf = _device_run(conv, case, dtype)
     assert set(leaf) == set(want)
-    _judge(case, dtype, "out", out, want_out)
+    ch.judge_case(case, dtype, "out", out, want_out, SELF_ERROR)
     for k, w in want.items():
-        _judge(case, dtype, k, leaf[k].grad, w)
+        ch.judge_case(case, dtype, k, leaf[k].grad, w, SELF_ERROR)
     return out, leaf
 
 
-@pytest.mark.parametrize("case,dtype", **_params(gc.SHAPES))
+@pytest.mark.parametrize("case,dtype", **ch.params(gc.SHAPES))
 def test_shapes(conv, case, dtype):
     _run_case(conv, case, dtype)
 
 
-@pytest.mark.parametrize("case,dtype", **_params(gc.SEAMS))
+@pytest.mark.parametrize("case,dtype", **ch.params(gc.SEAMS))
 def test_degree_seams(conv, case, dtype):
     out, _ = _run_case(conv, case, dtype)
     assert float(out[0].detach().abs().max()) == 0.0   # the destination without an edge
 
 
-@pytest.mark.parametrize("case,dtype", **_params(gc.RANGE))
+@pytest.mark.parametrize("case,dtype", **ch.params(gc.RANGE))
 def test_online_rescale(conv, case, dtype):
     _run_case(conv, case, dtype)
 
 
-@pytest.mark.parametrize("case,dtype", **_params(gc.HEAVY))
+@pytest.mark.parametrize("case,dtype", **ch.params(gc.HEAVY))
 def test_heavy_destinations(conv, case, dtype):
     _run_case(conv, case, dtype)
 
 
-@pytest.mark.parametrize("case,dtype", **_params(gc.MASK))
+@pytest.mark.parametrize("case,dtype", **ch.params(gc.MASK))
 def test_edge_scale_with_a_dead_destination(conv, case, dtype):
     out, leaf = _run_case(conv, case, dtype)
     assert float(out[gc.MASK_DEAD_DST].detach().abs().max()) == 0.0       # every edge dropped: exactly zero
     assert all(bool(torch.isfinite(v.grad).all()) for v in leaf.values())
 
 
-@pytest.mark.parametrize("case,dtype", **_params(gc.MASK))
+@pytest.mark.parametrize("case,dtype", **ch.params(gc.MASK))
 def test_mask_of_ones_is_no_mask(conv, case, dtype):
     _, ei, _, _ = gc.inputs(case, dtype)
     ones = torch.ones(ei.size(1), case.H, dtype=dtype, device="cuda")
@@ -128,12 +97,12 @@ def test_mask_of_ones_is_no_mask(conv, case, dtype):
         assert torch.equal(a[k].grad, b[k].grad), k
 
 
-@pytest.mark.parametrize("case,dtype", **_params(gc.PLAN))
+@pytest.mark.parametrize("case,dtype", **ch.params(gc.PLAN))
 def test_both_sides_of_the_one_launch_plan(conv, case, dtype):
     _run_case(conv, case, dtype)
 
 
-@pytest.mark.parametrize("case,dtype", **_params(gc.EDGES[:1]))
+@pytest.mark.parametrize("case,dtype", **ch.params(gc.EDGES[:1]))
 def test_repeated_edges_and_self_loops(conv, case, dtype):
     _run_case(conv, case, dtype)
 

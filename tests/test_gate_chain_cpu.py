@@ -7,6 +7,7 @@ import math
 
 import torch
 
+import chain_harness as ch
 import gate_chain as gc
 
 F64 = torch.float64
@@ -202,18 +203,4 @@ def test_case_tables_have_their_edges():
 def test_self_error_table(capsys):
     """The numbers the bars of the GPU tests are 4 x of: recomputed from the chain alone, equal to the committed JSON, and every one
     below 8e-2, so that no bar reaches 1/3: a gradient of zeros (error 1) fails every case."""
-    recorded = gc.load_self_error()
-    table = gc.self_error_table()
-    with capsys.disabled():
-        worst = {}
-        for k, v in table.items():
-            t, _, d = k.split("/")[:3]
-            worst[(t, d)] = max(worst.get((t, d), (0.0, "")), (v, k))
-        print("\nself error of tests/gate_chain.py (library-order float32 chain against the float64 chain)")
-        for (t, d), (v, k) in sorted(worst.items()):
-            print(f"  worst of {t:6s} {d:4s} {v:.3e}  ({k})")
-    assert set(recorded) == set(table)
-    for k, v in table.items():
-        assert v == v and 0 <= v, (k, v)
-        assert v < 8e-2, (k, v)
-        assert v == recorded[k], (k, v, recorded[k])
+    ch.check_self_error_table(gc, 8e-2, capsys)

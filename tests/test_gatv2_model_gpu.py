@@ -6,6 +6,7 @@ dropout 0.3, the masks being those of the fixture handed to the model through it
 import pytest
 import torch
 
+import chain_harness as ch
 import norm_chain as nc
 
 pytestmark = pytest.mark.gpu
@@ -16,11 +17,7 @@ _REFERENCE = {}
 
 @pytest.fixture(scope="module")
 def conv():
-    import gnnops
-    from gnnops import conv as c
-
-    gnnops.load_library()
-    return c
+    return ch.load_conv()
 
 
 def _reference(dtype, train):
@@ -38,20 +35,10 @@ def _model(conv, dtype):
     return model.to(dtype).cuda(), x.to(dtype).cuda(), ei.cuda(), batch.cuda(), [m.to(dtype).cuda() for m in masks]
 
 
-def _bar(dtype, mode, tensor):
-    if dtype == nc.BF16:
-        key = nc.model_key(mode, dtype, tensor)
-        return 4 * SELF_ERROR[key], f"4 x self error, {key}"
-    return nc.PROJECT_BAR[dtype], "the project's bar"
-
-
 def _judge(dtype, mode, tensor, got, want):
-    got = got.detach().double().cpu()
-    assert got.shape == want.shape and bool(torch.isfinite(got).all()), tensor
-    err = nc.rel_err(got, want)
-    bar, why = _bar(dtype, mode, tensor)
-    print(f"{mode} {nc.DNAME[dtype]} {tensor}: {err:.3e} (bar {bar:.3e}: {why})")
-    assert err <= bar, f"{mode} {nc.DNAME[dtype]} {tensor}: error {err:.3e} of scale exceeds {bar:.3e} ({why})"
+    """bf16: 4 x the recorded self error of the model chain; fp32 / fp16: the project's bar."""
+    ch.judge(f"{mode} {nc.DNAME[dtype]}", tensor, got, want, nc.PROJECT_BAR.get(dtype), self_bar=dtype == nc.BF16,
+             key=nc.model_key(mode, dtype, tensor), recorded=SELF_ERROR)
 
 
 @pytest.mark.parametrize("dtype", nc.DTYPES, ids=[nc.DNAME[d] for d in nc.DTYPES])

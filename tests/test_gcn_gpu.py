@@ -4,6 +4,7 @@ gradients of sum(out * R). Bars: conv_chain.PROJECT_BAR for fp32 / fp16; 4 x the
 import pytest
 import torch
 
+import chain_harness as ch
 import unet_chain as uc
 from unet_chain import BF16, DNAME, DTYPES, F32, PROJECT_BAR
 
@@ -13,10 +14,6 @@ pytestmark = pytest.mark.gpu
 @pytest.fixture(scope="module")
 def golden():
     return uc.load_self_error()
-
-
-def _bar(golden, key, dtype, self_bar):
-    return 4 * golden[key] if self_bar else PROJECT_BAR[dtype]
 
 
 def _place(t, layout, dtype):
@@ -45,12 +42,8 @@ def _run_case(case, dtype, golden):
     got = {"out": out.detach(), "h": h.grad, "bias": bias.grad if case.bias else None}
     want_g = dict(want_g, out=want)
     for k, v in got.items():
-        if v is None:
-            continue
-        err = uc.rel_err(v.double().cpu(), want_g[k])
-        bar = _bar(golden, case.key(dtype, k), dtype, case.self_bar(dtype))
-        print(case.id(dtype), k, err, bar)
-        assert err <= bar, (case.id(dtype), k, err, bar)
+        if v is not None:           # None: a case without a bias
+            ch.judge_case(case, dtype, k, v, want_g[k], golden)
     return out.detach()
 
 
@@ -111,10 +104,8 @@ def test_gcn_conv_layer(dtype, improved, golden):
     got = {"out": out.detach(), "x": x.grad, "lin.weight": layer.lin.weight.grad, "bias": layer.bias.grad}
     want_g = dict(want_g, out=want)
     for k, v in got.items():
-        err = uc.rel_err(v.double().cpu(), want_g[k])
-        bar = 4 * golden[f"conv/improved{int(improved)}/bf16/{k}"] if dtype == BF16 else PROJECT_BAR[dtype]
-        print(DNAME[dtype], improved, k, err, bar)
-        assert err <= bar, (k, err, bar)
+        ch.judge(f"improved{int(improved)}-{DNAME[dtype]}", k, v, want_g[k], PROJECT_BAR.get(dtype), self_bar=dtype == BF16,
+                 key=f"conv/improved{int(improved)}/bf16/{k}", recorded=golden)
     with torch.no_grad():
         assert torch.equal(layer.eval()(x.detach(), ei.cuda(), w.cuda()), out.detach())
 
@@ -136,10 +127,7 @@ def test_topk_pooling(C, dtype, golden):
     got = {"out": out.detach(), "x": xg.grad, "weight": layer.weight.grad}
     want_g = dict(want_g, out=want)
     for k, v in got.items():
-        err = uc.rel_err(v.double().cpu(), want_g[k])
-        bar = 4 * golden[f"pool/C{C}/bf16/{k}"] if dtype == BF16 else PROJECT_BAR[dtype]
-        print(C, DNAME[dtype], k, err, bar)
-        assert err <= bar, (k, err, bar)
+        ch.judge(f"C{C}-{DNAME[dtype]}", k, v, want_g[k], PROJECT_BAR.get(dtype), self_bar=dtype == BF16, key=f"pool/C{C}/bf16/{k}", recorded=golden)
 
 
 def test_refusals():

@@ -5,6 +5,7 @@ parameter's gradient within conv_chain.PROJECT_BAR. unet_chain.model_case builds
 import pytest
 import torch
 
+import chain_harness as ch
 import unet_chain as uc
 from unet_chain import F32, PROJECT_BAR
 
@@ -43,9 +44,7 @@ def test_graph_unet(graph, depth, sum_res, reference):
     want_g = dict(want_g, out=want)
     assert set(got) == set(want_g)
     for k, v in got.items():
-        err = uc.rel_err(v.double().cpu(), want_g[k])
-        print(graph, depth, sum_res, k, err)
-        assert err <= PROJECT_BAR[F32], (k, err)
+        ch.judge(f"{graph}-depth{depth}-sum_res{int(sum_res)}", k, v, want_g[k], PROJECT_BAR[F32])
     # a state_dict round trip between two instances, and eval / no_grad against training: bit for bit
     from gnnops.conv import GraphUNet
 

@@ -11,34 +11,18 @@ Bars: fp32 3e-5 and fp16 1e-2 are the project's (conv_chain.PROJECT_BAR) for the
 import pytest
 import torch
 
+import chain_harness as ch
 import norm_chain as nc
 
 pytestmark = pytest.mark.gpu
 
 SELF_ERROR = nc.load_self_error()
-_REFERENCE = {}
+_reference = ch.Reference(lambda case, dtype, ones=False: nc.case_grads(case, dtype, ones=ones))
 
 
 @pytest.fixture(scope="module")
 def conv():
-    import gnnops
-    from gnnops import conv as c
-
-    gnnops.load_library()
-    return c
-
-
-def _params(table):
-    pairs = [(c, d) for c in table for d in c.dtypes]
-    return {"argvalues": pairs, "ids": [c.id(d) for c, d in pairs]}
-
-
-def _reference(case, dtype, ones=False):
-    """The float64 chain of a case, computed once and shared."""
-    key = (case.table, case.name, dtype, ones)
-    if key not in _REFERENCE:
-        _REFERENCE[key] = nc.case_grads(case, dtype, ones=ones)
-    return _REFERENCE[key]
+    return ch.load_conv()
 
 
 def _leaves(case, dtype):
@@ -63,42 +47,27 @@ def _device_run(conv, case, dtype):
     return out, leaf
 
 
-def _judge(case, dtype, name, got, want):
-    assert got is not None, f"{name}: no gradient"
-    got = got.detach().double().cpu()
-    assert got.shape == want.shape, (name, got.shape, want.shape)
-    assert bool(torch.isfinite(got).all()), f"{case.id(dtype)} {name}: not finite"
-    err = nc.rel_err(got, want)
-    if case.self_bar(dtype):
-        key = case.key(dtype, name)
-        bar, why = 4 * SELF_ERROR[key], f"4 x self error, {key}"
-    else:
-        bar, why = nc.PROJECT_BAR[dtype], "the project's bar"
-    print(f"{case.id(dtype)} {name}: {err:.3e} (bar {bar:.3e}: {why})")
-    assert err <= bar, f"{case.id(dtype)} {name}: error {err:.3e} of scale exceeds {bar:.3e} ({why})"
-
-
 def _run_case(conv, case, dtype):
     want_out, want = _reference(case, dtype)
     out, leaf = _device_run(conv, case, dtype)
-    _judge(case, dtype, "out", out, want_out)
+    ch.judge_case(case, dtype, "out", out, want_out, SELF_ERROR)
     for n, w in want.items():
-        _judge(case, dtype, n, leaf[n].grad, w)
+        ch.judge_case(case, dtype, n, leaf[n].grad, w, SELF_ERROR)
     assert leaf["k"] is None or leaf["k"].grad is None
     return out, leaf
 
 
-@pytest.mark.parametrize("case,dtype", **_params(nc.SHAPES))
+@pytest.mark.parametrize("case,dtype", **ch.params(nc.SHAPES))
 def test_shapes(conv, case, dtype):
     _run_case(conv, case, dtype)
 
 
-@pytest.mark.parametrize("case,dtype", **_params(nc.ROWS))
+@pytest.mark.parametrize("case,dtype", **ch.params(nc.ROWS))
 def test_rows(conv, case, dtype):
     _run_case(conv, case, dtype)
 
 
-@pytest.mark.parametrize("case,dtype", **_params(nc.VALUES))
+@pytest.mark.parametrize("case,dtype", **ch.params(nc.VALUES))
 def test_values(conv, case, dtype):
     out, leaf = _run_case(conv, case, dtype)
     rows = list(nc.SPECIAL_ROWS)
@@ -141,12 +110,12 @@ GRAD_CASE = nc.SHAPES[[c.name for c in nc.SHAPES].index("H3-C136")]
 
 def test_expanded_gradient(conv):
     """out.sum(): autograd hands the backward one expanded scalar (strides 0, 0)."""
-    want_out, want = _reference(GRAD_CASE, torch.float32, ones=True)
+    want_out, want = _reference(GRAD_CASE, torch.float32, True)
     leaf, _ = _leaves(GRAD_CASE, torch.float32)
     out = _call(conv, GRAD_CASE, leaf)
     out.sum().backward()
     for n, w in want.items():
-        _judge(GRAD_CASE, torch.float32, n, leaf[n].grad, w)
+        ch.judge_case(GRAD_CASE, torch.float32, n, leaf[n].grad, w, SELF_ERROR)
 
 
 def test_transposed_gradient(conv):
@@ -156,7 +125,7 @@ def test_transposed_gradient(conv):
     out = _call(conv, GRAD_CASE, leaf)
     out.t().backward(R.t().contiguous())
     for n, w in want.items():
-        _judge(GRAD_CASE, torch.float32, n, leaf[n].grad, w)
+        ch.judge_case(GRAD_CASE, torch.float32, n, leaf[n].grad, w, SELF_ERROR)
 
 
 @pytest.mark.parametrize("case", [GRAD_CASE, nc.ROWS[-1], nc.SHAPES[-2]], ids=lambda c: c.name)

@@ -5,6 +5,7 @@ import math
 
 import torch
 
+import chain_harness as ch
 import norm_chain as nc
 
 F64 = torch.float64
@@ -149,17 +150,4 @@ def test_model_restatement():
 
 def test_self_error_table(capsys):
     """The numbers the bars of the GPU tests are 4 x of: recomputed from the chain alone, equal to the committed JSON."""
-    recorded = nc.load_self_error()
-    table = nc.self_error_table()
-    with capsys.disabled():
-        worst = {}
-        for k, v in table.items():
-            t, _, d = k.split("/")[:3]
-            worst[(t, d)] = max(worst.get((t, d), (0.0, "")), (v, k))
-        print("\nself error of tests/norm_chain.py (library-order float32 chain against the float64 chain)")
-        for (t, d), (v, k) in sorted(worst.items()):
-            print(f"  worst of {t:6s} {d:4s} {v:.3e}  ({k})")
-    assert set(recorded) == set(table)
-    for k, v in table.items():
-        assert v == v and 0 <= v < 1e-1, (k, v)
-        assert v == recorded[k], (k, v, recorded[k])
+    ch.check_self_error_table(nc, 1e-1, capsys)

@@ -9,6 +9,7 @@ import functools
 import pytest
 import torch
 
+import chain_harness as ch
 import spmm_reduce_chain as sc
 
 pytestmark = pytest.mark.gpu
@@ -50,14 +51,10 @@ def run(case, dtype, reduce, backward=True):
     return out.detach(), arg, grads
 
 
-def check(got, want, bar, what):
-    assert got is not None, f"{what}: no gradient"
-    got = got.detach().double().cpu()
-    assert got.shape == want.shape, (what, got.shape, want.shape)
-    err = sc.rel_err(got, want)
-    print(f"{what}: {err:.3e} (bar {bar:.3e})")
-    assert bool(torch.isfinite(got).all()), f"{what}: not finite"
-    assert err <= bar, f"{what}: error {err:.3e} of scale exceeds {bar:.3e}"
+def check(case, dtype, reduce, name, got, want):
+    """PROJECT_BAR for fp32 / fp16; bf16: 4 x the chain's recorded self error (attention_chain.py's rule)."""
+    ch.judge(f"{case.name}-{sc.DNAME[dtype]}-{reduce}", name, got, want, sc.PROJECT_BAR.get(dtype), self_bar=dtype == sc.BF16,
+             key=case.key(dtype, reduce, name), recorded=table())
 
 
 def exact_forward(case, dtype, reduce, out, arg):
@@ -80,11 +77,10 @@ def test_forward_and_gradients_against_the_float64_chain(case, dtype, reduce):
         empty = torch.tensor(case.lengths) == 0
         assert bool(empty.any()) and bool((arg.cpu()[empty] == sum(case.lengths)).all()) and bool((out.cpu()[empty] == 0).all())
     want, _, want_grads = chain(case, dtype, reduce, False)
-    bar = lambda t: sc.bar(case, dtype, reduce, t, table())   # noqa: E731
-    check(out, want, bar("out"), "out")
+    check(case, dtype, reduce, "out", out, want)
     assert set(grads) == set(want_grads)
     for k in want_grads:
-        check(grads[k], want_grads[k], bar(k), f"d {k}")
+        check(case, dtype, reduce, k, grads[k], want_grads[k])
 
 
 # ---- with perm: the kernel's operand, and COO in random order through SparseTensor ------------------------------------------------------
@@ -156,9 +152,9 @@ def test_one_row_longer_than_the_hub_threshold(dtype, reduce):
     if reduce == "max":
         exact_forward(sc.LONG, dtype, reduce, out, arg)
     want, _, want_grads = chain(sc.LONG, dtype, reduce, False)
-    check(out, want, sc.bar(sc.LONG, dtype, reduce, "out", table()), "out")
+    check(sc.LONG, dtype, reduce, "out", out, want)
     for k in want_grads:
-        check(grads[k], want_grads[k], sc.bar(sc.LONG, dtype, reduce, k, table()), f"d {k}")
+        check(sc.LONG, dtype, reduce, k, grads[k], want_grads[k])
 
 
 @pytest.mark.parametrize("reduce", sc.REDUCES)
@@ -274,9 +270,9 @@ def test_backward_through_matmul_reaches_x_and_the_edge_weights(reduce):
     wl, xl = w.detach().cpu().double().requires_grad_(True), x.detach().cpu().double().requires_grad_(True)
     ref, _ = sc.spmm_reduce(sc.rowptr_of(ei[1][order], n_dst), ei[0][order], wl[order], xl, reduce)
     (ref * R.cpu().double()).sum().backward()
-    check(out, ref.detach(), sc.PROJECT_BAR[sc.F32], "out")
-    check(x.grad, xl.grad, sc.PROJECT_BAR[sc.F32], "d x")
-    check(w.grad, wl.grad, sc.PROJECT_BAR[sc.F32], "d value")
+    ch.judge(reduce, "out", out, ref.detach(), sc.PROJECT_BAR[sc.F32])
+    ch.judge(reduce, "d x", x.grad, xl.grad, sc.PROJECT_BAR[sc.F32])
+    ch.judge(reduce, "d value", w.grad, wl.grad, sc.PROJECT_BAR[sc.F32])
 
 
 def test_sparse_times_sparse_and_cpu_tensors_raise():

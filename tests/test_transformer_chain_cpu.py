@@ -5,6 +5,7 @@ import math
 
 import torch
 
+import chain_harness as ch
 import transformer_chain as tc
 
 F64 = torch.float64
@@ -157,17 +158,4 @@ def test_case_tables_have_their_edges():
 
 def test_self_error_table(capsys):
     """The numbers the bars of the GPU tests are 4 x of: recomputed from the chain alone, equal to the committed JSON."""
-    recorded = tc.load_self_error()
-    table = tc.self_error_table()
-    with capsys.disabled():
-        worst = {}
-        for key, e in table.items():
-            t, _, d = key.split("/")[:3]
-            worst[(t, d)] = max(worst.get((t, d), (0.0, "")), (e, key))
-        print("\nself error of tests/transformer_chain.py (library-order float32 chain against the float64 chain)")
-        for (t, d), (e, key) in sorted(worst.items()):
-            print(f"  worst of {t:6s} {d:4s} {e:.3e}  ({key})")
-    assert set(recorded) == set(table)
-    for key, e in table.items():
-        assert e == e and 0 <= e < 5e-2, (key, e)
-        assert e == recorded[key], (key, e, recorded[key])
+    ch.check_self_error_table(tc, 5e-2, capsys)

@@ -19,34 +19,18 @@ tensor (tests/golden/transformer_self_error.json, measured on the CPU from the c
 import pytest
 import torch
 
+import chain_harness as ch
 import transformer_chain as tc
 
 pytestmark = pytest.mark.gpu
 
 SELF_ERROR = tc.load_self_error()
-_REFERENCE = {}
+_reference = ch.Reference(tc.case_grads)
 
 
 @pytest.fixture(scope="module")
 def conv():
-    import gnnops
-    from gnnops import conv as c
-
-    gnnops.load_library()
-    return c
-
-
-def _params(table):
-    pairs = [(c, d) for c in table for d in c.dtypes]
-    return {"argvalues": pairs, "ids": [c.id(d) for c, d in pairs]}
-
-
-def _reference(case, dtype):
-    """The float64 chain of a case, computed once and shared."""
-    key = (case.table, case.name, dtype)
-    if key not in _REFERENCE:
-        _REFERENCE[key] = tc.case_grads(case, dtype)
-    return _REFERENCE[key]
+    return ch.load_conv()
 
 
 def _placed(leaf, case):
@@ -75,58 +59,43 @@ def _device_run(conv, case, dtype, edge_index=None, edge_scale=None):
     return out, leaf
 
 
-def _judge(case, dtype, name, got, want, self_error=None):
-    assert got is not None, f"{name}: no gradient"
-    got = got.detach().double().cpu()
-    assert got.shape == want.shape, (name, got.shape, want.shape)
-    assert bool(torch.isfinite(got).all()), f"{case.id(dtype)} {name}: not finite"
-    err = tc.rel_err(got, want)
-    if case.self_bar(dtype):
-        key = case.key(dtype, name)
-        bar, why = 4 * (SELF_ERROR[key] if self_error is None else self_error[name]), f"4 x self error, {key}"
-    else:
-        bar, why = tc.PROJECT_BAR[dtype], "the project's bar"
-    print(f"{case.id(dtype)} {name}: {err:.3e} (bar {bar:.3e}: {why})")
-    assert err <= bar, f"{case.id(dtype)} {name}: error {err:.3e} of scale exceeds {bar:.3e} ({why})"
-
-
 def _run_case(conv, case, dtype):
     want_out, want = _reference(case, dtype)
     out, leaf = _device_run(conv, case, dtype)
-    _judge(case, dtype, "out", out, want_out)
+    ch.judge_case(case, dtype, "out", out, want_out, SELF_ERROR)
     assert set(want) == set(leaf)
     for name, w in want.items():
-        _judge(case, dtype, name, leaf[name].grad, w)
+        ch.judge_case(case, dtype, name, leaf[name].grad, w, SELF_ERROR)
     return out
 
 
-@pytest.mark.parametrize("case,dtype", **_params(tc.SHAPES))
+@pytest.mark.parametrize("case,dtype", **ch.params(tc.SHAPES))
 def test_shapes(conv, case, dtype):
     _run_case(conv, case, dtype)
 
 
-@pytest.mark.parametrize("case,dtype", **_params(tc.SEAMS))
+@pytest.mark.parametrize("case,dtype", **ch.params(tc.SEAMS))
 def test_degree_seams(conv, case, dtype):
     out = _run_case(conv, case, dtype)
     assert tc.SEAM_DEGREES[0] == 0 and float(out[0].detach().abs().max()) == 0.0   # the destination without an edge: exactly zero
 
 
-@pytest.mark.parametrize("case,dtype", **_params(tc.RANGE))
+@pytest.mark.parametrize("case,dtype", **ch.params(tc.RANGE))
 def test_online_rescale(conv, case, dtype):
     _run_case(conv, case, dtype)
 
 
-@pytest.mark.parametrize("case,dtype", **_params(tc.HEAVY))
+@pytest.mark.parametrize("case,dtype", **ch.params(tc.HEAVY))
 def test_heavy_destinations(conv, case, dtype):
     _run_case(conv, case, dtype)
 
 
-@pytest.mark.parametrize("case,dtype", **_params(tc.PLAN))
+@pytest.mark.parametrize("case,dtype", **ch.params(tc.PLAN))
 def test_both_sides_of_the_one_launch_plan(conv, case, dtype):
     _run_case(conv, case, dtype)
 
 
-@pytest.mark.parametrize("case,dtype", **_params(tc.EDGES[:2]))
+@pytest.mark.parametrize("case,dtype", **ch.params(tc.EDGES[:2]))
 def test_repeated_edges_and_self_loops(conv, case, dtype):
     _run_case(conv, case, dtype)
 
@@ -189,7 +158,7 @@ def test_plan_routes(conv, case, cache):
 SCALE_CASES = [tc.SHAPES[7], tc.SHAPES[-3]]        # H3-C8 without u, H3-C8 with u
 
 
-@pytest.mark.parametrize("case,dtype", **_params(SCALE_CASES))
+@pytest.mark.parametrize("case,dtype", **ch.params(SCALE_CASES))
 def test_explicit_edge_scale(conv, case, dtype):
     """edge_scale of zeros and 1 / (1 - p) entries: the chain with that mask. The bar of bf16 is 4 x the self error of the chain
     WITH the mask, computed here on the CPU from the chain alone."""
@@ -198,17 +167,18 @@ def test_explicit_edge_scale(conv, case, dtype):
     assert set(mask.unique().tolist()) == {0.0, 2.0}
     ops, ei, R = tc.inputs(case, dtype)
     want_out, want = tc.dot_grads(ops, ei, case.n_dst, case.H, tc.scale_of(case), R, ks=mask)
-    self_error = None
+    self_error = {}           # the table in place of the recorded one, under the same keys
     if case.self_bar(dtype):
         out_r, gr_r = tc.dot_grads(ops, ei, case.n_dst, case.H, tc.scale_of(case), R, rnd=dtype, ks=mask)
-        self_error = {"out": tc.rel_err(out_r, want_out), **{name: tc.rel_err(gr_r[name], want[name]) for name in want}}
+        self_error = {case.key(dtype, "out"): tc.rel_err(out_r, want_out),
+                      **{case.key(dtype, name): tc.rel_err(gr_r[name], want[name]) for name in want}}
     out, leaf = _device_run(conv, case, dtype, edge_scale=mask)
-    _judge(case, dtype, "out", out, want_out, self_error)
+    ch.judge_case(case, dtype, "out", out, want_out, self_error)
     for name, w in want.items():
-        _judge(case, dtype, name, leaf[name].grad, w, self_error)
+        ch.judge_case(case, dtype, name, leaf[name].grad, w, self_error)
 
 
-@pytest.mark.parametrize("case,dtype", **_params(SCALE_CASES))
+@pytest.mark.parametrize("case,dtype", **ch.params(SCALE_CASES))
 def test_edge_scale_of_ones_gives_the_same_bits(conv, case, dtype):
     _, ei, _ = tc.inputs(case, dtype)
     plain_out, plain = _device_run(conv, case, dtype)

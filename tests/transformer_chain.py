@@ -26,7 +26,7 @@ gate_chain.SEAM_DEGREES, which has every step of this pass's unrolls (4 forward;
 restatement follows torch_geometric's TransformerConv (lin_key / lin_query / lin_value with biases, lin_edge without, lin_skip,
 lin_beta on [out, x_r, out - x_r]; no self loops added; mean over heads when concat=False). PyG is not available to compare
 against: parity unpinned."""
-import json
+import functools
 import math
 import os
 from dataclasses import dataclass
@@ -34,8 +34,10 @@ from dataclasses import dataclass
 import torch
 
 import attention_chain as ac
+import chain_harness as ch
 from attention_chain import Case, SPECIAL, _amax, _dot, _exp, _log  # noqa: F401
-from conv_chain import BF16, DNAME, DTYPES, F16, F32, PROJECT_BAR, _lin, _q, _rand, _straight_through, place, rel_err  # noqa: F401
+from chain_harness import BF16, DNAME, DTYPES, F16, F32, PROJECT_BAR, rel_err  # noqa: F401
+from conv_chain import _lin, _q, _rand, _straight_through, place  # noqa: F401
 from gate_chain import SEAM_DEGREES
 
 GOLDEN_FILE = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "transformer_self_error.json")
@@ -183,17 +185,11 @@ def case_grads(case, dtype, rnd=None):
     return dot_grads(ops, ei, case.n_dst, case.H, scale_of(case), R, rnd=rnd)
 
 
-def self_error(case, dtype):
-    out, grads = case_grads(case, dtype)
-    out_r, grads_r = case_grads(case, dtype, rnd=dtype)
-    err = {"out": rel_err(out_r, out)}
-    for name in grads:
-        err[name] = rel_err(grads_r[name], grads[name])
-    return err
+self_error = functools.partial(ch.self_error, case_grads)
 
 
 def self_error_cases():
-    return [(c, d) for t in TABLES.values() for c in t for d in c.dtypes if c.self_bar(d)]
+    return ch.self_bar_cases(TABLES)
 
 
 def project_group_check():
@@ -292,25 +288,14 @@ PYG_STATE = {"lin_key.weight": (128, 16), "lin_key.bias": (128,), "lin_query.wei
 
 
 # ---- the table ----------------------------------------------------------------------------------------------------------------
-def self_error_table(progress=None):
-    table = {}
-    for c, d in self_error_cases():
-        for name, e in self_error(c, d).items():
-            table[c.key(d, name)] = e
-        if progress:
-            progress(c.id(d))
-    return table
+def self_error_table():
+    return ch.build_table(self_error_cases(), self_error)
 
 
 def write_self_error_table(path=GOLDEN_FILE):
     """Regenerates tests/golden/transformer_self_error.json (python -c "import transformer_chain as tc; tc.write_self_error_table()")."""
-    table = self_error_table()
-    with open(path, "w") as f:
-        json.dump(table, f, indent=0, sort_keys=True)
-        f.write("\n")
-    return table
+    return ch.write_table(self_error_table(), path)
 
 
 def load_self_error():
-    with open(GOLDEN_FILE) as f:
-        return json.load(f)
+    return ch.load_table(GOLDEN_FILE)

@@ -13,7 +13,7 @@ fp32 / fp16; 4 x the recorded self error for bf16 and for the heavy table, the p
 Selections must be reproduced exactly, so every layer case keeps the scores inside a graph apart (``min_gap``): at least 1e-3 in
 fp32 cases and 0.05 in 16-bit cases — test_unet_chain_cpu.py checks it. Random inputs cannot do that for 130 nodes under a tanh,
 so the inputs are built: `pool_inputs` places the scores on a shuffled grid, `model_case` builds the model cases (see there)."""
-import json
+import functools
 import math
 import os
 from dataclasses import dataclass
@@ -21,7 +21,9 @@ from dataclasses import dataclass
 import numpy as np
 import torch
 
-from conv_chain import BF16, DNAME, DTYPES, F16, F32, PROJECT_BAR, _q, rel_err  # noqa: F401
+import chain_harness as ch
+from chain_harness import BF16, DNAME, DTYPES, F16, F32, PROJECT_BAR, rel_err  # noqa: F401
+from conv_chain import _q
 
 GOLDEN_FILE = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "unet_self_error.json")
 SEAM_DEGREES = (0, 1, 2, 3, 4, 5, 7, 8, 9, 63, 64, 65, 129)
@@ -339,7 +341,7 @@ def degree_graph(degrees, n_extra, g):
 
 
 @dataclass(frozen=True)
-class GcnCase:
+class GcnCase(ch.CaseBars):
     table: str
     name: str
     K: int = 8
@@ -353,9 +355,6 @@ class GcnCase:
 
     def id(self, dtype):
         return f"{self.table}-{self.name}-{DNAME[dtype]}"
-
-    def key(self, dtype, tensor):
-        return f"{self.table}/{self.name}/{DNAME[dtype]}/{tensor}"
 
     def self_bar(self, dtype):
         return dtype == BF16 or self.table == "heavy"
@@ -465,17 +464,7 @@ def self_error_table():
 
 
 def _self_error_table():
-    table = {}
-    for t in TABLES.values():
-        for c in t:
-            for d in c.dtypes:
-                if not c.self_bar(d):
-                    continue
-                out, grads = gcn_case_grads(c, d)
-                out_r, grads_r = gcn_case_grads(c, d, rnd=d)
-                table[c.key(d, "out")] = rel_err(out_r, out)
-                for k in grads:
-                    table[c.key(d, k)] = rel_err(grads_r[k], grads[k])
+    table = ch.build_table(ch.self_bar_cases(TABLES), functools.partial(ch.self_error, gcn_case_grads))
     for C, d in POOL_CASES:
         if d != BF16:
             continue
@@ -508,13 +497,8 @@ def conv_inputs(dtype, improved, seed=31):
 
 def write_self_error_table(path=GOLDEN_FILE):
     """Regenerates tests/golden/unet_self_error.json (python -c "import unet_chain as uc; uc.write_self_error_table()")."""
-    table = self_error_table()
-    with open(path, "w") as f:
-        json.dump(table, f, indent=0, sort_keys=True)
-        f.write("\n")
-    return table
+    return ch.write_table(self_error_table(), path)
 
 
 def load_self_error():
-    with open(GOLDEN_FILE) as f:
-        return json.load(f)
+    return ch.load_table(GOLDEN_FILE)
