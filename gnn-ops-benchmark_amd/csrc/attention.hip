@@ -52,10 +52,9 @@
 // edge_dim; read exactly as edge_scale is): backward writes gc[e,h] = d pre, one store per edge and head. Instantiated without u only.
 //
 // THIRD FAMILY, scaled dot product (gnnops.conv.edge_attention_dot: TransformerConv): see the comment above DotArgs.
-#include <initializer_list>
-#include <utility>
 #include "common.h"
 #include "lane_group.h"
+#include "dispatch.h"
 
 namespace {
 
@@ -1136,17 +1135,6 @@ inline int rows_of_partials(int64_t N, int H, int C) {
     return (int)(rows < 1 ? 1 : rows);
 }
 
-using Operands = std::initializer_list<std::pair<const void*, int64_t>>;   // (pointer, row pitch) of what a kernel reads or writes in pieces
-
-inline int max_vec_of(int es, Operands operands) {
-    int max_vec = 16 / es;
-    for (const auto& op : operands) {
-        if (!op.first) continue;
-        while (max_vec > 1 && ((uintptr_t)op.first % (max_vec * es) != 0 || (op.second * es) % (max_vec * es) != 0)) max_vec >>= 1;
-    }
-    return max_vec;
-}
-
 // the forward or the backward kernel of one instance, whatever the family
 template <bool BW, typename Args>
 void run(void (*fwd)(Args), void (*bwd)(Args), const Args& a, int grid, hipStream_t stream) {
@@ -1193,22 +1181,16 @@ void launch_pieces(const typename F::Args& a, int nch, int grid, hipStream_t str
 template <typename F, typename T, bool BW>
 void launch_typed(const typename F::Args& a, const Geometry& geo, int grid, hipStream_t stream) {
     if (geo.nch == 128) return F::template launch<T, BW, 1, 128>(a, grid, stream);
-    if constexpr (Elem<T>::VEC == 8) {
-        if (geo.vec == 8) return launch_pieces<F, T, BW, 8>(a, geo.nch, grid, stream);
-    }
-    if (geo.vec == 4) return launch_pieces<F, T, BW, 4>(a, geo.nch, grid, stream);
-    if (geo.vec == 2) return launch_pieces<F, T, BW, 2>(a, geo.nch, grid, stream);
-    return launch_pieces<F, T, BW, 1>(a, geo.nch, grid, stream);
+    gnnops_with_piece_width<T>(geo.vec, [&](auto v) { launch_pieces<F, T, BW, decltype(v)::value>(a, geo.nch, grid, stream); });
 }
 
-// dtype was checked by check_sizes
+// what: the entry point's name, for the refusal of a dtype code check_sizes has already refused
 template <typename F, bool BW>
-void launch(const typename F::Args& a, const Geometry& geo, int grid, int dtype, hipStream_t stream) {
-    switch (dtype) {
-        case GNNOPS_F32: launch_typed<F, float, BW>(a, geo, grid, stream); break;
-        case GNNOPS_F16: launch_typed<F, __half, BW>(a, geo, grid, stream); break;
-        default: launch_typed<F, __hip_bfloat16, BW>(a, geo, grid, stream); break;
-    }
+int launch(const char* what, const typename F::Args& a, const Geometry& geo, int grid, int dtype, hipStream_t stream) {
+    return gnnops_with_dtype(dtype, what, [&](auto t) {
+        launch_typed<F, typename decltype(t)::type, BW>(a, geo, grid, stream);
+        return (int)GNNOPS_OK;
+    });
 }
 
 template <typename T>
@@ -1216,12 +1198,11 @@ void launch_datt_typed(const float* partial, int rows, int HC, void* grad_att, h
     hipLaunchKernelGGL(attention_datt_kernel<T>, dim3((unsigned)gnnops_cdiv(HC, 256)), dim3(256), 0, stream, partial, rows, HC, (T*)grad_att);
 }
 
-void launch_datt(const float* partial, int rows, int HC, void* grad_att, int dtype, hipStream_t stream) {
-    switch (dtype) {
-        case GNNOPS_F32: launch_datt_typed<float>(partial, rows, HC, grad_att, stream); break;
-        case GNNOPS_F16: launch_datt_typed<__half>(partial, rows, HC, grad_att, stream); break;
-        default: launch_datt_typed<__hip_bfloat16>(partial, rows, HC, grad_att, stream); break;
-    }
+int launch_datt(const char* what, const float* partial, int rows, int HC, void* grad_att, int dtype, hipStream_t stream) {
+    return gnnops_with_dtype(dtype, what, [&](auto t) {
+        launch_datt_typed<typename decltype(t)::type>(partial, rows, HC, grad_att, stream);
+        return (int)GNNOPS_OK;
+    });
 }
 
 int check_sizes(const char* what, int64_t N, int64_t E, int64_t H, int64_t C, int64_t ldq, int64_t ldp, int dtype, int* es) {
@@ -1231,11 +1212,8 @@ int check_sizes(const char* what, int64_t N, int64_t E, int64_t H, int64_t C, in
     GNNOPS_REQUIRE(N < ((int64_t)1 << 31) && E < ((int64_t)1 << 31) && ldq < ((int64_t)1 << 31), GNNOPS_EUNSUPPORTED,
                    "%s: N, E and the row pitch must be < 2^31", what);
     GNNOPS_REQUIRE(ldq >= H * C && ldp >= H * C, GNNOPS_EINVAL, "%s: a row pitch is shorter than the row", what);
-    switch (dtype) {
-        case GNNOPS_F32: *es = 4; break;
-        case GNNOPS_F16: case GNNOPS_BF16: *es = 2; break;
-        default: gnnops_set_error("%s: unknown dtype %d", what, dtype); return GNNOPS_EINVAL;
-    }
+    *es = gnnops_elem_bytes(dtype);
+    GNNOPS_REQUIRE(*es, GNNOPS_EINVAL, "%s: unknown dtype %d", what, dtype);
     return GNNOPS_OK;
 }
 
@@ -1260,7 +1238,7 @@ int forward_prologue(const char* what, int64_t N, int64_t E, int64_t H, int64_t 
     GNNOPS_REQUIRE(!u_and_c, GNNOPS_EUNSUPPORTED, "%s: a per-edge row u and a per-edge score term c together have no kernel instance", what);
     if (N == 0) return GNNOPS_OK;
     GNNOPS_REQUIRE(pointers, GNNOPS_EINVAL, "%s: null pointer", what);
-    l->geo = geometry((int)H, (int)C, max_vec_of(es, operands), es);
+    l->geo = geometry((int)H, (int)C, gnnops_widest_piece(es, operands), es);
     l->grid = gnnops_grid_cap(gnnops_cdiv(N * l->geo.hblocks, 4), 256 * 32);
     l->nwaves = l->grid * 4;
     return GNNOPS_OK;
@@ -1283,7 +1261,7 @@ int backward_prologue(const char* what, int64_t N, int64_t E, int64_t H, int64_t
     const size_t need = gnnops_edge_attention_backward_workspace_bytes(N, H, C);
     GNNOPS_REQUIRE(workspace && workspace_bytes >= need && (uintptr_t)workspace % 16 == 0, GNNOPS_EWORKSPACE, "%s: workspace %zu < %zu",
                    what, workspace_bytes, need);
-    l->geo = geometry((int)H, (int)C, max_vec_of(es, operands), es);
+    l->geo = geometry((int)H, (int)C, gnnops_widest_piece(es, operands), es);
     l->rows = rows_of_partials(N, (int)H, (int)C);
     l->nwaves = l->rows * l->geo.hblocks;
     l->grid = (int)gnnops_cdiv(l->nwaves, 4);
@@ -1310,7 +1288,7 @@ extern "C" int gnnops_edge_attention(const void* q, int64_t ldq, const void* p, 
     a.q = q; a.p = p; a.att = att; a.u = u; a.rowptr = rowptr; a.perm = perm; a.col = col; a.out = out; a.lse = lse;
     a.N = N; a.ldq = ldq; a.ldp = ldp; a.ldo = ldo; a.H = (int)H; a.C = (int)C; a.slope = negative_slope;
     set_geometry(a, l);
-    launch<AttFamily, false>(a, l.geo, l.grid, dtype, (hipStream_t)s);
+    if (const int rc = launch<AttFamily, false>("edge_attention", a, l.geo, l.grid, dtype, (hipStream_t)s)) return rc;
     return gnnops_check_launch("edge_attention");
 }
 
@@ -1332,8 +1310,8 @@ extern "C" int gnnops_edge_attention_backward(const void* q, int64_t ldq, const 
     a.dp = grad_p; a.gq = gq; a.gu = gu; a.lse = const_cast<float*>(lse); a.partial = (float*)workspace;
     a.N = N; a.ldq = ldq; a.ldp = ldp; a.ldo = ldo; a.ldg = ldg; a.H = (int)H; a.C = (int)C; a.slope = negative_slope;
     set_geometry(a, l);
-    launch<AttFamily, true>(a, l.geo, l.grid, dtype, (hipStream_t)s);
-    launch_datt(a.partial, l.rows, (int)(H * C), grad_att, dtype, (hipStream_t)s);
+    if (const int rc = launch<AttFamily, true>("edge_attention_backward", a, l.geo, l.grid, dtype, (hipStream_t)s)) return rc;
+    if (const int rc = launch_datt("edge_attention_backward", a.partial, l.rows, (int)(H * C), grad_att, dtype, (hipStream_t)s)) return rc;
     return gnnops_check_launch("edge_attention_backward");
 }
 
@@ -1353,7 +1331,7 @@ extern "C" int gnnops_edge_attention_v1(const void* q, int64_t ldq, const void* 
     a.N = N; a.ldq = ldq; a.ldd = ldd; a.ldo = ldo; a.H = (int)H; a.C = (int)C;
     a.slope = negative_slope; a.row_slope = has_row_slope ? row_slope : 1.f;
     set_geometry(a, l);
-    launch<GateFamily, false>(a, l.geo, l.grid, dtype, (hipStream_t)s);
+    if (const int rc = launch<GateFamily, false>("edge_attention_v1", a, l.geo, l.grid, dtype, (hipStream_t)s)) return rc;
     return gnnops_check_launch("edge_attention_v1");
 }
 
@@ -1378,8 +1356,8 @@ extern "C" int gnnops_edge_attention_v1_backward(const void* q, int64_t ldq, con
     a.N = N; a.ldq = ldq; a.ldd = ldd; a.ldo = ldo; a.ldg = ldg; a.H = (int)H; a.C = (int)C;
     a.slope = negative_slope; a.row_slope = has_row_slope ? row_slope : 1.f;
     set_geometry(a, l);
-    launch<GateFamily, true>(a, l.geo, l.grid, dtype, (hipStream_t)s);
-    launch_datt(a.partial, l.rows, (int)(H * C), grad_att, dtype, (hipStream_t)s);
+    if (const int rc = launch<GateFamily, true>("edge_attention_v1_backward", a, l.geo, l.grid, dtype, (hipStream_t)s)) return rc;
+    if (const int rc = launch_datt("edge_attention_v1_backward", a.partial, l.rows, (int)(H * C), grad_att, dtype, (hipStream_t)s)) return rc;
     return gnnops_check_launch("edge_attention_v1_backward");
 }
 
@@ -1411,7 +1389,7 @@ extern "C" int gnnops_edge_attention_dot(const void* qry, int64_t ldq, const voi
     a.qry = qry; a.k = k; a.v = v; a.u = u; a.ks = edge_scale; a.rowptr = rowptr; a.perm = perm; a.col = col; a.out = out; a.lse = lse;
     a.N = N; a.ldq = ldq; a.ldkv = ldkv; a.ldo = ldo; a.H = (int)H; a.C = (int)C; a.scale = scale;
     set_geometry(a, l);
-    launch<DotFamily, false>(a, l.geo, l.grid, dtype, (hipStream_t)s);
+    if (const int rc = launch<DotFamily, false>("edge_attention_dot", a, l.geo, l.grid, dtype, (hipStream_t)s)) return rc;
     return gnnops_check_launch("edge_attention_dot");
 }
 
@@ -1433,6 +1411,6 @@ extern "C" int gnnops_edge_attention_dot_backward(const void* qry, int64_t ldq, 
     a.dq = grad_qry; a.gkv = gkv; a.gu = gu; a.lse = const_cast<float*>(lse);
     a.N = N; a.ldq = ldq; a.ldkv = ldkv; a.ldo = ldo; a.ldg = ldg; a.H = (int)H; a.C = (int)C; a.scale = scale;
     set_geometry(a, l);
-    launch<DotFamily, true>(a, l.geo, l.grid, dtype, (hipStream_t)s);
+    if (const int rc = launch<DotFamily, true>("edge_attention_dot_backward", a, l.geo, l.grid, dtype, (hipStream_t)s)) return rc;
     return gnnops_check_launch("edge_attention_dot_backward");
 }

@@ -7,6 +7,7 @@
 //   gnnops_sddmm           out[k] = <a[ra[k], :], b[rb[k], :]> per nonzero: d(value) of torch_sparse.spmm
 //                          (benchmark_sparse_spmm.py:12-14 in training), fp32 accumulation, one rounding
 #include "common.h"
+#include "dispatch.h"
 
 namespace {
 
@@ -61,8 +62,7 @@ template <typename T>
 int launch_sddmm(const int64_t* ra, const int64_t* rb, const void* a, const void* b, void* out, int64_t nnz, int64_t D,
                  hipStream_t stream) {
     const int64_t pieces = gnnops_cdiv(D, Elem<T>::VEC);
-    int gshift = 0;
-    while ((1 << gshift) < pieces && gshift < 6) ++gshift;
+    const int gshift = gnnops_group_shift(pieces);
     const int grid = gnnops_grid_cap(gnnops_cdiv(nnz, 256 >> gshift), 256 * 32);
     hipLaunchKernelGGL((sddmm_kernel<T>), dim3(grid), dim3(256), 0, stream, ra, rb, (const T*)a, (const T*)b, (T*)out, nnz, D,
                        gshift);
@@ -85,13 +85,9 @@ extern "C" int gnnops_sddmm(const int64_t* rows_a, const int64_t* rows_b, const 
     GNNOPS_REQUIRE(nnz >= 0 && D >= 0, GNNOPS_EINVAL, "sddmm: negative size");
     if (nnz == 0) return GNNOPS_OK;
     GNNOPS_REQUIRE(rows_a && rows_b && out && (D == 0 || (a && b)), GNNOPS_EINVAL, "sddmm: null pointer");
-    switch (dtype) {
-        case GNNOPS_F32: return launch_sddmm<float>(rows_a, rows_b, a, b, out, nnz, D, (hipStream_t)s);
-        case GNNOPS_F16: return launch_sddmm<__half>(rows_a, rows_b, a, b, out, nnz, D, (hipStream_t)s);
-        case GNNOPS_BF16: return launch_sddmm<__hip_bfloat16>(rows_a, rows_b, a, b, out, nnz, D, (hipStream_t)s);
-    }
-    gnnops_set_error("sddmm: unknown dtype %d", dtype);
-    return GNNOPS_EINVAL;
+    return gnnops_with_dtype(dtype, "sddmm", [&](auto t) {
+        return launch_sddmm<typename decltype(t)::type>(rows_a, rows_b, a, b, out, nnz, D, (hipStream_t)s);
+    });
 }
 
 // ---- destination-partitioned scatter across GPUs (gnnops/dist.py): how many of this rank's edges go to each owner ----

@@ -18,6 +18,7 @@
 // holds the running value exactly, i.e. fp32 for every reduce and any type for min / max; the host side (ops.py) keeps
 // 16-bit sums / means / products on the plan path, where the fp32 accumulator is rounded once.
 #include "common.h"
+#include "dispatch.h"
 #include "hub.h"
 #include "lds_sort.h"
 #include "sort_engine.h"
@@ -334,8 +335,7 @@ int launch_bucket(const void* src, const uint32_t* keys, const uint32_t* vals, c
                   hipStream_t stream, void* hub_ws, size_t hub_ws_bytes, uint32_t* spare_keys, uint32_t* spare_vals) {
     constexpr int VEC = Elem<T>::VEC;
     const int64_t vecs = K / VEC;
-    int gshift = 0;
-    while ((1 << gshift) < vecs && gshift < 6) ++gshift;
+    const int gshift = gnnops_group_shift(vecs);
     const int kchunks = (int)gnnops_cdiv(vecs, (int64_t)1 << gshift);
     const int grid = gnnops_grid_cap(NB, 256 * 16);
     constexpr bool want_arg = (R == GNNOPS_MIN || R == GNNOPS_MAX);
@@ -521,11 +521,10 @@ extern "C" int gnnops_bucket_reduce_hubs(const void* src, const void* workspace,
     // the other half of the ping-pong buffers is scratch once the partition is built: the hub path compacts into it
     uint32_t* sk = (uint32_t*)(const_cast<char*>(w) + (last ? l.keys_a : l.keys_b));
     uint32_t* sv = (uint32_t*)(const_cast<char*>(w) + (last ? l.vals_a : l.vals_b));
-    switch (dtype) {
-        case GNNOPS_F32: return dispatch_bucket<float>(reduce, src, keys, vals, bptr, out, arg_out, E, K, N, NB, init_from_out, stream, hub_workspace, hub_workspace_bytes, sk, sv);
-        case GNNOPS_F16: return dispatch_bucket<__half>(reduce, src, keys, vals, bptr, out, arg_out, E, K, N, NB, init_from_out, stream, hub_workspace, hub_workspace_bytes, sk, sv);
-        default: return dispatch_bucket<__hip_bfloat16>(reduce, src, keys, vals, bptr, out, arg_out, E, K, N, NB, init_from_out, stream, hub_workspace, hub_workspace_bytes, sk, sv);
-    }
+    return gnnops_with_dtype(dtype, "bucket_reduce", [&](auto t) {
+        return dispatch_bucket<typename decltype(t)::type>(reduce, src, keys, vals, bptr, out, arg_out, E, K, N, NB, init_from_out, stream,
+                                                           hub_workspace, hub_workspace_bytes, sk, sv);
+    });
 }
 
 // index_select(input [N, K], index [E]) -> out [E, K] from a workspace gnnops_bucket_partition filled for (index, E, N):
@@ -555,8 +554,7 @@ extern "C" int gnnops_bucket_select_hubs(const void* input, const void* workspac
     const int32_t* bptr = (const int32_t*)(w + l.bptr);
     const int64_t NB = gnnops_cdiv(N, BROWS);
     const int64_t lanes = rowbytes / 16;
-    int gshift = 0;
-    while ((1 << gshift) < lanes && gshift < 6) ++gshift;
+    const int gshift = gnnops_group_shift(lanes);
     const int chunks = (int)gnnops_cdiv(lanes, (int64_t)1 << gshift);
     const int grid = gnnops_grid_cap(NB, 256 * 16);
     hub::Ws hw{};

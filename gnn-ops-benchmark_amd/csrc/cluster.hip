@@ -10,6 +10,7 @@
 // deterministic — ties go to the smaller index, neighbour lists come out in the package's order (knn: ascending distance;
 // radius: ascending candidate index, first max_num_neighbors).
 #include "common.h"
+#include "dispatch.h"
 #include <stdlib.h>
 
 namespace {
@@ -586,23 +587,18 @@ __global__ void graclus_finish_kernel(int64_t N, int64_t* __restrict__ cluster) 
 
 }  // namespace
 
-#define GNNOPS_BY_DTYPE(dtype, CALL, what)                                   \
-    switch (dtype) {                                                         \
-        case GNNOPS_F32: { using T = float; CALL; } break;                   \
-        case GNNOPS_F16: { using T = __half; CALL; } break;                  \
-        case GNNOPS_BF16: { using T = __hip_bfloat16; CALL; } break;         \
-        default: gnnops_set_error(what ": unknown dtype %d", dtype); return GNNOPS_EINVAL; \
-    }
-
 extern "C" int gnnops_grid_cluster(const void* pos, int64_t N, int D, const double* d_size, const double* d_start, const double* d_end,
                                    int64_t* cluster, int dtype, gnnops_stream_t s) {
     GNNOPS_REQUIRE(N >= 0 && D >= 1 && D <= 16, GNNOPS_EINVAL, "grid_cluster: bad shape");
     if (N == 0) return GNNOPS_OK;
     GNNOPS_REQUIRE(pos && d_size && d_start && d_end && cluster, GNNOPS_EINVAL, "grid_cluster: null pointer");
     const int grid = gnnops_grid_cap(gnnops_cdiv(N, 256));
-    GNNOPS_BY_DTYPE(dtype, hipLaunchKernelGGL((grid_cluster_kernel<T>), dim3(grid), dim3(256), 0, (hipStream_t)s, (const T*)pos, N, D, d_size,
-                                              d_start, d_end, cluster), "grid_cluster")
-    return gnnops_check_launch("grid_cluster");
+    return gnnops_with_dtype(dtype, "grid_cluster", [&](auto t) {
+        using T = typename decltype(t)::type;
+        hipLaunchKernelGGL((grid_cluster_kernel<T>), dim3(grid), dim3(256), 0, (hipStream_t)s, (const T*)pos, N, D, d_size, d_start, d_end,
+                           cluster);
+        return gnnops_check_launch("grid_cluster");
+    });
 }
 
 extern "C" int gnnops_knn(const void* x, const void* y, const int64_t* ptr_x, const int64_t* ptr_y, int64_t batches, int64_t Ny, int D,
@@ -612,24 +608,14 @@ extern "C" int gnnops_knn(const void* x, const void* y, const int64_t* ptr_x, co
     GNNOPS_REQUIRE(x && y && ptr_x && ptr_y && col, GNNOPS_EINVAL, "knn: null pointer");
     const int grid = gnnops_grid_cap(gnnops_cdiv(Ny, 4), 256 * 32);
     const char* kf = getenv("GNNOPS_KNN_ROUNDS");   // A/B (tools/time_knn.py): 1 = the k-round kernel for every k
-    if (k <= 64 && !(kf && kf[0] == '1')) {
-        if (cosine) {
-            GNNOPS_BY_DTYPE(dtype, hipLaunchKernelGGL((knn_topk_kernel<T, true>), dim3(grid), dim3(256), 0, (hipStream_t)s, (const T*)x, (const T*)y,
-                                                      ptr_x, ptr_y, (int)batches, Ny, D, k, col), "knn")
-        } else {
-            GNNOPS_BY_DTYPE(dtype, hipLaunchKernelGGL((knn_topk_kernel<T, false>), dim3(grid), dim3(256), 0, (hipStream_t)s, (const T*)x, (const T*)y,
-                                                      ptr_x, ptr_y, (int)batches, Ny, D, k, col), "knn")
-        }
+    const bool topk = k <= 64 && !(kf && kf[0] == '1');
+    return gnnops_with_dtype(dtype, "knn", [&](auto t) {
+        using T = typename decltype(t)::type;
+        auto* kernel = topk ? (cosine ? knn_topk_kernel<T, true> : knn_topk_kernel<T, false>)
+                            : (cosine ? knn_kernel<T, true> : knn_kernel<T, false>);
+        hipLaunchKernelGGL(kernel, dim3(grid), dim3(256), 0, (hipStream_t)s, (const T*)x, (const T*)y, ptr_x, ptr_y, (int)batches, Ny, D, k, col);
         return gnnops_check_launch("knn");
-    }
-    if (cosine) {
-        GNNOPS_BY_DTYPE(dtype, hipLaunchKernelGGL((knn_kernel<T, true>), dim3(grid), dim3(256), 0, (hipStream_t)s, (const T*)x, (const T*)y, ptr_x,
-                                                  ptr_y, (int)batches, Ny, D, k, col), "knn")
-    } else {
-        GNNOPS_BY_DTYPE(dtype, hipLaunchKernelGGL((knn_kernel<T, false>), dim3(grid), dim3(256), 0, (hipStream_t)s, (const T*)x, (const T*)y, ptr_x,
-                                                  ptr_y, (int)batches, Ny, D, k, col), "knn")
-    }
-    return gnnops_check_launch("knn");
+    });
 }
 
 // Step 1 of the grid form: bounding box of x (6 words at `box`, device) and the cell id of every point (int64, the plan
@@ -681,9 +667,12 @@ extern "C" int gnnops_radius(const void* x, const void* y, const int64_t* ptr_x,
     GNNOPS_REQUIRE(x && y && ptr_x && ptr_y && col, GNNOPS_EINVAL, "radius: null pointer");
     const int grid = gnnops_grid_cap(gnnops_cdiv(Ny, 4), 256 * 32);
     const float r2 = (float)(r * r);
-    GNNOPS_BY_DTYPE(dtype, hipLaunchKernelGGL((radius_kernel<T>), dim3(grid), dim3(256), 0, (hipStream_t)s, (const T*)x, (const T*)y, ptr_x, ptr_y,
-                                              (int)batches, Ny, D, r2, max_num_neighbors, col), "radius")
-    return gnnops_check_launch("radius");
+    return gnnops_with_dtype(dtype, "radius", [&](auto t) {
+        using T = typename decltype(t)::type;
+        hipLaunchKernelGGL((radius_kernel<T>), dim3(grid), dim3(256), 0, (hipStream_t)s, (const T*)x, (const T*)y, ptr_x, ptr_y, (int)batches, Ny,
+                           D, r2, max_num_neighbors, col);
+        return gnnops_check_launch("radius");
+    });
 }
 
 extern "C" int gnnops_fps(const void* x, const int64_t* ptr, const int64_t* out_ptr, const int64_t* start, int64_t batches, int D,
@@ -693,9 +682,12 @@ extern "C" int gnnops_fps(const void* x, const int64_t* ptr, const int64_t* out_
     GNNOPS_REQUIRE(x && ptr && out_ptr && start && dist_workspace && out, GNNOPS_EINVAL, "fps: null pointer");
     const char* fr = getenv("GNNOPS_FPS_REGISTERS");   // A/B and tests: 0 = the general loop for every cloud
     const int in_registers = !(fr && fr[0] == '0');
-    GNNOPS_BY_DTYPE(dtype, hipLaunchKernelGGL((fps_kernel<T>), dim3((unsigned)batches), dim3(1024), 0, (hipStream_t)s, (const T*)x, ptr, out_ptr,
-                                              start, D, dist_workspace, out, in_registers), "fps")
-    return gnnops_check_launch("fps");
+    return gnnops_with_dtype(dtype, "fps", [&](auto t) {
+        using T = typename decltype(t)::type;
+        hipLaunchKernelGGL((fps_kernel<T>), dim3((unsigned)batches), dim3(1024), 0, (hipStream_t)s, (const T*)x, ptr, out_ptr, start, D,
+                           dist_workspace, out, in_registers);
+        return gnnops_check_launch("fps");
+    });
 }
 
 extern "C" int gnnops_random_walk(const int64_t* rowptr, const int64_t* col, const int64_t* start, int64_t walkers, int walk_length,
@@ -732,8 +724,13 @@ extern "C" int gnnops_graclus_rounds(const int64_t* rowptr, const int64_t* col, 
     const int grid = gnnops_grid_cap(gnnops_cdiv(N, 256));
     for (int r = 0; r < rounds; ++r) {
         if (gnnops_memset_async(d_active, 0, sizeof(int), stream) != hipSuccess) return gnnops_check_launch("graclus memset");
-        GNNOPS_BY_DTYPE(dtype, hipLaunchKernelGGL((graclus_propose_kernel<T>), dim3(grid), dim3(256), 0, stream, rowptr, col, (const T*)weight, N,
-                                                  seed, cluster, proposal, d_active), "graclus")
+        const int rc = gnnops_with_dtype(dtype, "graclus", [&](auto t) {
+            using T = typename decltype(t)::type;
+            hipLaunchKernelGGL((graclus_propose_kernel<T>), dim3(grid), dim3(256), 0, stream, rowptr, col, (const T*)weight, N, seed, cluster,
+                               proposal, d_active);
+            return (int)GNNOPS_OK;
+        });
+        if (rc != GNNOPS_OK) return rc;
         hipLaunchKernelGGL(graclus_match_kernel, dim3(grid), dim3(256), 0, stream, N, proposal, cluster);
     }
     if (finish) hipLaunchKernelGGL(graclus_finish_kernel, dim3(grid), dim3(256), 0, stream, N, cluster);

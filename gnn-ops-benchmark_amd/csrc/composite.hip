@@ -12,6 +12,7 @@
 //   logsumexp    out[b,n,k] = max_n + log(sum_n + eps)          (empty group: max := 0, sum = 0)
 //   std          out[b,n,k] = sqrt( sum_n (x - mean_n)^2 / (cnt' + 1e-6) ),  cnt' = unbiased ? max(cnt-1,1) : max(cnt,1)
 #include "common.h"
+#include "dispatch.h"
 #include "hub.h"
 
 namespace {
@@ -384,8 +385,7 @@ int dispatch(int mode, const void* src, const int32_t* rowptr, const int32_t* pe
     constexpr int VEC = Elem<T>::VEC;
     if (K % VEC == 0 && (uintptr_t)src % 16 == 0 && (uintptr_t)out % 16 == 0) {
         const int64_t vecs = K / VEC;
-        int gshift = 0;
-        while ((1 << gshift) < vecs && gshift < 6) ++gshift;
+        const int gshift = gnnops_group_shift(vecs);
         const int kchunks = (int)gnnops_cdiv(vecs, (int64_t)1 << gshift);
         const int rgrid = gnnops_grid_cap(gnnops_cdiv(B * kchunks * N, 256 >> gshift), 256 * 64);
         hub::Ws hw{};
@@ -445,11 +445,8 @@ extern "C" int gnnops_segment_composite_hubs(const void* src, const int32_t* row
     GNNOPS_REQUIRE(E < ((int64_t)1 << 31), GNNOPS_EUNSUPPORTED, "segment_composite: E must be < 2^31");
     if (B * N * K == 0) return GNNOPS_OK;
     GNNOPS_REQUIRE(rowptr && out && (E == 0 || src), GNNOPS_EINVAL, "segment_composite: null pointer");
-    switch (dtype) {
-        case GNNOPS_F32: return dispatch<float>(mode, src, rowptr, perm, out, B, E, K, N, (float)param, stream, hub_workspace, hub_workspace_bytes);
-        case GNNOPS_F16: return dispatch<__half>(mode, src, rowptr, perm, out, B, E, K, N, (float)param, stream, hub_workspace, hub_workspace_bytes);
-        case GNNOPS_BF16: return dispatch<__hip_bfloat16>(mode, src, rowptr, perm, out, B, E, K, N, (float)param, stream, hub_workspace, hub_workspace_bytes);
-    }
-    gnnops_set_error("segment_composite: unknown dtype %d", dtype);
-    return GNNOPS_EINVAL;
+    return gnnops_with_dtype(dtype, "segment_composite", [&](auto t) {
+        return dispatch<typename decltype(t)::type>(mode, src, rowptr, perm, out, B, E, K, N, (float)param, stream, hub_workspace,
+                                                    hub_workspace_bytes);
+    });
 }

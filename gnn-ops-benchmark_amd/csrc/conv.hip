@@ -24,6 +24,7 @@
 // Algorithmic bytes per launch: E * (q row + 8 B column id (+ w row)) + N * (p row + out row) + 4 (N + 1); measured traffic
 // and the optimisation ladder: DESIGN.md §4 "Message-passing layers", profiles/round2_f_*.
 #include "common.h"
+#include "dispatch.h"
 
 namespace {
 
@@ -536,8 +537,7 @@ int launch_vec(Args& a, hipStream_t stream) {
     // gathered tables beyond ~2 GiB do not stay in the Infinity Cache between visits: stream them past it (as spmm.hip)
     a.nt = (double)a.N * (double)a.ldq * sizeof(T) > 2.0 * 1024 * 1024 * 1024;
     const int64_t lanes = a.K / VEC;
-    int gshift = 0;
-    while ((1 << gshift) < lanes && gshift < 6) ++gshift;
+    const int gshift = gnnops_group_shift(lanes);
     a.gshift = gshift;
     a.kchunks = (int)gnnops_cdiv(lanes, (int64_t)1 << gshift);
     const int64_t items = (int64_t)a.kchunks * a.N;
@@ -566,12 +566,7 @@ int launch(const Args& a0, int max_vec, hipStream_t stream) {
     while (vec > 1 && (vec > max_vec || a.K % vec != 0)) vec >>= 1;
     if (HEAVY)
         while (vec > 1 && vec * sizeof(T) > 4 && a.K / vec < 64) vec >>= 1;
-    if constexpr (NATIVE == 8) {
-        if (vec == 8) return launch_vec<T, F, MULTI, HAS_W, 8>(a, stream);
-    }
-    if (vec == 4) return launch_vec<T, F, MULTI, HAS_W, 4>(a, stream);
-    if (vec == 2) return launch_vec<T, F, MULTI, HAS_W, 2>(a, stream);
-    return launch_vec<T, F, MULTI, HAS_W, 1>(a, stream);
+    return gnnops_with_piece_width<T>(vec, [&](auto v) { return launch_vec<T, F, MULTI, HAS_W, decltype(v)::value>(a, stream); });
 }
 
 template <typename T>
@@ -662,22 +657,11 @@ extern "C" int gnnops_edge_reduce_hubs(int functor, const void* q, int64_t ldq, 
     GNNOPS_REQUIRE(ldq >= parts_q[functor] * K && (!p || ldp >= parts_p[functor] * K) && (!w || ldw >= parts_w[functor] * K) &&
                        (!add || ldadd >= K) && ldo >= (int64_t)a.n_scal * n_aggr * K,
                    GNNOPS_EINVAL, "edge_reduce: a row pitch is shorter than the row");
-    size_t es;
-    int vec;
-    switch (dtype) {
-        case GNNOPS_F32: es = 4; vec = 4; break;
-        case GNNOPS_F16: case GNNOPS_BF16: es = 2; vec = 8; break;
-        default: gnnops_set_error("edge_reduce: unknown dtype %d", dtype); return GNNOPS_EINVAL;
-    }
-    // widest aligned piece (elements) every operand row allows: pointers and pitches in bytes share a power-of-two factor
-    int max_vec = vec;
-    auto narrow = [&](const void* ptr, int64_t ld) {
-        if (!ptr) return;
-        while (max_vec > 1 && ((uintptr_t)ptr % (max_vec * es) != 0 || (ld * es) % (max_vec * es) != 0)) max_vec >>= 1;
-    };
-    narrow(q, ldq); narrow(p, ldp); narrow(w, ldw); narrow(add, ldadd); narrow(out, ldo);
-    if ((K * es) % (max_vec * es) != 0)
-        while (max_vec > 1 && K % max_vec != 0) max_vec >>= 1;
+    const int es = gnnops_elem_bytes(dtype);
+    GNNOPS_REQUIRE(es, GNNOPS_EINVAL, "edge_reduce: unknown dtype %d", dtype);
+    // widest aligned piece (elements) every operand row allows, narrowed here until it divides the K offset of a row's parts
+    int max_vec = gnnops_widest_piece(es, {{q, ldq}, {p, ldp}, {w, ldw}, {add, ldadd}, {out, ldo}});
+    while (max_vec > 1 && K % max_vec != 0) max_vec >>= 1;
     if (hub_workspace && E > 4 * T_HUB) {   // destinations with more than T_HUB edges are reduced piecewise (sums re-associated)
         const HubLayout l = hub_layout(E, K);
         GNNOPS_REQUIRE(hub_workspace_bytes >= l.total && (uintptr_t)hub_workspace % 16 == 0, GNNOPS_EWORKSPACE,
@@ -690,11 +674,7 @@ extern "C" int gnnops_edge_reduce_hubs(int functor, const void* q, int64_t ldq, 
         a.max_hubs = l.max_hubs;
     }
     hipStream_t stream = (hipStream_t)s;
-    switch (dtype) {
-        case GNNOPS_F32: return dispatch<float>(functor, multi, a, max_vec, stream);
-        case GNNOPS_F16: return dispatch<__half>(functor, multi, a, max_vec, stream);
-        default: return dispatch<__hip_bfloat16>(functor, multi, a, max_vec, stream);
-    }
+    return gnnops_with_dtype(dtype, "edge_reduce", [&](auto t) { return dispatch<typename decltype(t)::type>(functor, multi, a, max_vec, stream); });
 }
 
 // ---- backward of the edge pass (training through gnnops.conv; the reference's OpProfiler.py:259-292 profiles a TRAIN loop) ----
@@ -764,12 +744,13 @@ int launch_edge_grad(const void* p, int64_t ldp, const void* q, int64_t ldq, con
                      const int64_t* src, const int64_t* dst, void* gp, void* gq, int64_t E, int64_t K, int vec, hipStream_t stream) {
     const int64_t items = E * (K / vec);
     const int grid = gnnops_grid_cap(gnnops_cdiv(items, 256), 256 * 32);
-#define GNNOPS_EG(V)                                                                                                              \
-    hipLaunchKernelGGL((edge_grad_kernel<T, F, HAS_W, V>), dim3(grid), dim3(256), 0, stream, (const T*)p, ldp, (const T*)q, ldq, \
-                       (const T*)w, ldw, (const T*)g, ldg, src, dst, (T*)gp, (T*)gq, E, K)
-    if (vec == Elem<T>::VEC) GNNOPS_EG(Elem<T>::VEC);
-    else GNNOPS_EG(1);
-#undef GNNOPS_EG
+    // two widths only, 16 bytes or one element: gnnops_with_piece_width would instantiate the kernels between them as well
+    auto run = [&](auto v) {
+        hipLaunchKernelGGL((edge_grad_kernel<T, F, HAS_W, decltype(v)::value>), dim3(grid), dim3(256), 0, stream, (const T*)p, ldp, (const T*)q,
+                           ldq, (const T*)w, ldw, (const T*)g, ldg, src, dst, (T*)gp, (T*)gq, E, K);
+    };
+    if (vec == Elem<T>::VEC) run(std::integral_constant<int, Elem<T>::VEC>{});
+    else run(std::integral_constant<int, 1>{});
     return gnnops_check_launch("edge_grad");
 }
 
@@ -794,22 +775,16 @@ extern "C" int gnnops_edge_grad(int functor, const void* p, int64_t ldp, const v
     GNNOPS_REQUIRE(p && q && g && src && dst && gp && (functor == F_CGCONV || gq), GNNOPS_EINVAL, "edge_grad: null pointer");
     GNNOPS_REQUIRE(ldp >= 2 * K && ldq >= (functor == F_CGCONV ? 2 : 1) * K && ldg >= K && (!w || ldw >= 2 * K), GNNOPS_EINVAL,
                    "edge_grad: a row pitch is shorter than the row");
-    int es, vec;
-    switch (dtype) {
-        case GNNOPS_F32: es = 4; vec = 4; break;
-        case GNNOPS_F16: case GNNOPS_BF16: es = 2; vec = 8; break;
-        default: gnnops_set_error("edge_grad: unknown dtype %d", dtype); return GNNOPS_EINVAL;
-    }
-    bool wide = K % vec == 0;   // 16-B pieces need every row start 16-B aligned: pointers, pitches and the K offset of a part
-    auto ok = [&](const void* ptr, int64_t ld) { return !ptr || ((uintptr_t)ptr % 16 == 0 && (ld * es) % 16 == 0); };
-    wide = wide && ok(p, ldp) && ok(q, ldq) && ok(w, ldw) && ok(g, ldg) && ok(gp, 2 * K) && ok(gq, K) && (K * es) % 16 == 0;
+    const int es = gnnops_elem_bytes(dtype);
+    GNNOPS_REQUIRE(es, GNNOPS_EINVAL, "edge_grad: unknown dtype %d", dtype);
+    const int vec = 16 / es;
+    // 16-B pieces need every row start 16-B aligned: pointers, pitches and the K offset of a part
+    const bool wide = K % vec == 0 && gnnops_widest_piece(es, {{p, ldp}, {q, ldq}, {w, ldw}, {g, ldg}, {gp, 2 * K}, {gq, K}}) == vec;
     const int v = wide ? vec : 1;
     hipStream_t stream = (hipStream_t)s;
-    switch (dtype) {
-        case GNNOPS_F32: return dispatch_edge_grad<float>(functor, p, ldp, q, ldq, w, ldw, g, ldg, src, dst, gp, gq, E, K, v, stream);
-        case GNNOPS_F16: return dispatch_edge_grad<__half>(functor, p, ldp, q, ldq, w, ldw, g, ldg, src, dst, gp, gq, E, K, v, stream);
-        default: return dispatch_edge_grad<__hip_bfloat16>(functor, p, ldp, q, ldq, w, ldw, g, ldg, src, dst, gp, gq, E, K, v, stream);
-    }
+    return gnnops_with_dtype(dtype, "edge_grad", [&](auto t) {
+        return dispatch_edge_grad<typename decltype(t)::type>(functor, p, ldp, q, ldq, w, ldw, g, ldg, src, dst, gp, gq, E, K, v, stream);
+    });
 }
 
 // ---- backward of the MULTI-aggregator pass (PNAConv in a training loop) ----
@@ -1009,8 +984,7 @@ int launch_multi_grad_vec(MultiGradArgs& b, hipStream_t stream) {   // lane layo
     Args& a = b.a;
     a.nt = (double)a.N * (double)a.ldq * sizeof(T) > 2.0 * 1024 * 1024 * 1024;
     const int64_t lanes = a.K / VEC;
-    int gshift = 0;
-    while ((1 << gshift) < lanes && gshift < 6) ++gshift;
+    const int gshift = gnnops_group_shift(lanes);
     a.gshift = gshift;
     a.kchunks = (int)gnnops_cdiv(lanes, (int64_t)1 << gshift);
     const int64_t items = (int64_t)a.kchunks * a.N;
@@ -1025,12 +999,7 @@ int launch_multi_grad(MultiGradArgs& b, int max_vec, hipStream_t stream) {   // 
     int vec = Elem<T>::VEC;
     while (vec > 1 && (vec > max_vec || b.a.K % vec != 0)) vec >>= 1;
     while (vec > 1 && vec * sizeof(T) > 4 && b.a.K / vec < 64) vec >>= 1;
-    if constexpr (Elem<T>::VEC == 8) {
-        if (vec == 8) return launch_multi_grad_vec<T, F, HAS_W, 8>(b, stream);
-    }
-    if (vec == 4) return launch_multi_grad_vec<T, F, HAS_W, 4>(b, stream);
-    if (vec == 2) return launch_multi_grad_vec<T, F, HAS_W, 2>(b, stream);
-    return launch_multi_grad_vec<T, F, HAS_W, 1>(b, stream);
+    return gnnops_with_piece_width<T>(vec, [&](auto v) { return launch_multi_grad_vec<T, F, HAS_W, decltype(v)::value>(b, stream); });
 }
 
 template <typename T>
@@ -1078,24 +1047,13 @@ extern "C" int gnnops_edge_multi_grad(int functor, const void* q, int64_t ldq, c
     b.g = g; b.ldg = ldg; b.gm = gm; b.gp = gp;
     GNNOPS_REQUIRE(ldq >= K && (!p || ldp >= K) && (!w || ldw >= K) && (ldg == 0 || ldg >= (int64_t)a.n_scal * n_aggr * K), GNNOPS_EINVAL,
                    "edge_multi_grad: a row pitch is shorter than the row");
-    size_t es;
-    int vec;
-    switch (dtype) {
-        case GNNOPS_F32: es = 4; vec = 4; break;
-        case GNNOPS_F16: case GNNOPS_BF16: es = 2; vec = 8; break;
-        default: gnnops_set_error("edge_multi_grad: unknown dtype %d", dtype); return GNNOPS_EINVAL;
-    }
-    int max_vec = vec;   // widest aligned piece (elements) every operand row allows, as gnnops_edge_reduce_hubs
-    auto narrow = [&](const void* ptr, int64_t ld) {
-        if (!ptr) return;
-        while (max_vec > 1 && ((uintptr_t)ptr % (max_vec * es) != 0 || (ld * es) % (max_vec * es) != 0)) max_vec >>= 1;
-    };
-    narrow(q, ldq); narrow(p, ldp); narrow(w, ldw); narrow(g, ldg); narrow(gm, K); narrow(gp, K);
+    const int es = gnnops_elem_bytes(dtype);
+    GNNOPS_REQUIRE(es, GNNOPS_EINVAL, "edge_multi_grad: unknown dtype %d", dtype);
+    // widest aligned piece (elements) every operand row allows, narrowed by K as gnnops_edge_reduce_hubs
+    int max_vec = gnnops_widest_piece(es, {{q, ldq}, {p, ldp}, {w, ldw}, {g, ldg}, {gm, K}, {gp, K}});
     while (max_vec > 1 && K % max_vec != 0) max_vec >>= 1;
     hipStream_t stream = (hipStream_t)s;
-    switch (dtype) {
-        case GNNOPS_F32: return dispatch_multi_grad<float>(functor, b, max_vec, stream);
-        case GNNOPS_F16: return dispatch_multi_grad<__half>(functor, b, max_vec, stream);
-        default: return dispatch_multi_grad<__hip_bfloat16>(functor, b, max_vec, stream);
-    }
+    return gnnops_with_dtype(dtype, "edge_multi_grad", [&](auto t) {
+        return dispatch_multi_grad<typename decltype(t)::type>(functor, b, max_vec, stream);
+    });
 }

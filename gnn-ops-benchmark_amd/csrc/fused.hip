@@ -12,6 +12,7 @@
 //     combined in slice order by a second launch (deterministic).
 //   K == 1 (dim 1 of a matrix): one wave per row b, lanes stride over n (coalesced), wave reduction.
 #include "common.h"
+#include "dispatch.h"
 
 namespace {
 
@@ -214,11 +215,7 @@ extern "C" int gnnops_fused_index_add_select_sum(const void* input, const void* 
                    GNNOPS_EWORKSPACE, "fused_index_add_select_sum: workspace too small");
     GNNOPS_REQUIRE(gnnops_cdiv(B * K, 256) < ((int64_t)1 << 31), GNNOPS_EUNSUPPORTED, "fused: too many columns");
     float* partial = (float*)workspace;
-    switch (dtype) {
-        case GNNOPS_F32: return launch<float>(input, other, rowptr, perm, out_f32, B, N, E, K, partial, stream);
-        case GNNOPS_F16: return launch<__half>(input, other, rowptr, perm, out_f32, B, N, E, K, partial, stream);
-        case GNNOPS_BF16: return launch<__hip_bfloat16>(input, other, rowptr, perm, out_f32, B, N, E, K, partial, stream);
-    }
-    gnnops_set_error("fused_index_add_select_sum: unknown dtype %d", dtype);
-    return GNNOPS_EINVAL;
+    return gnnops_with_dtype(dtype, "fused_index_add_select_sum", [&](auto t) {
+        return launch<typename decltype(t)::type>(input, other, rowptr, perm, out_f32, B, N, E, K, partial, stream);
+    });
 }

@@ -5,6 +5,7 @@
 // All HBM-bound byte movers: 16-B lane accesses along the feature dimension, several rows in flight
 // per lane group to cover the dependent index -> row latency. No MFMA here by design.
 #include "common.h"
+#include "dispatch.h"
 #include <stdlib.h>
 #include "hub.h"
 #include <type_traits>
@@ -492,8 +493,7 @@ __global__ __launch_bounds__(256) void combine_partials_kernel(const float* __re
 
 struct RowGeom { int gshift; int chunks; };
 inline RowGeom row_geom(int64_t vecs) {
-    RowGeom g{0, 1};
-    while ((1 << g.gshift) < vecs && g.gshift < 6) ++g.gshift;
+    RowGeom g{gnnops_group_shift(vecs), 1};
     g.chunks = (int)gnnops_cdiv(vecs, (int64_t)1 << g.gshift);
     return g;
 }
@@ -884,11 +884,7 @@ extern "C" int gnnops_fused_index_select_sum(const void* input, const int64_t* i
     GNNOPS_REQUIRE(workspace && workspace_bytes >= gnnops_fused_select_sum_workspace_bytes(), GNNOPS_EWORKSPACE,
                    "fused_index_select_sum: workspace too small");
     float* partial = (float*)workspace;
-    switch (dtype) {
-        case GNNOPS_F32: return launch_select_sum<float>(input, index, d_sum_f32, B, N, K, E, partial, stream);
-        case GNNOPS_F16: return launch_select_sum<__half>(input, index, d_sum_f32, B, N, K, E, partial, stream);
-        case GNNOPS_BF16: return launch_select_sum<__hip_bfloat16>(input, index, d_sum_f32, B, N, K, E, partial, stream);
-    }
-    gnnops_set_error("fused_index_select_sum: unknown dtype %d", dtype);
-    return GNNOPS_EINVAL;
+    return gnnops_with_dtype(dtype, "fused_index_select_sum", [&](auto t) {
+        return launch_select_sum<typename decltype(t)::type>(input, index, d_sum_f32, B, N, K, E, partial, stream);
+    });
 }

@@ -14,6 +14,7 @@
 // combined by a fixed xor tree: the same bits every run). No atomics. A destination of any in-degree is handled by the same
 // loop: its group just runs longer ("GraphUNet", says what that costs).
 #include "common.h"
+#include "dispatch.h"
 
 namespace {
 
@@ -185,9 +186,5 @@ extern "C" int gnnops_gcn_propagate(const void* h, int64_t ldh, const int32_t* r
     a.h = h; a.bias = bias; a.out = out; a.rowptr = rowptr; a.perm = perm; a.col = col; a.w = w; a.dis = dis; a.lw = lw;
     a.N = N; a.K = K; a.ldh = ldh; a.ldo = ldo; a.lpr_shift = a.slot_shift = 0;
     hipStream_t stream = (hipStream_t)s;
-    switch (dtype) {
-        case GNNOPS_F32: return launch<float>(a, stream);
-        case GNNOPS_F16: return launch<__half>(a, stream);
-        default: return launch<__hip_bfloat16>(a, stream);
-    }
+    return gnnops_with_dtype(dtype, "gcn_propagate", [&](auto t) { return launch<typename decltype(t)::type>(a, stream); });
 }

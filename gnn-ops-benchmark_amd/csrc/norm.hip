@@ -17,10 +17,9 @@
 // N * C * H written. d bias / d gamma / d beta: every lane group keeps fp32 partials over its rows (registers; the wide
 // instance keeps them in its own row of the workspace), writes one row of [groups, 3, C], and a second small kernel adds the
 // rows in a fixed order: no atomics, the same bits every run.
-#include <initializer_list>
-#include <utility>
 #include "common.h"
 #include "lane_group.h"
+#include "dispatch.h"
 
 namespace {
 
@@ -315,7 +314,7 @@ inline Geometry geometry(int C, int max_vec) {
     const int pieces = C / vec;
     Geometry g{};
     g.vec = vec;
-    while ((1 << g.gshift) < pieces && g.gshift < 6) ++g.gshift;
+    g.gshift = gnnops_group_shift(pieces);
     g.nch = pieces <= 64 ? 1 : pieces <= 128 ? 2 : pieces <= 256 ? 4 : 0;
     if (g.nch == 0) { g.vec = 1; g.gshift = 6; }      // 64 lanes x single elements, the row re-read per pass: any C <= 8192
     g.nk = (int)gnnops_cdiv(C, (int64_t)g.vec << g.gshift);
@@ -329,15 +328,6 @@ inline int backward_waves(int64_t N, int C, int gshift) {
     waves = waves < 64 ? 64 : waves > 2048 ? 2048 : waves;
     const int64_t need = gnnops_cdiv(N, R);
     return (int)(waves < need ? waves : need < 1 ? 1 : need);
-}
-
-inline int max_vec_of(int es, std::initializer_list<std::pair<const void*, int64_t>> operands) {
-    int max_vec = 16 / es;
-    for (const auto& op : operands) {
-        if (!op.first) continue;
-        while (max_vec > 1 && ((uintptr_t)op.first % (max_vec * es) != 0 || (op.second * es) % (max_vec * es) != 0)) max_vec >>= 1;
-    }
-    return max_vec;
 }
 
 template <typename T, bool BW, int VEC, int NCH>
@@ -356,12 +346,7 @@ void launch_pieces(const NormArgs& a, int nch, int grid, hipStream_t stream) {
 template <typename T, bool BW>
 void launch(const NormArgs& a, const Geometry& geo, int grid, hipStream_t stream) {
     if (geo.nch == 0) return launch_kernel<T, BW, 1, 0>(a, grid, stream);
-    if constexpr (Elem<T>::VEC == 8) {
-        if (geo.vec == 8) return launch_pieces<T, BW, 8>(a, geo.nch, grid, stream);
-    }
-    if (geo.vec == 4) return launch_pieces<T, BW, 4>(a, geo.nch, grid, stream);
-    if (geo.vec == 2) return launch_pieces<T, BW, 2>(a, geo.nch, grid, stream);
-    return launch_pieces<T, BW, 1>(a, geo.nch, grid, stream);
+    gnnops_with_piece_width<T>(geo.vec, [&](auto v) { launch_pieces<T, BW, decltype(v)::value>(a, geo.nch, grid, stream); });
 }
 
 int check_sizes(const char* what, int64_t N, int64_t H, int64_t C, int64_t lda, int dtype, int* es) {
@@ -370,11 +355,8 @@ int check_sizes(const char* what, int64_t N, int64_t H, int64_t C, int64_t lda, 
                    "%s: needs heads >= 1, channels >= 1 and heads * channels <= 8192 (got %lld x %lld)", what, (long long)H, (long long)C);
     GNNOPS_REQUIRE(N < ((int64_t)1 << 31) && lda < ((int64_t)1 << 31), GNNOPS_EUNSUPPORTED, "%s: N and the row pitch must be < 2^31", what);
     GNNOPS_REQUIRE(lda >= H * C, GNNOPS_EINVAL, "%s: a row pitch is shorter than the row", what);
-    switch (dtype) {
-        case GNNOPS_F32: *es = 4; break;
-        case GNNOPS_F16: case GNNOPS_BF16: *es = 2; break;
-        default: gnnops_set_error("%s: unknown dtype %d", what, dtype); return GNNOPS_EINVAL;
-    }
+    *es = gnnops_elem_bytes(dtype);
+    GNNOPS_REQUIRE(*es, GNNOPS_EINVAL, "%s: unknown dtype %d", what, dtype);
     return GNNOPS_OK;
 }
 
@@ -389,7 +371,7 @@ extern "C" int gnnops_head_act_norm(const void* a, int64_t lda, const void* bias
     GNNOPS_REQUIRE(gamma || !beta, GNNOPS_EINVAL, "head_act_norm: beta without gamma");
     if (N == 0) return GNNOPS_OK;
     GNNOPS_REQUIRE(a && out, GNNOPS_EINVAL, "head_act_norm: null pointer");
-    const int max_vec = max_vec_of(es, {{a, lda}, {bias, 0}, {scale, C}, {gamma, 0}, {beta, 0}, {out, C}});
+    const int max_vec = gnnops_widest_piece(es, {{a, lda}, {bias, 0}, {scale, C}, {gamma, 0}, {beta, 0}, {out, C}});
     const Geometry geo = geometry((int)C, max_vec);
     NormArgs args{};
     args.a = a; args.bias = bias; args.k = scale; args.gamma = gamma; args.beta = beta; args.out = out; args.stats = gamma ? stats : nullptr;
@@ -398,12 +380,10 @@ extern "C" int gnnops_head_act_norm(const void* a, int64_t lda, const void* bias
     const int grid = gnnops_grid_cap(gnnops_cdiv(gnnops_cdiv(N, 64 >> geo.gshift), 4), 256 * 32);
     args.nwaves = grid * 4;
     hipStream_t stream = (hipStream_t)s;
-    switch (dtype) {
-        case GNNOPS_F32: launch<float, false>(args, geo, grid, stream); break;
-        case GNNOPS_F16: launch<__half, false>(args, geo, grid, stream); break;
-        default: launch<__hip_bfloat16, false>(args, geo, grid, stream); break;
-    }
-    return gnnops_check_launch("head_act_norm");
+    return gnnops_with_dtype(dtype, "head_act_norm", [&](auto t) {
+        launch<typename decltype(t)::type, false>(args, geo, grid, stream);
+        return gnnops_check_launch("head_act_norm");
+    });
 }
 
 extern "C" size_t gnnops_head_act_norm_backward_workspace_bytes(int64_t N, int64_t H, int64_t C) {
@@ -432,7 +412,7 @@ extern "C" int gnnops_head_act_norm_backward(const void* a, int64_t lda, const v
     const size_t need = gnnops_head_act_norm_backward_workspace_bytes(N, H, C);
     GNNOPS_REQUIRE(workspace && workspace_bytes >= need && (uintptr_t)workspace % 16 == 0, GNNOPS_EWORKSPACE,
                    "head_act_norm_backward: workspace %zu < %zu", workspace_bytes, need);
-    const int max_vec = max_vec_of(es, {{a, lda}, {bias, 0}, {scale, C}, {gamma, 0}, {grad_out, ldg}, {grad_a, H * C}});
+    const int max_vec = gnnops_widest_piece(es, {{a, lda}, {bias, 0}, {scale, C}, {gamma, 0}, {grad_out, ldg}, {grad_a, H * C}});
     const Geometry geo = geometry((int)C, max_vec);
     NormArgs args{};
     args.a = a; args.bias = bias; args.k = scale; args.gamma = gamma; args.g = grad_out; args.da = grad_a;
@@ -442,19 +422,15 @@ extern "C" int gnnops_head_act_norm_backward(const void* a, int64_t lda, const v
     args.nwaves = backward_waves(N, (int)C, geo.gshift);
     const int grid = (int)gnnops_cdiv(args.nwaves, 4);
     hipStream_t stream = (hipStream_t)s;
-    switch (dtype) {
-        case GNNOPS_F32: launch<float, true>(args, geo, grid, stream); break;
-        case GNNOPS_F16: launch<__half, true>(args, geo, grid, stream); break;
-        default: launch<__hip_bfloat16, true>(args, geo, grid, stream); break;
-    }
-    if (grad_bias || grad_gamma || grad_beta) {
-        const int rows = args.nwaves * (64 >> geo.gshift);
-        const dim3 cgrid((unsigned)gnnops_cdiv(3 * C, 32));
-        switch (dtype) {
-            case GNNOPS_F32: hipLaunchKernelGGL(head_act_norm_colsum_kernel<float>, cgrid, dim3(256), 0, stream, args.partial, rows, (int)C, (float*)grad_bias, (float*)grad_gamma, (float*)grad_beta); break;
-            case GNNOPS_F16: hipLaunchKernelGGL(head_act_norm_colsum_kernel<__half>, cgrid, dim3(256), 0, stream, args.partial, rows, (int)C, (__half*)grad_bias, (__half*)grad_gamma, (__half*)grad_beta); break;
-            default: hipLaunchKernelGGL(head_act_norm_colsum_kernel<__hip_bfloat16>, cgrid, dim3(256), 0, stream, args.partial, rows, (int)C, (__hip_bfloat16*)grad_bias, (__hip_bfloat16*)grad_gamma, (__hip_bfloat16*)grad_beta); break;
+    return gnnops_with_dtype(dtype, "head_act_norm_backward", [&](auto t) {
+        using T = typename decltype(t)::type;
+        launch<T, true>(args, geo, grid, stream);
+        if (grad_bias || grad_gamma || grad_beta) {
+            const int rows = args.nwaves * (64 >> geo.gshift);
+            const dim3 cgrid((unsigned)gnnops_cdiv(3 * C, 32));
+            hipLaunchKernelGGL(head_act_norm_colsum_kernel<T>, cgrid, dim3(256), 0, stream, args.partial, rows, (int)C, (T*)grad_bias,
+                               (T*)grad_gamma, (T*)grad_beta);
         }
-    }
-    return gnnops_check_launch("head_act_norm_backward");
+        return gnnops_check_launch("head_act_norm_backward");
+    });
 }

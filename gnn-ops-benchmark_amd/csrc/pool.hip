@@ -19,6 +19,7 @@
 // order, so survivors keep their order. 2 x 16 B read per edge and pass, 16 B (+ the value row) written per survivor.
 #include <type_traits>
 #include "common.h"
+#include "dispatch.h"
 #include "lds_sort.h"
 
 namespace {
@@ -322,11 +323,10 @@ extern "C" int gnnops_segment_topk(const void* score, const int32_t* graph_ptr, 
     GNNOPS_REQUIRE(on_chip || (workspace && workspace_bytes >= need), GNNOPS_EWORKSPACE, "segment_topk: workspace %zu < %zu",
                    workspace_bytes, need);
     hipStream_t stream = (hipStream_t)s;
-    switch (dtype) {
-        case GNNOPS_F32: return topk_typed<float>(score, graph_ptr, out_ptr, perm, G, N, max_graph_len, on_chip, route == 0 && !on_chip, workspace, stream);
-        case GNNOPS_F16: return topk_typed<__half>(score, graph_ptr, out_ptr, perm, G, N, max_graph_len, on_chip, route == 0 && !on_chip, workspace, stream);
-        default: return topk_typed<__hip_bfloat16>(score, graph_ptr, out_ptr, perm, G, N, max_graph_len, on_chip, route == 0 && !on_chip, workspace, stream);
-    }
+    return gnnops_with_dtype(dtype, "segment_topk", [&](auto t) {
+        return topk_typed<typename decltype(t)::type>(score, graph_ptr, out_ptr, perm, G, N, max_graph_len, on_chip, route == 0 && !on_chip,
+                                                      workspace, stream);
+    });
 }
 
 extern "C" int gnnops_node_map(const int64_t* perm, int64_t k, int64_t N, int32_t* node_map, gnnops_stream_t s) {

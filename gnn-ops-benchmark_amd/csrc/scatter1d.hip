@@ -29,6 +29,7 @@
 // HBM-bound, and no random access anywhere: per element ~100 B of streamed traffic (first pass 12 + 12 read, 12 written;
 // second 8 + 12 read, 12 written; reduce 12 + 12 read) + 12 B written per destination.
 #include "common.h"
+#include "dispatch.h"
 #include "lds_sort.h"
 #include "sort_engine.h"
 
@@ -315,6 +316,11 @@ int run1d(const void* src, const int64_t* index, void* out, int64_t* arg_out, in
     return gnnops_check_launch("scatter1d_minmax");
 }
 
+// the sort engine's first pass of each element type
+inline auto first_pass_of(gnnops_type_tag<float>) { return sortengine::pass_first_dstval_f32; }
+inline auto first_pass_of(gnnops_type_tag<__half>) { return sortengine::pass_first_dstval_f16; }
+inline auto first_pass_of(gnnops_type_tag<__hip_bfloat16>) { return sortengine::pass_first_dstval_bf16; }
+
 }  // namespace
 
 extern "C" size_t gnnops_scatter1d_workspace_bytes(int64_t E, int64_t N) {
@@ -336,14 +342,9 @@ extern "C" int gnnops_scatter1d_minmax(const void* src, const int64_t* index, vo
     GNNOPS_REQUIRE(workspace && workspace_bytes >= l.total && (uintptr_t)workspace % 256 == 0, GNNOPS_EWORKSPACE,
                    "scatter1d_minmax: workspace %zu < %zu (or not 256-B aligned)", workspace_bytes, l.total);
     hipStream_t stream = (hipStream_t)s;
-    switch (dtype) {
-        case GNNOPS_F32: return run1d<float>(src, index, out, arg_out, E, N, reduce, workspace, stream, sortengine::pass_first_dstval_f32);
-        case GNNOPS_F16: return run1d<__half>(src, index, out, arg_out, E, N, reduce, workspace, stream, sortengine::pass_first_dstval_f16);
-        case GNNOPS_BF16:
-            return run1d<__hip_bfloat16>(src, index, out, arg_out, E, N, reduce, workspace, stream, sortengine::pass_first_dstval_bf16);
-    }
-    gnnops_set_error("scatter1d_minmax: unknown dtype %d", dtype);
-    return GNNOPS_EINVAL;
+    return gnnops_with_dtype(dtype, "scatter1d_minmax", [&](auto t) {
+        return run1d<typename decltype(t)::type>(src, index, out, arg_out, E, N, reduce, workspace, stream, first_pass_of(t));
+    });
 }
 
 // out[n] = sum / mean / product of src[e] over index[e] == n, in source position order (0 — 1 for a product — where nothing
@@ -360,12 +361,7 @@ extern "C" int gnnops_scatter1d_sum(const void* src, const int64_t* index, void*
     GNNOPS_REQUIRE(workspace && workspace_bytes >= l.total && (uintptr_t)workspace % 256 == 0, GNNOPS_EWORKSPACE,
                    "scatter1d_sum: workspace %zu < %zu (or not 256-B aligned)", workspace_bytes, l.total);
     hipStream_t stream = (hipStream_t)s;
-    switch (dtype) {
-        case GNNOPS_F32: return run1d_sum<float>(src, index, out, E, N, reduce, workspace, stream, sortengine::pass_first_dstval_f32);
-        case GNNOPS_F16: return run1d_sum<__half>(src, index, out, E, N, reduce, workspace, stream, sortengine::pass_first_dstval_f16);
-        case GNNOPS_BF16:
-            return run1d_sum<__hip_bfloat16>(src, index, out, E, N, reduce, workspace, stream, sortengine::pass_first_dstval_bf16);
-    }
-    gnnops_set_error("scatter1d_sum: unknown dtype %d", dtype);
-    return GNNOPS_EINVAL;
+    return gnnops_with_dtype(dtype, "scatter1d_sum", [&](auto t) {
+        return run1d_sum<typename decltype(t)::type>(src, index, out, E, N, reduce, workspace, stream, first_pass_of(t));
+    });
 }

@@ -11,6 +11,7 @@
 // Which form takes a call — one LDS strip, chunked LDS strips or memory-side atomics — and with what geometry is decided
 // in elem_route() alone; gnnops_scatter_elementwise_route reports it.
 #include "common.h"
+#include "dispatch.h"
 
 namespace {
 
@@ -836,13 +837,9 @@ extern "C" int gnnops_scatter_elementwise_ixa(const void* src, const void* index
     const size_t need = gnnops_scatter_elementwise_workspace_bytes(B, N, K, dtype, reduce);
     GNNOPS_REQUIRE(need == 0 || (workspace && workspace_bytes >= need), GNNOPS_EWORKSPACE,
                    "scatter_elementwise: workspace %zu < %zu", workspace_bytes, need);
-    switch (dtype) {
-        case GNNOPS_F32: return run<float>(src, index, index_bytes, out, arg_out, B, E, K, N, reduce, init_from_out, workspace, stream, arg32);
-        case GNNOPS_F16: return run<__half>(src, index, index_bytes, out, arg_out, B, E, K, N, reduce, init_from_out, workspace, stream, arg32);
-        case GNNOPS_BF16: return run<__hip_bfloat16>(src, index, index_bytes, out, arg_out, B, E, K, N, reduce, init_from_out, workspace, stream, arg32);
-    }
-    gnnops_set_error("scatter_elementwise: unknown dtype %d", dtype);
-    return GNNOPS_EINVAL;
+    return gnnops_with_dtype(dtype, "scatter_elementwise", [&](auto t) {
+        return run<typename decltype(t)::type>(src, index, index_bytes, out, arg_out, B, E, K, N, reduce, init_from_out, workspace, stream, arg32);
+    });
 }
 
 namespace {

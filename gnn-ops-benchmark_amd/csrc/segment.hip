@@ -12,6 +12,7 @@
 // Algorithmic bytes per destination row: deg*K*s (src) + deg*8 (index) + K*s (out)
 // [+ K*8 arg_out]. Extra real traffic: rowptr 4 B/row and perm 4 B/edge instead of the 8-B index.
 #include "common.h"
+#include "dispatch.h"
 #include <stdlib.h>
 #include "hub.h"
 
@@ -314,8 +315,7 @@ int launch_seg(const void* src, const int32_t* rowptr, const int32_t* perm, void
     }
     if (K % VEC == 0 && aligned) {
         const int64_t vecs = K / VEC;  // 16-B lanes per row
-        int gshift = 0;
-        while ((1 << gshift) < vecs && gshift < 6) ++gshift;
+        const int gshift = gnnops_group_shift(vecs);
         const int G = 1 << gshift;
         const int kchunks = (int)gnnops_cdiv(vecs, G);
         const int64_t items = B * kchunks * N;
@@ -389,11 +389,8 @@ extern "C" int gnnops_segment_reduce_hubs(const void* src, const int32_t* rowptr
                    "segment_reduce: mean cannot start from out");
     if (B * N * K == 0) return GNNOPS_OK;
     GNNOPS_REQUIRE(rowptr && out && (E == 0 || src), GNNOPS_EINVAL, "segment_reduce: null pointer");
-    switch (dtype) {
-        case GNNOPS_F32: return dispatch_reduce<float>(reduce, src, rowptr, perm, out, arg_out, B, E, K, N, init_from_out, stream, hub_workspace, hub_workspace_bytes);
-        case GNNOPS_F16: return dispatch_reduce<__half>(reduce, src, rowptr, perm, out, arg_out, B, E, K, N, init_from_out, stream, hub_workspace, hub_workspace_bytes);
-        case GNNOPS_BF16: return dispatch_reduce<__hip_bfloat16>(reduce, src, rowptr, perm, out, arg_out, B, E, K, N, init_from_out, stream, hub_workspace, hub_workspace_bytes);
-    }
-    gnnops_set_error("segment_reduce: unknown dtype %d", dtype);
-    return GNNOPS_EINVAL;
+    return gnnops_with_dtype(dtype, "segment_reduce", [&](auto t) {
+        return dispatch_reduce<typename decltype(t)::type>(reduce, src, rowptr, perm, out, arg_out, B, E, K, N, init_from_out, stream,
+                                                           hub_workspace, hub_workspace_bytes);
+    });
 }

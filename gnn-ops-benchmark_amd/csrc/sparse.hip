@@ -9,6 +9,7 @@
 // data dependent: outputs are sized nnz and the count is left in device memory for the caller.
 // All phases are HBM-bound index work (8-16 B per entry per pass).
 #include "common.h"
+#include "dispatch.h"
 #include <stdlib.h>
 #include "sort_engine.h"
 
@@ -438,27 +439,14 @@ extern "C" int gnnops_coalesce(const int64_t* row, const int64_t* col, const voi
     if (rc) return rc;
     if (value && C > 0) {
         const int grid = grid_for(nnz * C);
-        switch (dtype) {
-            case GNNOPS_F32:
-                if (carry_values)
-                    hipLaunchKernelGGL((reduce_runs_kernel<float>), dim3(grid), dim3(256), 0, stream, (const float*)vin,
-                                       (const uint32_t*)nullptr, seg_start, d_count, (float*)out_value, nnz, C);
-                else
-                    hipLaunchKernelGGL((reduce_runs_kernel<float>), dim3(grid), dim3(256), 0, stream, (const float*)value,
-                                       vin, seg_start, d_count, (float*)out_value, nnz, C);
-                break;
-            case GNNOPS_F16:
-                hipLaunchKernelGGL((reduce_runs_kernel<__half>), dim3(grid), dim3(256), 0, stream, (const __half*)value, vin,
-                                   seg_start, d_count, (__half*)out_value, nnz, C);
-                break;
-            case GNNOPS_BF16:
-                hipLaunchKernelGGL((reduce_runs_kernel<__hip_bfloat16>), dim3(grid), dim3(256), 0, stream,
-                                   (const __hip_bfloat16*)value, vin, seg_start, d_count, (__hip_bfloat16*)out_value, nnz, C);
-                break;
-            default:
-                gnnops_set_error("coalesce: unknown dtype %d", dtype);
-                return GNNOPS_EINVAL;
-        }
+        // carry_values (fp32 only): the sorted payload IS the values, no permutation to follow
+        const int rv = gnnops_with_dtype(dtype, "coalesce", [&](auto t) {
+            using V = typename decltype(t)::type;
+            hipLaunchKernelGGL((reduce_runs_kernel<V>), dim3(grid), dim3(256), 0, stream, (const V*)(carry_values ? (const void*)vin : value),
+                               carry_values ? (const uint32_t*)nullptr : vin, seg_start, d_count, (V*)out_value, nnz, C);
+            return (int)GNNOPS_OK;
+        });
+        if (rv != GNNOPS_OK) return rv;
     }
     return gnnops_check_launch("coalesce");
 }

@@ -38,6 +38,7 @@
 // wave: 8 B per slot + 1 KiB of histogram. Three classes by the call's largest row count: up to 256 / 1024 / 2048 entries = 512 /
 // 2048 / 4096 slots per wave = 20 / 68 / 132 KiB per workgroup of 4 waves = 8 / 2 / 1 workgroups = 32 / 8 / 4 waves per CU.
 #include "common.h"
+#include "dispatch.h"
 #include "lds_sort.h"
 
 namespace {
@@ -681,19 +682,11 @@ extern "C" int gnnops_spgemm_numeric(const int32_t* rowptrA, const int32_t* perm
     const int64_t* rowlo = (const int64_t*)(ws + L.rowlo);
     const uint32_t* rowspan = (const uint32_t*)(ws + L.rowspan);
     const int64_t* rowptrC = (const int64_t*)(ws + L.rowptr);
-#define NUMERIC(V)                                                                                                                   \
-    (max_span <= SMALL_SPAN                                                                                                          \
-         ? launch_numeric<V, SMALL_SPAN>(stream, rowptrA, permA, colA, valA, m, rowptrB, permB, colB, valB, rowlo, rowspan, rowptrC,  \
-                                         out_row, out_col, out_val)                                                                  \
-         : launch_numeric<V, MAX_SPAN>(stream, rowptrA, permA, colA, valA, m, rowptrB, permB, colB, valB, rowlo, rowspan, rowptrC,    \
-                                       out_row, out_col, out_val))
-    switch (dtype) {
-        case GNNOPS_F32: return NUMERIC(float);
-        case GNNOPS_F16: return NUMERIC(__half);
-        case GNNOPS_BF16: return NUMERIC(__hip_bfloat16);
-        default: gnnops_set_error("spgemm_numeric: unknown dtype %d", dtype); return GNNOPS_EINVAL;
-    }
-#undef NUMERIC
+    return gnnops_with_dtype(dtype, "spgemm_numeric", [&](auto t) {
+        using V = typename decltype(t)::type;
+        auto* numeric = max_span <= SMALL_SPAN ? launch_numeric<V, SMALL_SPAN> : launch_numeric<V, MAX_SPAN>;
+        return numeric(stream, rowptrA, permA, colA, valA, m, rowptrB, permB, colB, valB, rowlo, rowspan, rowptrC, out_row, out_col, out_val);
+    });
 }
 
 // ---- the hashed route: same phases, same workspace, same arguments ----
@@ -755,17 +748,12 @@ extern "C" int gnnops_spgemm_hash_numeric(const int32_t* rowptrA, const int32_t*
     const uint32_t* rowcnt = (const uint32_t*)(ws + L.rowcnt);
     const uint32_t* rowspan = (const uint32_t*)(ws + L.rowspan);
     const int64_t* rowptrC = (const int64_t*)(ws + L.rowptr);
-#define NUMERIC_ARGS stream, rowptrA, permA, colA, valA, m, rowptrB, permB, colB, valB, rowlo, rowcnt, rowspan, rowptrC, out_row, out_col, out_val
-#define NUMERIC(V)                                                                      \
-    (2 * max_row <= HASH_SLOTS_S   ? launch_hash_numeric<V, HASH_SLOTS_S>(NUMERIC_ARGS) \
-     : 2 * max_row <= HASH_SLOTS_M ? launch_hash_numeric<V, HASH_SLOTS_M>(NUMERIC_ARGS) \
-                                   : launch_hash_numeric<V, HASH_SLOTS_L>(NUMERIC_ARGS))
-    switch (dtype) {
-        case GNNOPS_F32: return NUMERIC(float);
-        case GNNOPS_F16: return NUMERIC(__half);
-        case GNNOPS_BF16: return NUMERIC(__hip_bfloat16);
-        default: gnnops_set_error("spgemm_hash_numeric: unknown dtype %d", dtype); return GNNOPS_EINVAL;
-    }
-#undef NUMERIC
-#undef NUMERIC_ARGS
+    return gnnops_with_dtype(dtype, "spgemm_hash_numeric", [&](auto t) {
+        using V = typename decltype(t)::type;
+        auto* numeric = 2 * max_row <= HASH_SLOTS_S   ? launch_hash_numeric<V, HASH_SLOTS_S>
+                        : 2 * max_row <= HASH_SLOTS_M ? launch_hash_numeric<V, HASH_SLOTS_M>
+                                                      : launch_hash_numeric<V, HASH_SLOTS_L>;
+        return numeric(stream, rowptrA, permA, colA, valA, m, rowptrB, permB, colB, valB, rowlo, rowcnt, rowspan, rowptrC, out_row, out_col,
+                       out_val);
+    });
 }

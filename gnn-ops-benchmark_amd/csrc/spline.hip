@@ -21,6 +21,7 @@
 // of weight matrices, there is no shared operand tile to put on the matrix cores without first sorting E * S products by
 // kernel index.
 #include "common.h"
+#include "dispatch.h"
 #include "spline_common.h"
 
 namespace {
@@ -144,13 +145,9 @@ extern "C" int gnnops_spline_basis(const void* pseudo, const int64_t* kernel_siz
     GNNOPS_REQUIRE(E >= 0, GNNOPS_EINVAL, "spline_basis: negative size");
     if (E == 0) return GNNOPS_OK;
     GNNOPS_REQUIRE(pseudo && basis && weight_index, GNNOPS_EINVAL, "spline_basis: null pointer");
-    switch (dtype) {
-        case GNNOPS_F32: return run_basis<float>(pseudo, sm, E, basis, weight_index, (hipStream_t)s);
-        case GNNOPS_F16: return run_basis<__half>(pseudo, sm, E, basis, weight_index, (hipStream_t)s);
-        case GNNOPS_BF16: return run_basis<__hip_bfloat16>(pseudo, sm, E, basis, weight_index, (hipStream_t)s);
-    }
-    gnnops_set_error("spline_basis: unknown dtype %d", dtype);
-    return GNNOPS_EINVAL;
+    return gnnops_with_dtype(dtype, "spline_basis", [&](auto t) {
+        return run_basis<typename decltype(t)::type>(pseudo, sm, E, basis, weight_index, (hipStream_t)s);
+    });
 }
 
 extern "C" int gnnops_spline_weighting(const void* x, const void* weight, const void* basis, const int64_t* weight_index, void* out,
@@ -162,17 +159,12 @@ extern "C" int gnnops_spline_weighting(const void* x, const void* weight, const 
     const int ochunks = (int)((Mout + 63) / 64);
     const int grid = gnnops_grid_cap(gnnops_cdiv(E * ochunks, 4), 256 * 32);
     hipStream_t stream = (hipStream_t)s;
-#define GNNOPS_SW(T)                                                                                                        \
-    hipLaunchKernelGGL((spline_weighting_kernel<T>), dim3(grid), dim3(256), 0, stream, (const T*)x, (const T*)weight,       \
-                       (const T*)basis, weight_index, (T*)out, E, (int)Min, (int)Mout, (int)S, ochunks)
-    switch (dtype) {
-        case GNNOPS_F32: GNNOPS_SW(float); break;
-        case GNNOPS_F16: GNNOPS_SW(__half); break;
-        case GNNOPS_BF16: GNNOPS_SW(__hip_bfloat16); break;
-        default: gnnops_set_error("spline_weighting: unknown dtype %d", dtype); return GNNOPS_EINVAL;
-    }
-#undef GNNOPS_SW
-    return gnnops_check_launch("spline_weighting");
+    return gnnops_with_dtype(dtype, "spline_weighting", [&](auto t) {
+        using T = typename decltype(t)::type;
+        hipLaunchKernelGGL((spline_weighting_kernel<T>), dim3(grid), dim3(256), 0, stream, (const T*)x, (const T*)weight, (const T*)basis,
+                           weight_index, (T*)out, E, (int)Min, (int)Mout, (int)S, ochunks);
+        return gnnops_check_launch("spline_weighting");
+    });
 }
 
 extern "C" int gnnops_spline_conv(const void* x, const int32_t* rowptr, const int32_t* perm, const int64_t* src, const void* pseudo,
@@ -187,11 +179,8 @@ extern "C" int gnnops_spline_conv(const void* x, const int32_t* rowptr, const in
     if (N * Mout == 0) return GNNOPS_OK;
     GNNOPS_REQUIRE(rowptr && out && (E == 0 || (x && src && pseudo && weight)), GNNOPS_EINVAL, "spline_conv: null pointer");
     hipStream_t stream = (hipStream_t)s;
-    switch (dtype) {
-        case GNNOPS_F32: return run_conv<float>(x, rowptr, perm, src, pseudo, weight, sm, root_weight, bias, out, N, (int)Min, (int)Mout, norm, stream);
-        case GNNOPS_F16: return run_conv<__half>(x, rowptr, perm, src, pseudo, weight, sm, root_weight, bias, out, N, (int)Min, (int)Mout, norm, stream);
-        case GNNOPS_BF16: return run_conv<__hip_bfloat16>(x, rowptr, perm, src, pseudo, weight, sm, root_weight, bias, out, N, (int)Min, (int)Mout, norm, stream);
-    }
-    gnnops_set_error("spline_conv: unknown dtype %d", dtype);
-    return GNNOPS_EINVAL;
+    return gnnops_with_dtype(dtype, "spline_conv", [&](auto t) {
+        return run_conv<typename decltype(t)::type>(x, rowptr, perm, src, pseudo, weight, sm, root_weight, bias, out, N, (int)Min, (int)Mout, norm,
+                                                    stream);
+    });
 }

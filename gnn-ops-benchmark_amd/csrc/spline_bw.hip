@@ -22,6 +22,7 @@
 // a group's partials in ascending chunk order. That pass also writes the exact zeros of the empty kernels. No atomics:
 // two calls on the same inputs give the same bits.
 #include "common.h"
+#include "dispatch.h"
 #include "hub.h"
 #include "spline_common.h"
 
@@ -302,13 +303,9 @@ extern "C" int gnnops_spline_basis_bw(const void* grad_basis, const void* pseudo
     GNNOPS_REQUIRE(E >= 0, GNNOPS_EINVAL, "spline_basis_bw: negative size");
     if (E == 0) return GNNOPS_OK;
     GNNOPS_REQUIRE(grad_basis && pseudo && grad_pseudo, GNNOPS_EINVAL, "spline_basis_bw: null pointer");
-    switch (dtype) {
-        case GNNOPS_F32: return run_basis_bw<float>(grad_basis, pseudo, sm, E, grad_pseudo, (hipStream_t)s);
-        case GNNOPS_F16: return run_basis_bw<__half>(grad_basis, pseudo, sm, E, grad_pseudo, (hipStream_t)s);
-        case GNNOPS_BF16: return run_basis_bw<__hip_bfloat16>(grad_basis, pseudo, sm, E, grad_pseudo, (hipStream_t)s);
-    }
-    gnnops_set_error("spline_basis_bw: unknown dtype %d", dtype);
-    return GNNOPS_EINVAL;
+    return gnnops_with_dtype(dtype, "spline_basis_bw", [&](auto t) {
+        return run_basis_bw<typename decltype(t)::type>(grad_basis, pseudo, sm, E, grad_pseudo, (hipStream_t)s);
+    });
 }
 
 extern "C" int gnnops_spline_weighting_bw_basis(const void* grad_out, const void* x, const void* weight, const int64_t* weight_index,
@@ -321,17 +318,12 @@ extern "C" int gnnops_spline_weighting_bw_basis(const void* grad_out, const void
                    "spline_weighting_bw_basis: null pointer");
     const int grid = gnnops_grid_cap(gnnops_cdiv(E, 4), 256 * 32);
     hipStream_t stream = (hipStream_t)s;
-#define GNNOPS_WB(T)                                                                                                             \
-    hipLaunchKernelGGL((bw_basis_kernel<T>), dim3(grid), dim3(256), 0, stream, (const T*)grad_out, (const T*)x, (const T*)weight, \
-                       weight_index, x_rows, g_rows, (T*)grad_basis, E, (int)Min, (int)Mout, (int)S)
-    switch (dtype) {
-        case GNNOPS_F32: GNNOPS_WB(float); break;
-        case GNNOPS_F16: GNNOPS_WB(__half); break;
-        case GNNOPS_BF16: GNNOPS_WB(__hip_bfloat16); break;
-        default: gnnops_set_error("spline_weighting_bw_basis: unknown dtype %d", dtype); return GNNOPS_EINVAL;
-    }
-#undef GNNOPS_WB
-    return gnnops_check_launch("spline_weighting_bw_basis");
+    return gnnops_with_dtype(dtype, "spline_weighting_bw_basis", [&](auto t) {
+        using T = typename decltype(t)::type;
+        hipLaunchKernelGGL((bw_basis_kernel<T>), dim3(grid), dim3(256), 0, stream, (const T*)grad_out, (const T*)x, (const T*)weight,
+                           weight_index, x_rows, g_rows, (T*)grad_basis, E, (int)Min, (int)Mout, (int)S);
+        return gnnops_check_launch("spline_weighting_bw_basis");
+    });
 }
 
 extern "C" size_t gnnops_spline_weighting_bw_weight_workspace_bytes(int64_t E, int64_t S, int64_t Min, int64_t Mout) {
@@ -356,11 +348,8 @@ extern "C" int gnnops_spline_weighting_bw_weight(const void* grad_out, const voi
     GNNOPS_REQUIRE(((uintptr_t)workspace & 3) == 0, GNNOPS_EINVAL, "spline_weighting_bw_weight: workspace must be 4-byte aligned");
     hipStream_t stream = (hipStream_t)s;
     float* partial = (float*)workspace;
-    switch (dtype) {
-        case GNNOPS_F32: return run_bw_weight<float>(grad_out, x, basis, rowptr, perm, x_rows, g_rows, grad_weight, P, K, (int)Min, (int)Mout, (int)S, partial, stream);
-        case GNNOPS_F16: return run_bw_weight<__half>(grad_out, x, basis, rowptr, perm, x_rows, g_rows, grad_weight, P, K, (int)Min, (int)Mout, (int)S, partial, stream);
-        case GNNOPS_BF16: return run_bw_weight<__hip_bfloat16>(grad_out, x, basis, rowptr, perm, x_rows, g_rows, grad_weight, P, K, (int)Min, (int)Mout, (int)S, partial, stream);
-    }
-    gnnops_set_error("spline_weighting_bw_weight: unknown dtype %d", dtype);
-    return GNNOPS_EINVAL;
+    return gnnops_with_dtype(dtype, "spline_weighting_bw_weight", [&](auto t) {
+        return run_bw_weight<typename decltype(t)::type>(grad_out, x, basis, rowptr, perm, x_rows, g_rows, grad_weight, P, K, (int)Min, (int)Mout,
+                                                         (int)S, partial, stream);
+    });
 }

@@ -14,6 +14,7 @@
 // roundings torch's `matrix[col] * value` followed by scatter_add perform; no FMA contraction.
 // 16-bit inputs: v*x is exact in fp32, acc in fp32, rounded once to the storage type.
 #include "common.h"
+#include "dispatch.h"
 #include "hub.h"
 
 namespace {
@@ -288,8 +289,7 @@ int launch(const int32_t* rowptr, const int32_t* perm, const int64_t* col, const
     constexpr int VEC = Elem<T>::VEC;
     if (D % VEC == 0 && (uintptr_t)mat % 16 == 0 && (uintptr_t)out % 16 == 0) {
         const int64_t vecs = D / VEC;
-        int gshift = 0;
-        while ((1 << gshift) < vecs && gshift < 6) ++gshift;
+        const int gshift = gnnops_group_shift(vecs);
         const int kchunks = (int)gnnops_cdiv(vecs, (int64_t)1 << gshift);
         const int grid = gnnops_grid_cap(gnnops_cdiv((int64_t)kchunks * M, 256 >> gshift), 256 * 64);
         // a dense operand far beyond the 256 MiB Infinity Cache is streamed nontemporally (its rows would only evict
@@ -344,13 +344,10 @@ extern "C" int gnnops_spmm_hubs(const int32_t* rowptr, const int32_t* perm, cons
     GNNOPS_REQUIRE(nnz < ((int64_t)1 << 31), GNNOPS_EUNSUPPORTED, "spmm: nnz must be < 2^31");
     if (M * D == 0) return GNNOPS_OK;
     GNNOPS_REQUIRE(rowptr && out && (nnz == 0 || (col && mat)), GNNOPS_EINVAL, "spmm: null pointer");
-    switch (dtype) {
-        case GNNOPS_F32: return launch<float>(rowptr, perm, col, value, mat, out, M, D, mat_rows, stream, nnz, hub_workspace, hub_workspace_bytes);
-        case GNNOPS_F16: return launch<__half>(rowptr, perm, col, value, mat, out, M, D, mat_rows, stream, nnz, hub_workspace, hub_workspace_bytes);
-        case GNNOPS_BF16: return launch<__hip_bfloat16>(rowptr, perm, col, value, mat, out, M, D, mat_rows, stream, nnz, hub_workspace, hub_workspace_bytes);
-    }
-    gnnops_set_error("spmm: unknown dtype %d", dtype);
-    return GNNOPS_EINVAL;
+    return gnnops_with_dtype(dtype, "spmm", [&](auto t) {
+        return launch<typename decltype(t)::type>(rowptr, perm, col, value, mat, out, M, D, mat_rows, stream, nnz, hub_workspace,
+                                                  hub_workspace_bytes);
+    });
 }
 
 // CSR x dense through a tile plan (include/gnnops.h): bit-identical to gnnops_spmm(rowptr, NULL, col, ...).
@@ -369,13 +366,9 @@ extern "C" int gnnops_spmm_tiled(const int32_t* rowptr, const int64_t* col, cons
     GNNOPS_REQUIRE(rowptr && out && tile_ptr && (nnz == 0 || (col && mat && slot)), GNNOPS_EINVAL, "spmm_tiled: null pointer");
     int rshift = 0;
     while ((1 << rshift) < block_rows) ++rshift;
-    switch (dtype) {
-        case GNNOPS_F32: return launch_tiled<float>(rowptr, col, value, mat, out, M, D, tile_ptr, tile_cols, slot, rshift, slots, stream);
-        case GNNOPS_F16: return launch_tiled<__half>(rowptr, col, value, mat, out, M, D, tile_ptr, tile_cols, slot, rshift, slots, stream);
-        case GNNOPS_BF16: return launch_tiled<__hip_bfloat16>(rowptr, col, value, mat, out, M, D, tile_ptr, tile_cols, slot, rshift, slots, stream);
-    }
-    gnnops_set_error("spmm_tiled: unknown dtype %d", dtype);
-    return GNNOPS_EINVAL;
+    return gnnops_with_dtype(dtype, "spmm_tiled", [&](auto t) {
+        return launch_tiled<typename decltype(t)::type>(rowptr, col, value, mat, out, M, D, tile_ptr, tile_cols, slot, rshift, slots, stream);
+    });
 }
 
 // out[j] = in[perm[j]], elements of 2, 4 or 8 bytes: turns (plan, COO columns / values) into CSR arrays once, so the

@@ -24,6 +24,7 @@
 // gnnops_spmm_reduce_grad_terms is the per-output-element half of the min / max backward: the three tensors that the two
 // deterministic scatter-adds of gnnops/autograd.py (_SpMMReduce) then sum by destination.
 #include "common.h"
+#include "dispatch.h"
 
 namespace {
 
@@ -160,8 +161,7 @@ int launch_reduce(const int32_t* rowptr, const int32_t* perm, const int64_t* col
     constexpr int VEC = Elem<T>::VEC;
     if (D % VEC == 0 && (uintptr_t)mat % 16 == 0 && (uintptr_t)out % 16 == 0 && (uintptr_t)arg % 16 == 0) {
         const int64_t vecs = D / VEC;
-        int gshift = 0;
-        while ((1 << gshift) < vecs && gshift < 6) ++gshift;
+        const int gshift = gnnops_group_shift(vecs);
         const int kchunks = (int)gnnops_cdiv(vecs, (int64_t)1 << gshift);
         const int grid = gnnops_grid_cap(gnnops_cdiv((int64_t)kchunks * M, 256 >> gshift), 256 * 64);
         // as in spmm.hip: a dense operand far beyond the Infinity Cache is streamed nontemporally
@@ -245,13 +245,9 @@ extern "C" int gnnops_spmm_reduce(const int32_t* rowptr, const int32_t* perm, co
     GNNOPS_REQUIRE(nnz < ((int64_t)1 << 31) - U, GNNOPS_EUNSUPPORTED, "spmm_reduce: nnz must be < 2^31 - 8");
     if (M * D == 0) return GNNOPS_OK;
     GNNOPS_REQUIRE(rowptr && out && (nnz == 0 || (col && mat)), GNNOPS_EINVAL, "spmm_reduce: null pointer");
-    switch (dtype) {
-        case GNNOPS_F32: return launch_dtype<float>(rowptr, perm, col, value, mat, out, arg, M, D, nnz, mat_rows, reduce, stream);
-        case GNNOPS_F16: return launch_dtype<__half>(rowptr, perm, col, value, mat, out, arg, M, D, nnz, mat_rows, reduce, stream);
-        case GNNOPS_BF16: return launch_dtype<__hip_bfloat16>(rowptr, perm, col, value, mat, out, arg, M, D, nnz, mat_rows, reduce, stream);
-    }
-    gnnops_set_error("spmm_reduce: unknown dtype %d", dtype);
-    return GNNOPS_EINVAL;
+    return gnnops_with_dtype(dtype, "spmm_reduce", [&](auto t) {
+        return launch_dtype<typename decltype(t)::type>(rowptr, perm, col, value, mat, out, arg, M, D, nnz, mat_rows, reduce, stream);
+    });
 }
 
 extern "C" int gnnops_spmm_reduce_grad_terms(const int64_t* arg, const void* g, const int32_t* perm, const int64_t* col,
@@ -261,11 +257,7 @@ extern "C" int gnnops_spmm_reduce_grad_terms(const int64_t* arg, const void* g, 
     GNNOPS_REQUIRE(M >= 0 && D >= 0 && nnz >= 0 && mat_rows >= 0, GNNOPS_EINVAL, "spmm_reduce_grad_terms: negative size");
     if (M * D == 0) return GNNOPS_OK;
     GNNOPS_REQUIRE(arg && g && dst && to_mat && (nnz == 0 || (col && mat)), GNNOPS_EINVAL, "spmm_reduce_grad_terms: null pointer");
-    switch (dtype) {
-        case GNNOPS_F32: return launch_grad_terms<float>(arg, g, perm, col, value, mat, dst, to_mat, to_val, M, D, nnz, mat_rows, stream);
-        case GNNOPS_F16: return launch_grad_terms<__half>(arg, g, perm, col, value, mat, dst, to_mat, to_val, M, D, nnz, mat_rows, stream);
-        case GNNOPS_BF16: return launch_grad_terms<__hip_bfloat16>(arg, g, perm, col, value, mat, dst, to_mat, to_val, M, D, nnz, mat_rows, stream);
-    }
-    gnnops_set_error("spmm_reduce_grad_terms: unknown dtype %d", dtype);
-    return GNNOPS_EINVAL;
+    return gnnops_with_dtype(dtype, "spmm_reduce_grad_terms", [&](auto t) {
+        return launch_grad_terms<typename decltype(t)::type>(arg, g, perm, col, value, mat, dst, to_mat, to_val, M, D, nnz, mat_rows, stream);
+    });
 }

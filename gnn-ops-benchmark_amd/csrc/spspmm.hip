@@ -11,6 +11,7 @@
 //            expansion order (fp32) -> coalesced COO, bit-reproducible
 // Index-heavy and HBM-bound; nothing here is a dense contraction.
 #include "common.h"
+#include "dispatch.h"
 
 namespace {
 
@@ -129,15 +130,10 @@ extern "C" int gnnops_spspmm_expand(const int64_t* rowA, const int64_t* colA, co
                    GNNOPS_EINVAL, "spspmm_expand: null pointer");
     const int nb = (int)gnnops_cdiv(nnzA, T);
     const uint32_t* block_off = (const uint32_t*)workspace;
-#define EXPAND(V)                                                                                                     \
-    hipLaunchKernelGGL((expand_kernel<V>), dim3(nb), dim3(T), 0, stream, rowA, colA, (const V*)valA, nnzA, rowptrB,   \
-                       permB, colB, (const V*)valB, block_off, out_row, out_col, (V*)out_val)
-    switch (dtype) {
-        case GNNOPS_F32: EXPAND(float); break;
-        case GNNOPS_F16: EXPAND(__half); break;
-        case GNNOPS_BF16: EXPAND(__hip_bfloat16); break;
-        default: gnnops_set_error("spspmm_expand: unknown dtype %d", dtype); return GNNOPS_EINVAL;
-    }
-#undef EXPAND
-    return gnnops_check_launch("spspmm_expand");
+    return gnnops_with_dtype(dtype, "spspmm_expand", [&](auto t) {
+        using V = typename decltype(t)::type;
+        hipLaunchKernelGGL((expand_kernel<V>), dim3(nb), dim3(T), 0, stream, rowA, colA, (const V*)valA, nnzA, rowptrB, permB, colB,
+                           (const V*)valB, block_off, out_row, out_col, (V*)out_val);
+        return gnnops_check_launch("spspmm_expand");
+    });
 }

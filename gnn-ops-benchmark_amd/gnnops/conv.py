@@ -42,7 +42,7 @@ import torch
 
 from . import _lib, ops
 from ._lib import check
-from .ops import _dtype_code, _on, _require_gpu, _stream, get_plan
+from .ops import _dtype_code, _hub_workspace, _on, _ptr, _require_gpu, _stream, get_plan
 from .sparse import _coo_rows_cols, _csr_arrays
 
 FUNCTORS = {"copy": 0, "add": 1, "cgconv": 2, "film": 3}
@@ -119,15 +119,14 @@ def edge_reduce(functor, q, edge_index, num_dst, p=None, w=None, add=None, aggr=
         col, _ = _csr_arrays(plan, src_rows, None, owner=edge_index, tag=1 if flip else 0)
     c_aggr = (ctypes.c_int * len(aggr_ids))(*aggr_ids)
     c_scal = (ctypes.c_int * max(len(scal_ids), 1))(*scal_ids)
-    ptr = lambda t: t.data_ptr() if t is not None else None   # noqa: E731
     L = _lib.load()
-    hub_bytes = L.gnnops_edge_reduce_hub_workspace_bytes(E, K)   # destinations with more than 8192 edges: reduced piecewise
-    hub_ws = torch.empty(hub_bytes, dtype=torch.uint8, device=q.device) if hub_bytes else None
+    # destinations with more than 8192 edges: reduced piecewise
+    hub_ws, hub_ptr, hub_bytes = _hub_workspace(L.gnnops_edge_reduce_hub_workspace_bytes(E, K), q.device)
     with _on(q.device):
-        rc = L.gnnops_edge_reduce_hubs(FUNCTORS[functor], ptr(q), ldq, ptr(p), ldp, ptr(w), ldw, ptr(add), ldadd,
+        rc = L.gnnops_edge_reduce_hubs(FUNCTORS[functor], _ptr(q), ldq, _ptr(p), ldp, _ptr(w), ldw, _ptr(add), ldadd,
                                        plan.rowptr.data_ptr(), plan.perm.data_ptr(), col.data_ptr(), out.data_ptr(), ldo,
                                        num_dst, E, K, c_aggr, len(aggr_ids), c_scal, len(scal_ids), avg_log, avg_lin, dt,
-                                       ptr(hub_ws), hub_bytes, _stream())
+                                       hub_ptr, hub_bytes, _stream())
     check(rc, "edge_reduce")
     return out
 
@@ -183,10 +182,9 @@ class _EdgeReduce(torch.autograd.Function):
         g, ldg = _rows(g, "the output gradient", 1, K)     # one expanded row (out.sum().backward()) has stride 0
         gp = torch.empty((E, 2 * K), dtype=g.dtype, device=g.device)
         gq = torch.empty((E, K), dtype=g.dtype, device=g.device) if ctx.functor == "film" else None
-        ptr = lambda t: t.data_ptr() if t is not None else None   # noqa: E731
         with _on(g.device):
-            check(_lib.load().gnnops_edge_grad(FUNCTORS[ctx.functor], ptr(p_), ldp, ptr(q_), ldq, ptr(w_), ldw, g.data_ptr(), ldg,
-                                               src_rows.data_ptr(), dst_rows.data_ptr(), gp.data_ptr(), ptr(gq), E, K,
+            check(_lib.load().gnnops_edge_grad(FUNCTORS[ctx.functor], _ptr(p_), ldp, _ptr(q_), ldq, _ptr(w_), ldw, g.data_ptr(), ldg,
+                                               src_rows.data_ptr(), dst_rows.data_ptr(), gp.data_ptr(), _ptr(gq), E, K,
                                                _dtype_code(g, "edge_grad"), _stream()), "edge_grad")
         if need_p:
             d_p = ops.scatter(gp, plan_dst, 0, None, None, "sum")
@@ -267,11 +265,10 @@ class _EdgeAggregate(torch.autograd.Function):
         c_aggr = (ctypes.c_int * len(aggr_ids))(*aggr_ids)
         c_scal = (ctypes.c_int * max(len(scal_ids), 1))(*scal_ids)
         avg_log, avg_lin = (1.0, 1.0) if avg_deg is None else (float(avg_deg["log"]), float(avg_deg["lin"]))
-        ptr = lambda t: t.data_ptr() if t is not None else None   # noqa: E731
         with _on(q.device):
-            check(_lib.load().gnnops_edge_multi_grad(FUNCTORS[functor], q.data_ptr(), ldq, ptr(p), ldp, ptr(w), ldw, g.data_ptr(), ldg,
+            check(_lib.load().gnnops_edge_multi_grad(FUNCTORS[functor], q.data_ptr(), ldq, _ptr(p), ldp, _ptr(w), ldw, g.data_ptr(), ldg,
                                                      plan.rowptr.data_ptr(), plan.perm.data_ptr(), col.data_ptr(), gm.data_ptr(),
-                                                     ptr(d_p), num_dst, E, K, c_aggr, len(aggr_ids), c_scal, len(scal_ids), avg_log,
+                                                     _ptr(d_p), num_dst, E, K, c_aggr, len(aggr_ids), c_scal, len(scal_ids), avg_log,
                                                      avg_lin, _dtype_code(q, "edge_aggregate"), _stream()), "edge_multi_grad")
         pad = lambda d, t: d if t.size(1) == K else torch.nn.functional.pad(d, (0, t.size(1) - K))   # noqa: E731  (column blocks wider than K)
         d_q = None
@@ -977,10 +974,6 @@ def _norm_operands(a, heads, bias, scale, norm_weight, norm_bias):
             raise RuntimeError(f"{op}: scale must be [{a.size(0)}, {C}] of a's dtype")
         scale = scale.contiguous()
     return a, lda, vecs[0], scale, vecs[1], vecs[2], HC, C
-
-
-def _ptr(t):
-    return None if t is None else t.data_ptr()
 
 
 def _norm_forward(a, heads, bias, relu, scale, norm_weight, norm_bias, eps, want_stats):

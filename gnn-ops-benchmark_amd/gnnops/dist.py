@@ -105,7 +105,7 @@ class HipLocal:
         import ctypes
 
         from . import _lib
-        from .ops import _on, _stream, check, index_select
+        from .ops import _hub_workspace, _on, _stream, check, index_select
         from .sparse import sort
 
         src, index, ws = state
@@ -135,12 +135,12 @@ class HipLocal:
             slab = out if out is not None else torch.empty((n_loc, D), dtype=src.dtype, device=dev)
             if ws is None:
                 return slab.zero_()
-            hub_bytes = L.gnnops_hub_workspace_bytes(E, D, _lib.SUM)   # heavy destinations: csrc/hub.h
-            hub_ws = torch.empty(hub_bytes, dtype=torch.uint8, device=dev) if hub_bytes else None
+            # heavy destinations: csrc/hub.h
+            hub_ws, hub_ptr, hub_bytes = _hub_workspace(L.gnnops_hub_workspace_bytes(E, D, _lib.SUM), dev)
             with _on(dev):
                 check(L.gnnops_bucket_reduce_hubs(src.data_ptr(), ws.data_ptr(), slab.data_ptr(), None, E, D, n_loc, _lib.F32,
-                                                  _lib.SUM, 0, hub_ws.data_ptr() if hub_ws is not None else None, hub_bytes,
-                                                  _stream()), "bucket_reduce")
+                                                  _lib.SUM, 0, hub_ptr, hub_bytes, _stream()),
+                      "bucket_reduce")
             return slab
 
         return own, send_ids, send_rows
@@ -250,20 +250,20 @@ class HipLocal:
         """out[i] = reduce over src[perm[crow[i] : crow[i+1]]] (crow int32: absolute positions into perm); ``arg`` (min /
         max) receives the position in src of each extremum."""
         from . import _lib
-        from .ops import REDUCE_CODE, _dtype_code, _on, _stream, check
+        from .ops import REDUCE_CODE, _dtype_code, _hub_workspace, _on, _stream, check
 
         if n_rows == 0:
             return
         E, D = src.shape
         L = _lib.load()
         rcode = REDUCE_CODE["sum" if reduce == "add" else reduce]
-        hub_bytes = L.gnnops_hub_workspace_bytes(E, D, rcode)   # heavy destinations: csrc/hub.h
-        hub_ws = torch.empty(hub_bytes, dtype=torch.uint8, device=src.device) if hub_bytes else None
+        # heavy destinations: csrc/hub.h
+        hub_ws, hub_ptr, hub_bytes = _hub_workspace(L.gnnops_hub_workspace_bytes(E, D, rcode), src.device)
         with _on(src.device):
             check(L.gnnops_segment_reduce_hubs(src.data_ptr(), crow.data_ptr(), perm.data_ptr(), out.data_ptr(),
                                                arg.data_ptr() if arg is not None else None, 1,
                                                E, D, n_rows, _dtype_code(src, "sharded_scatter"), rcode, 0,
-                                               hub_ws.data_ptr() if hub_ws is not None else None, hub_bytes, _stream()),
+                                               hub_ptr, hub_bytes, _stream()),
                   "segment_reduce")
 
     def spmm_split(self, row, col, value, mat, n_total, lo, hi, counts_only=False):

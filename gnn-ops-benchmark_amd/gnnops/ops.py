@@ -59,6 +59,20 @@ def _on(device):
     return torch.cuda.device(device)
 
 
+def _ptr(t):
+    """The device pointer of a tensor; None (the C ABI's NULL) for None."""
+    return None if t is None else t.data_ptr()
+
+
+def _hub_workspace(nbytes, device):
+    """The hub workspace of an entry point (csrc/hub.h), `nbytes` as its size query answered: the tensor to keep alive until the
+    call is enqueued, its pointer or None, and the size: what the call site passes on."""
+    if not nbytes:
+        return None, None, 0
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=device)
+    return ws, ws.data_ptr(), nbytes
+
+
 def _require_gpu(*tensors):
     for t in tensors:
         if t is not None and not t.is_cuda:
@@ -545,21 +559,21 @@ def scatter(src, index, dim=-1, out=None, dim_size=None, reduce="sum"):
             ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=src.device)
             rc = L.gnnops_bucket_partition(row_index.data_ptr(), E, N, ws.data_ptr(), ws_bytes, _stream())
             if rc == _lib.OK:
-                hub_bytes = L.gnnops_hub_workspace_bytes(E, K, rcode)   # heavy destinations are reduced piecewise (hub.h)
-                hub_ws = torch.empty(hub_bytes, dtype=torch.uint8, device=src.device) if hub_bytes else None
+                # heavy destinations are reduced piecewise (hub.h)
+                hub_ws, hub_ptr, hub_bytes = _hub_workspace(L.gnnops_hub_workspace_bytes(E, K, rcode), src.device)
                 rc = L.gnnops_bucket_reduce_hubs(src.data_ptr(), ws.data_ptr(), out.data_ptr(),
                                                  arg.data_ptr() if want_arg else None, E, K, N, dt, rcode, init,
-                                                 hub_ws.data_ptr() if hub_ws is not None else None, hub_bytes, _stream())
+                                                 hub_ptr, hub_bytes, _stream())
             if rc != _lib.EUNSUPPORTED:
                 check(rc, "scatter_rows_oneshot")
                 return (out, arg) if want_arg else out
         if row_index is not None:
             plan = get_plan(row_index, N)
-            hub_bytes = L.gnnops_hub_workspace_bytes(E, K, rcode) if B == 1 else 0   # heavy destinations: hub.h
-            hub_ws = torch.empty(hub_bytes, dtype=torch.uint8, device=src.device) if hub_bytes else None
+            # heavy destinations: hub.h
+            hub_ws, hub_ptr, hub_bytes = _hub_workspace(L.gnnops_hub_workspace_bytes(E, K, rcode) if B == 1 else 0, src.device)
             rc = L.gnnops_segment_reduce_hubs(src.data_ptr(), plan.rowptr.data_ptr(), plan.perm.data_ptr(), out.data_ptr(),
                                               arg.data_ptr() if want_arg else None, B, E, K, N, dt, rcode, init,
-                                              hub_ws.data_ptr() if hub_ws is not None else None, hub_bytes, _stream())
+                                              hub_ptr, hub_bytes, _stream())
             check(rc, "segment_reduce")
         else:
             full = index if (index.shape == src.shape and index.is_contiguous()) else _broadcast_index(index, src, dim).contiguous()
@@ -681,10 +695,10 @@ def index_select(input, dim, index, plan=None):
             ws = torch.empty(ws_bytes, dtype=torch.uint8, device=input.device)
             with _on(input.device):
                 check(L.gnnops_bucket_partition(index.data_ptr(), E, N, ws.data_ptr(), ws_bytes, _stream()), "bucket_partition")
-                hub_bytes = L.gnnops_hub_workspace_bytes(E, 0, 0)   # hot rows are written by whole workgroups (hub.h)
-                hub_ws = torch.empty(hub_bytes, dtype=torch.uint8, device=input.device) if hub_bytes else None
+                # hot rows are written by whole workgroups (hub.h)
+                hub_ws, hub_ptr, hub_bytes = _hub_workspace(L.gnnops_hub_workspace_bytes(E, 0, 0), input.device)
                 check(L.gnnops_bucket_select_hubs(input.data_ptr(), ws.data_ptr(), out.data_ptr(), N, K, E, eb,
-                                                  hub_ws.data_ptr() if hub_ws is not None else None, hub_bytes, _stream()),
+                                                  hub_ptr, hub_bytes, _stream()),
                       "bucket_select")
             return out
         plan = get_plan(index, N)
@@ -692,11 +706,11 @@ def index_select(input, dim, index, plan=None):
         if plan is not None:
             if plan.E != E or plan.N != N:
                 raise ValueError("index_select: plan does not match index / input.size(dim)")
-            hub_bytes = L.gnnops_hub_workspace_bytes(E, 0, 0) if B == 1 else 0   # hot rows: hub.h
-            hub_ws = torch.empty(hub_bytes, dtype=torch.uint8, device=input.device) if hub_bytes else None
+            # hot rows: hub.h
+            hub_ws, hub_ptr, hub_bytes = _hub_workspace(L.gnnops_hub_workspace_bytes(E, 0, 0) if B == 1 else 0, input.device)
             rc = L.gnnops_index_select_planned_hubs(input.data_ptr(), plan.rowptr.data_ptr(), plan.perm.data_ptr(),
                                                     out.data_ptr(), B, N, K, E, eb,
-                                                    hub_ws.data_ptr() if hub_ws is not None else None, hub_bytes, _stream())
+                                                    hub_ptr, hub_bytes, _stream())
         else:
             rc = L.gnnops_index_select(input.data_ptr(), index.data_ptr(), out.data_ptr(), B, N, K, E, eb, _stream())
     check(rc, "index_select")

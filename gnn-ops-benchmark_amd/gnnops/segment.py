@@ -7,7 +7,7 @@ import torch
 
 from . import _lib
 from ._lib import REDUCE_CODE, check
-from .ops import Plan, _bek, _check_index, _dtype_code, _norm_dim, _on, _require_gpu, _row_index_of, _stream, get_plan
+from .ops import Plan, _bek, _check_index, _dtype_code, _hub_workspace, _norm_dim, _on, _require_gpu, _row_index_of, _stream, get_plan
 
 _MODES = {"softmax": 0, "log_softmax": 1, "logsumexp": 2, "std": 3}
 
@@ -180,13 +180,13 @@ def _composite(src, index, dim, dim_size, mode, param):
         shape[dim] = plan.N
     out = torch.empty(shape, dtype=src.dtype, device=src.device)
     L = _lib.load()
-    hub_bytes = L.gnnops_hub_workspace_bytes(E, K, _lib.MIN) if B == 1 else 0   # groups with more than 8192 members: hub.h
-    hub_ws = torch.empty(hub_bytes, dtype=torch.uint8, device=src.device) if hub_bytes else None
+    # groups with more than 8192 members: hub.h
+    hub_ws, hub_ptr, hub_bytes = _hub_workspace(L.gnnops_hub_workspace_bytes(E, K, _lib.MIN) if B == 1 else 0, src.device)
     with _on(src.device):
         rc = L.gnnops_segment_composite_hubs(src.data_ptr(), plan.rowptr.data_ptr(),
                                              plan.perm.data_ptr() if plan.perm is not None else None, out.data_ptr(),
                                              B, E, K, plan.N, dt, _MODES[mode], float(param),
-                                             hub_ws.data_ptr() if hub_ws is not None else None, hub_bytes, _stream())
+                                             hub_ptr, hub_bytes, _stream())
     check(rc, "segment_composite")
     return out
 
