@@ -339,16 +339,9 @@ int launch_bucket(const void* src, const uint32_t* keys, const uint32_t* vals, c
     const int kchunks = (int)gnnops_cdiv(vecs, (int64_t)1 << gshift);
     const int grid = gnnops_grid_cap(NB, 256 * 16);
     constexpr bool want_arg = (R == GNNOPS_MIN || R == GNNOPS_MAX);
-    hub::Ws hw{};
-    int hub_on = 0;
-    if (hub_ws && E > hub::T_HUB) {
-        const hub::Layout hl = hub::layout(E, K, want_arg);
-        if (hub_ws_bytes >= hl.total) {
-            hw = hub::make_ws(hub_ws, hl, E, want_arg);
-            if (gnnops_memset_async(hw.counters, 0, 8, stream) != hipSuccess) return gnnops_check_launch("hub memset");
-            hub_on = 1;
-        }
-    }
+    hub::Ws hw;
+    const int hub_on = hub::open(hub_ws, hub_ws_bytes, E, K, want_arg, stream, hw);
+    if (hub_on < 0) return gnnops_check_launch("hub memset");
     hipLaunchKernelGGL((bucket_reduce_kernel<T, R>), dim3(grid), dim3(THREADS), 0, stream, (const T*)src, keys, vals, bptr,
                        (T*)out, arg_out, E, K, N, NB, gshift, kchunks, init_from_out, is_mean, hw, hub_on, spare_keys,
                        spare_vals);
@@ -557,16 +550,9 @@ extern "C" int gnnops_bucket_select_hubs(const void* input, const void* workspac
     const int gshift = gnnops_group_shift(lanes);
     const int chunks = (int)gnnops_cdiv(lanes, (int64_t)1 << gshift);
     const int grid = gnnops_grid_cap(NB, 256 * 16);
-    hub::Ws hw{};
-    int hub_on = 0;
-    if (hub_workspace && E > hub::T_HUB) {
-        const hub::Layout hl = hub::layout(E, 0, false);
-        if (hub_workspace_bytes >= hl.total) {
-            hw = hub::make_ws(hub_workspace, hl, E, false);
-            if (gnnops_memset_async(hw.counters, 0, 8, stream) != hipSuccess) return gnnops_check_launch("hub memset");
-            hub_on = 1;
-        }
-    }
+    hub::Ws hw;
+    const int hub_on = hub::open(hub_workspace, hub_workspace_bytes, E, 0, false, stream, hw);
+    if (hub_on < 0) return gnnops_check_launch("hub memset");
     uint32_t* sk = (uint32_t*)(const_cast<char*>(w) + (last ? l.keys_a : l.keys_b));   // spare half of the ping-pong buffers
     uint32_t* sv = (uint32_t*)(const_cast<char*>(w) + (last ? l.vals_a : l.vals_b));
     hipLaunchKernelGGL((bucket_push_kernel<8>), dim3(grid), dim3(THREADS), 0, stream, (const char*)input, keys, vals, bptr,

@@ -218,44 +218,30 @@ __global__ __launch_bounds__(hub::THREADS) void chub_stat2_kernel(const T* __res
     constexpr int VEC = Elem<T>::VEC;
     __shared__ int32_t s_match[hub::PART];
     __shared__ float s_part[hub::THREADS * VEC];
-    const int tid = threadIdx.x;
-    const int G = 1 << gshift, gl = tid & (G - 1), gi = tid >> gshift, groups = hub::THREADS >> gshift;
+    const hub::Lanes l(gshift);
     const float NEG_INF = -__builtin_huge_valf();
-    int npieces = w.counters[1];
-    if (npieces > w.cap_p) npieces = w.cap_p;
-    for (int q = blockIdx.x; q < npieces; q += gridDim.x) {
-        const int h = w.pieces[2 * q];
-        if (h < 0) continue;
-        const int pno = w.pieces[2 * q + 1];
-        const int beg = w.hubs[4 * h + 1], end = w.hubs[4 * h + 2];
-        const int pb = beg + pno * hub::PART;
-        const int n = (end - pb < hub::PART) ? end - pb : hub::PART;
+    const int np = hub::npieces(w);
+    for (int q = blockIdx.x; q < np; q += gridDim.x) {
+        hub::Piece p;
+        if (!hub::piece_at(w, q, p)) continue;
         __syncthreads();
-        for (int i = tid; i < n; i += hub::THREADS) s_match[i] = perm ? perm[pb + i] : pb + i;
+        const int n = hub::stage_piece(p, perm, s_match);
         __syncthreads();
-        const int part = (n + groups - 1) / groups;
-        const int jb = gi * part, je = (jb + part < n) ? jb + part : n;
+        int jb, je;
+        hub::slice(n, l, jb, je);
         for (int chunk = 0; chunk < kchunks; ++chunk) {
-            const int64_t col = ((int64_t)chunk * G + gl) * VEC;
+            const int64_t col = ((int64_t)chunk * l.G + l.gl) * VEC;
             float a1[VEC], acc[VEC];
 #pragma unroll
             for (int v = 0; v < VEC; ++v) { acc[v] = 0.f; a1[v] = 0.f; }
             if (col < K) {
 #pragma unroll
-                for (int v = 0; v < VEC; ++v) a1[v] = chub_stat1<MODE>(w, h, K, col + v);
-                for (int j = jb; j < je; j += U) {
-                    int32_t e[U];
-                    u32x4 rows[U];
-#pragma unroll
-                    for (int u = 0; u < U; ++u) e[u] = (j + u < je) ? s_match[j + u] : -1;
-#pragma unroll
-                    for (int u = 0; u < U; ++u)
-                        if (e[u] >= 0) rows[u] = *reinterpret_cast<const u32x4*>(src + (int64_t)e[u] * K + col);
-#pragma unroll
-                    for (int u = 0; u < U; ++u) {
-                        if (e[u] < 0) continue;
+                for (int v = 0; v < VEC; ++v) a1[v] = chub_stat1<MODE>(w, p.h, K, col + v);
+                hub::for_rows(
+                    s_match, jb, je, [&](int32_t e) { return *reinterpret_cast<const u32x4*>(src + (int64_t)e * K + col); },
+                    [&](int32_t, const u32x4& row) {
                         float f[VEC];
-                        Elem<T>::unpack(rows[u], f);
+                        Elem<T>::unpack(row, f);
 #pragma unroll
                         for (int v = 0; v < VEC; ++v) {
                             float d = f[v] - a1[v];
@@ -266,21 +252,11 @@ __global__ __launch_bounds__(hub::THREADS) void chub_stat2_kernel(const T* __res
                                 acc[v] += expf(d);
                             }
                         }
-                    }
-                }
+                    });
             }
-#pragma unroll
-            for (int v = 0; v < VEC; ++v) s_part[tid * VEC + v] = acc[v];
-            __syncthreads();
-            if (gi == 0 && col < K) {
-#pragma unroll
-                for (int v = 0; v < VEC; ++v) {
-                    float a = s_part[gl * VEC + v];
-                    for (int g = 1; g < groups; ++g) a += s_part[(g * G + gl) * VEC + v];
-                    partial2[(int64_t)q * K + col + v] = a;
-                }
-            }
-            __syncthreads();
+            hub::fold_groups<VEC>(
+                l, col < K, acc, s_part, [](float& a, float f) { a += f; return false; },
+                [&](int v, float a, int32_t) { partial2[(int64_t)q * K + col + v] = a; });
         }
     }
 }
@@ -292,57 +268,49 @@ __global__ __launch_bounds__(hub::THREADS) void chub_finish_kernel(const T* __re
                                                                    int kchunks, float param) {
     constexpr int VEC = Elem<T>::VEC;
     __shared__ int32_t s_match[hub::PART];
-    const int tid = threadIdx.x;
-    const int G = 1 << gshift, gl = tid & (G - 1), gi = tid >> gshift, groups = hub::THREADS >> gshift;
+    const hub::Lanes l(gshift);
     const float NEG_INF = -__builtin_huge_valf();
-    int npieces = w.counters[1];
-    if (npieces > w.cap_p) npieces = w.cap_p;
+    const int npieces = hub::npieces(w);
     for (int q = blockIdx.x; q < npieces; q += gridDim.x) {
-        const int h = w.pieces[2 * q];
-        if (h < 0) continue;
-        const int pno = w.pieces[2 * q + 1];
-        const int dst = w.hubs[4 * h], beg = w.hubs[4 * h + 1], end = w.hubs[4 * h + 2], cnt = w.hubs[4 * h + 3];
+        hub::Piece p;
+        if (!hub::piece_at(w, q, p)) continue;
         constexpr bool PER_MEMBER = (MODE == MODE_SOFTMAX || MODE == MODE_LOG_SOFTMAX);
-        if (!PER_MEMBER && pno != 0) continue;   // one output row per group: piece 0's workgroup writes it
-        const int pb = beg + pno * hub::PART;
-        const int n = (end - pb < hub::PART) ? end - pb : hub::PART;
-        const int np = (end - beg + hub::PART - 1) / hub::PART;
-        const int pbase = w.piece_base[h];
+        if (!PER_MEMBER && p.pno != 0) continue;   // one output row per group: piece 0's workgroup writes it
+        const int np = (p.end - p.beg + hub::PART - 1) / hub::PART;
+        const int pbase = w.piece_base[p.h];
         __syncthreads();
-        if (PER_MEMBER) {
-            for (int i = tid; i < n; i += hub::THREADS) s_match[i] = perm ? perm[pb + i] : pb + i;
-        }
+        if (PER_MEMBER) hub::stage_piece(p, perm, s_match);
         __syncthreads();
         for (int chunk = 0; chunk < kchunks; ++chunk) {
-            const int64_t col = ((int64_t)chunk * G + gl) * VEC;
+            const int64_t col = ((int64_t)chunk * l.G + l.gl) * VEC;
             if (col >= K) continue;
             float a1[VEC], a2[VEC];
 #pragma unroll
             for (int v = 0; v < VEC; ++v) {
-                a1[v] = chub_stat1<MODE>(w, h, K, col + v);
+                a1[v] = chub_stat1<MODE>(w, p.h, K, col + v);
                 float t = 0.f;
-                for (int p = 0; p < np; ++p) t += partial2[(int64_t)(pbase + p) * K + col + v];
+                for (int i = 0; i < np; ++i) t += partial2[(int64_t)(pbase + i) * K + col + v];
                 a2[v] = t;
             }
             if constexpr (!PER_MEMBER) {
-                if (gi == 0) {
+                if (l.gi == 0) {
                     float r[VEC];
-                    int32_t cc = (MODE == MODE_STD && param != 0.f) ? cnt - 1 : cnt;
+                    int32_t cc = (MODE == MODE_STD && param != 0.f) ? p.deg - 1 : p.deg;
                     if (cc < 1) cc = 1;
 #pragma unroll
                     for (int v = 0; v < VEC; ++v)
                         r[v] = (MODE == MODE_STD) ? sqrtf(a2[v] / ((float)cc + 1e-6f)) : a1[v] + logf(a2[v] + param);
-                    store16<true>(out + (int64_t)dst * K + col, Elem<T>::pack(r));
+                    store16<true>(out + (int64_t)p.dst * K + col, Elem<T>::pack(r));
                 }
             } else {
                 float lg[VEC];
 #pragma unroll
                 for (int v = 0; v < VEC; ++v) lg[v] = logf(a2[v] + param);
-                for (int j0 = gi; j0 < n; j0 += groups * U) {
+                for (int j0 = l.gi; j0 < p.n; j0 += l.groups * U) {
 #pragma unroll
                     for (int u = 0; u < U; ++u) {
-                        const int j = j0 + u * groups;
-                        if (j >= n) continue;
+                        const int j = j0 + u * l.groups;
+                        if (j >= p.n) continue;
                         const int64_t e = s_match[j];
                         float f[VEC];
                         Elem<T>::unpack(*reinterpret_cast<const u32x4*>(src + e * K + col), f);
@@ -363,7 +331,7 @@ __global__ __launch_bounds__(hub::THREADS) void chub_finish_kernel(const T* __re
 template <typename T, int MODE>
 void launch_chub(const T* src, const int32_t* perm, T* out, const hub::Ws& w, int64_t E, int64_t K, int gshift, int kchunks,
                  float param, hipStream_t stream) {
-    const int ga = w.cap_p < 2048 ? w.cap_p : 2048;
+    const int ga = hub::piece_grid(w);
     float* partial2 = reinterpret_cast<float*>(w.parg);
     hub::Ws w1 = w;
     w1.parg = nullptr;  // pass 1 keeps no positions: the second buffer belongs to pass 2
@@ -379,52 +347,43 @@ void launch_chub(const T* src, const int32_t* perm, T* out, const hub::Ws& w, in
                        gshift, kchunks, param);
 }
 
+// fn(std::integral_constant<int, MODE>{}) for the runtime mode; what fn returns. Any other code is refused here.
+template <typename Fn>
+int with_mode(int mode, Fn&& fn) {
+    switch (mode) {
+        case MODE_SOFTMAX: return fn(std::integral_constant<int, MODE_SOFTMAX>{});
+        case MODE_LOG_SOFTMAX: return fn(std::integral_constant<int, MODE_LOG_SOFTMAX>{});
+        case MODE_LOGSUMEXP: return fn(std::integral_constant<int, MODE_LOGSUMEXP>{});
+        case MODE_STD: return fn(std::integral_constant<int, MODE_STD>{});
+    }
+    gnnops_set_error("segment_composite: unknown mode %d", mode);
+    return GNNOPS_EINVAL;
+}
+
 template <typename T>
 int dispatch(int mode, const void* src, const int32_t* rowptr, const int32_t* perm, void* out, int64_t B, int64_t E,
              int64_t K, int64_t N, float param, hipStream_t stream, void* hub_ws, size_t hub_ws_bytes) {
-    constexpr int VEC = Elem<T>::VEC;
-    if (K % VEC == 0 && (uintptr_t)src % 16 == 0 && (uintptr_t)out % 16 == 0) {
-        const int64_t vecs = K / VEC;
-        const int gshift = gnnops_group_shift(vecs);
-        const int kchunks = (int)gnnops_cdiv(vecs, (int64_t)1 << gshift);
-        const int rgrid = gnnops_grid_cap(gnnops_cdiv(B * kchunks * N, 256 >> gshift), 256 * 64);
-        hub::Ws hw{};
-        int hub_on = 0;
-        if (hub_ws && B == 1 && E > hub::T_HUB) {
-            const hub::Layout hl = hub::layout(E, K, true);   // two partial buffers: the statistics of passes 1 and 2
-            if (hub_ws_bytes >= hl.total) {
-                hw = hub::make_ws(hub_ws, hl, E, true);
-                if (gnnops_memset_async(hw.counters, 0, 8, stream) != hipSuccess) return gnnops_check_launch("hub memset");
-                hub_on = 1;
-            }
+    return with_mode(mode, [&](auto m) {
+        constexpr int M = decltype(m)::value;
+        constexpr int VEC = Elem<T>::VEC;
+        if (K % VEC == 0 && (uintptr_t)src % 16 == 0 && (uintptr_t)out % 16 == 0) {
+            const int64_t vecs = K / VEC;
+            const int gshift = gnnops_group_shift(vecs);
+            const int kchunks = (int)gnnops_cdiv(vecs, (int64_t)1 << gshift);
+            const int rgrid = gnnops_grid_cap(gnnops_cdiv(B * kchunks * N, 256 >> gshift), 256 * 64);
+            hub::Ws hw;  // two partial buffers (want_arg): the statistics of passes 1 and 2
+            const int hub_on = hub::open(B == 1 ? hub_ws : nullptr, hub_ws_bytes, E, K, true, stream, hw);
+            if (hub_on < 0) return gnnops_check_launch("hub memset");
+            hipLaunchKernelGGL((seg_composite_rows_kernel<T, M>), dim3(rgrid), dim3(256), 0, stream, (const T*)src, rowptr, perm,
+                               (T*)out, B, E, K, N, gshift, kchunks, param, hw, hub_on);
+            if (hub_on) launch_chub<T, M>((const T*)src, perm, (T*)out, hw, E, K, gshift, kchunks, param, stream);
+        } else {
+            const int grid = gnnops_grid_cap(gnnops_cdiv(B * N * K, 256), 256 * 32);
+            hipLaunchKernelGGL((seg_composite_kernel<T, M>), dim3(grid), dim3(256), 0, stream, (const T*)src, rowptr, perm,
+                               (T*)out, B, E, K, N, param);
         }
-#define LAUNCH_ROWS(M)                                                                                                  \
-    hipLaunchKernelGGL((seg_composite_rows_kernel<T, M>), dim3(rgrid), dim3(256), 0, stream, (const T*)src, rowptr, perm,  \
-                       (T*)out, B, E, K, N, gshift, kchunks, param, hw, hub_on);                                           \
-    if (hub_on) launch_chub<T, M>((const T*)src, perm, (T*)out, hw, E, K, gshift, kchunks, param, stream)
-        switch (mode) {
-            case MODE_SOFTMAX: LAUNCH_ROWS(MODE_SOFTMAX); break;
-            case MODE_LOG_SOFTMAX: LAUNCH_ROWS(MODE_LOG_SOFTMAX); break;
-            case MODE_LOGSUMEXP: LAUNCH_ROWS(MODE_LOGSUMEXP); break;
-            case MODE_STD: LAUNCH_ROWS(MODE_STD); break;
-            default: gnnops_set_error("segment_composite: unknown mode %d", mode); return GNNOPS_EINVAL;
-        }
-#undef LAUNCH_ROWS
         return gnnops_check_launch("segment_composite");
-    }
-    const int grid = gnnops_grid_cap(gnnops_cdiv(B * N * K, 256), 256 * 32);
-#define LAUNCH(M)                                                                                              \
-    hipLaunchKernelGGL((seg_composite_kernel<T, M>), dim3(grid), dim3(256), 0, stream, (const T*)src, rowptr, perm, \
-                       (T*)out, B, E, K, N, param)
-    switch (mode) {
-        case MODE_SOFTMAX: LAUNCH(MODE_SOFTMAX); break;
-        case MODE_LOG_SOFTMAX: LAUNCH(MODE_LOG_SOFTMAX); break;
-        case MODE_LOGSUMEXP: LAUNCH(MODE_LOGSUMEXP); break;
-        case MODE_STD: LAUNCH(MODE_STD); break;
-        default: gnnops_set_error("segment_composite: unknown mode %d", mode); return GNNOPS_EINVAL;
-    }
-#undef LAUNCH
-    return gnnops_check_launch("segment_composite");
+    });
 }
 
 }  // namespace

@@ -823,16 +823,9 @@ extern "C" int gnnops_index_select_planned_hubs(const void* input, const int32_t
     RowGeom g = row_geom(rowbytes / 16);
     const int64_t items = B * g.chunks * N;
     const int grid = gnnops_grid_cap(gnnops_cdiv(items, 256 >> g.gshift), 256 * 64);
-    hub::Ws hw{};
-    int hub_on = 0;
-    if (hub_workspace && B == 1 && E > hub::T_HUB) {
-        const hub::Layout hl = hub::layout(E, 0, false);
-        if (hub_workspace_bytes >= hl.total) {
-            hw = hub::make_ws(hub_workspace, hl, E, false);
-            if (gnnops_memset_async(hw.counters, 0, 8, stream) != hipSuccess) return gnnops_check_launch("hub memset");
-            hub_on = 1;
-        }
-    }
+    hub::Ws hw;
+    const int hub_on = hub::open(B == 1 ? hub_workspace : nullptr, hub_workspace_bytes, E, 0, false, stream, hw);
+    if (hub_on < 0) return gnnops_check_launch("hub memset");
     hipLaunchKernelGGL((select_rows_push_kernel<true, true, 8>), dim3(grid), dim3(256), 0, stream, (const char*)input,
                        rowptr, perm, (char*)out, B, N, E, rowbytes, g.gshift, g.chunks, hw, hub_on);
     if (hub_on)

@@ -19,6 +19,18 @@
 // Bucket form: the partition groups a bucket's entries in source order but does not separate its 256 destinations, so a
 // piece is PART entries of the BUCKET, filtered by destination on chip (stable compaction), and at most MAX_PER_BUCKET
 // hubs of one bucket (those with the smallest ids) are set aside — the others take the sequential path.
+//
+// The five kernels that finish a hub by pieces (hub_partial_kernel, hub_partial_spmm_kernel, hub_push_kernel here,
+// chub_stat2_kernel and chub_finish_kernel of composite.hip) share ONE walk, the device helpers below:
+//   npieces / piece_at   the clamped piece count and the record of piece q (false: dropped); the loop stays in the kernel
+//   stage_piece          the piece's source positions into s_match, in order: perm[..] (identity without perm); the bucket
+//                        form's stable compaction is HUB_STAGE_BUCKET_PIECE, one text expanded in the two kernels that have it
+//   Lanes / slice        lane-group geometry of the workgroup and the contiguous part of a piece one group takes
+//   for_rows             the step of U rows in flight: positions, then every load, then the rows consumed in order (the SpMM
+//                        kernel keeps its own: it reads column and weight with the positions)
+//   fold_groups          the groups' partials through LDS, folded by group 0 in group (= source) order
+// and the host side: open (workspace -> Ws, counters cleared) and piece_grid (workgroups of a piece pass).
+// What each helper does to the compiled kernels, and why two are shaped as they are: profiles/hub_walk.txt.
 #pragma once
 #include "common.h"
 
@@ -75,6 +87,19 @@ inline Ws make_ws(void* base, const Layout& l, int64_t E, bool want_arg) {
     return s;
 }
 
+// Host: hubs are set aside when the caller brought a workspace (pass nullptr where the entry point's own condition rules
+// them out) that is large enough for E contributions of K columns. 1: w is ready and its counters are cleared on the
+// stream; 0: no hubs, w is empty; -1: the clear could not be launched.
+inline int open(void* ws, size_t bytes, int64_t E, int64_t K, bool want_arg, hipStream_t stream, Ws& w) {
+    w = Ws{};
+    if (!ws || E <= T_HUB) return 0;
+    const Layout l = layout(E, K, want_arg);
+    if (bytes < l.total) return 0;
+    w = make_ws(ws, l, E, want_arg);
+    return gnnops_memset_async(w.counters, 0, 8, stream) == hipSuccess ? 1 : -1;
+}
+inline int piece_grid(const Ws& w) { return w.cap_p < 2048 ? w.cap_p : 2048; }  // workgroups of a pass over the pieces
+
 // One thread: set a hub aside. The capacities cannot be exceeded (see above); should they be, the record is dropped and
 // the counters saturate at the capacity in the readers (the hub would be lost, which the bound rules out).
 __device__ inline void append(const Ws& w, int dst, int beg, int end, int deg) {
@@ -93,8 +118,114 @@ __device__ inline void append(const Ws& w, int dst, int beg, int end, int deg) {
     }
 }
 
-// A workgroup per piece: (1) the piece's source positions into LDS, in order — perm[beg + ...] (plan form) or the
-// positions of the bucket entries that belong to the hub (bucket form, stable compaction); (2) the lane groups reduce
+// ---- the shared walk of the piece passes -------------------------------------------------------------------------------
+struct Piece { int h, pno, dst, beg, end, deg, pb, n; };  // hub, piece number in it, the hub's record, first entry and length of the piece
+
+__device__ inline int npieces(const Ws& w) {  // saturates at the capacity (see append)
+    const int n = w.counters[1];
+    return n > w.cap_p ? w.cap_p : n;
+}
+
+__device__ inline bool piece_at(const Ws& w, int q, Piece& p) {
+    p.h = w.pieces[2 * q];
+    if (p.h < 0) return false;
+    p.pno = w.pieces[2 * q + 1];
+    p.dst = w.hubs[4 * p.h], p.beg = w.hubs[4 * p.h + 1], p.end = w.hubs[4 * p.h + 2], p.deg = w.hubs[4 * p.h + 3];
+    p.pb = p.beg + p.pno * PART;
+    p.n = (p.end - p.pb < PART) ? p.end - p.pb : PART;
+    return true;
+}
+
+// Plan form: the piece's source positions perm[pb + i] (the entries themselves without perm) into s_match, in order; returns
+// how many. The caller's barriers stand before and after.
+__device__ inline int stage_piece(const Piece p, const int32_t* perm, int32_t* s_match) {
+    for (int i = threadIdx.x; i < p.n; i += THREADS) s_match[i] = perm ? perm[p.pb + i] : p.pb + i;
+    return p.n;
+}
+
+// Bucket form: the positions of those entries of the bucket's piece that belong to the hub, compacted into s_match —
+// consecutive entries per thread and an exclusive scan of the counts keep it stable. A macro, not a function: called as a
+// function it costs hub_partial_kernel<float, SUM / MUL, true> and <__half, MUL, true> a wave per SIMD
+// (profiles/hub_walk.txt), expanded in place both kernels that use it compile as they did with their own copies.
+#define HUB_STAGE_BUCKET_PIECE(p, keys, vals, s_match, s_tmp, m)                                         \
+    {                                                                                                    \
+        constexpr int IPT = PART / THREADS;                                                              \
+        const uint32_t low = (uint32_t)(p).dst & 255u;                                                   \
+        uint32_t pos[IPT];                                                                               \
+        uint32_t c = 0;                                                                                  \
+        _Pragma("unroll") for (int j = 0; j < IPT; ++j) {                                                \
+            const int i = threadIdx.x * IPT + j;                                                         \
+            pos[j] = 0xffffffffu;                                                                        \
+            if (i < (p).n && ((keys)[(p).pb + i] & 255u) == low) { pos[j] = (vals)[(p).pb + i]; ++c; }   \
+        }                                                                                                \
+        uint32_t tot;                                                                                    \
+        uint32_t off = block_excl_scan_u32<THREADS / 64>(c, s_tmp, &tot);                                \
+        _Pragma("unroll") for (int j = 0; j < IPT; ++j)                                                  \
+            if (pos[j] != 0xffffffffu) (s_match)[off++] = (int32_t)pos[j];                               \
+        (m) = (int)tot;                                                                                  \
+    }
+
+struct Lanes {  // the workgroup as lane groups of G = 2^gshift lanes: lane gl of group gi
+    int G, gl, gi, groups;
+    __device__ explicit Lanes(int gshift)
+        : G(1 << gshift), gl(threadIdx.x & (G - 1)), gi(threadIdx.x >> gshift), groups(THREADS >> gshift) {}
+};
+
+// the contiguous part [jb, je) of a piece's m positions that the lane group takes
+__device__ inline void slice(int m, const Lanes l, int& jb, int& je) {
+    const int part = (m + l.groups - 1) / l.groups;
+    jb = l.gi * part;
+    je = (jb + part < m) ? jb + part : m;
+}
+
+// U rows in flight over s_match[jb .. je): the positions are read, then every load(e) is issued, then use(e, row) runs in
+// source order.
+template <typename Load, typename Use>
+__device__ inline void for_rows(const int32_t* s_match, int jb, int je, Load load, Use use) {
+    for (int j = jb; j < je; j += U) {
+        int32_t e[U];
+        decltype(load(0)) rows[U];
+#pragma unroll
+        for (int u = 0; u < U; ++u) e[u] = (j + u < je) ? s_match[j + u] : -1;
+#pragma unroll
+        for (int u = 0; u < U; ++u)
+            if (e[u] >= 0) rows[u] = load(e[u]);
+#pragma unroll
+        for (int u = 0; u < U; ++u)
+            if (e[u] >= 0) use(e[u], rows[u]);
+    }
+}
+
+// Every lane's VEC partials (and, ARG, their positions) through LDS; the lanes of group 0 that are `live` fold those of
+// groups 1 .. groups - 1 onto their own in group (= source) order — take(a, f) folds f into a and says whether f's position
+// replaces a's — and hand each result to store(v, a, position). Ends on a barrier: s_part may be written again.
+template <int VEC, bool ARG = false, typename Take, typename Store>
+__device__ inline void fold_groups(const Lanes l, bool live, const float* acc, float* s_part, Take take, Store store,
+                                   const int32_t* arg = nullptr, int32_t* s_parg = nullptr) {
+    const int tid = threadIdx.x;
+#pragma unroll
+    for (int v = 0; v < VEC; ++v) {
+        s_part[tid * VEC + v] = acc[v];
+        if constexpr (ARG) s_parg[tid * VEC + v] = arg[v];
+    }
+    __syncthreads();
+    if (l.gi == 0 && live) {
+#pragma unroll
+        for (int v = 0; v < VEC; ++v) {
+            float a = s_part[l.gl * VEC + v];
+            int32_t ar = ARG ? s_parg[l.gl * VEC + v] : 0;
+            for (int g = 1; g < l.groups; ++g) {
+                if (take(a, s_part[(g * l.G + l.gl) * VEC + v])) {
+                    if constexpr (ARG) ar = s_parg[(g * l.G + l.gl) * VEC + v];
+                }
+            }
+            store(v, a, ar);
+        }
+    }
+    __syncthreads();
+}
+
+// A workgroup per piece: (1) the piece's source positions into LDS, in order (stage_piece); (2) the lane groups reduce
 // contiguous parts of that list; (3) their partials are combined in group order into partial[piece].
 template <typename T, int R, bool BUCKET>
 __global__ __launch_bounds__(THREADS) void hub_partial_kernel(const T* __restrict__ src, const int32_t* __restrict__ perm,
@@ -107,102 +238,55 @@ __global__ __launch_bounds__(THREADS) void hub_partial_kernel(const T* __restric
     __shared__ uint32_t s_tmp[THREADS / 64];
     __shared__ float s_part[THREADS * VEC];
     __shared__ int32_t s_parg[IS_ARG ? THREADS * VEC : 1];
-    const int tid = threadIdx.x;
-    const int G = 1 << gshift, gl = tid & (G - 1), gi = tid >> gshift, groups = THREADS >> gshift;
-    int npieces = w.counters[1];
-    if (npieces > w.cap_p) npieces = w.cap_p;
-    for (int q = blockIdx.x; q < npieces; q += gridDim.x) {
-        const int h = w.pieces[2 * q];
-        if (h < 0) continue;
-        const int pno = w.pieces[2 * q + 1];
-        const int dst = w.hubs[4 * h], beg = w.hubs[4 * h + 1], end = w.hubs[4 * h + 2];
-        const int pb = beg + pno * PART;
-        const int n = (end - pb < PART) ? end - pb : PART;
+    const Lanes l(gshift);
+    auto take = [](float& a, float f) {  // min / max: the first of equal values keeps its position
+        if constexpr (IS_ARG) {
+            if (!Red<R>::better(f, a)) return false;
+            a = f;
+            return true;
+        } else {
+            a = Red<R>::apply(a, f);
+            return false;
+        }
+    };
+    const int np = npieces(w);
+    for (int q = blockIdx.x; q < np; q += gridDim.x) {
+        Piece p;
+        if (!piece_at(w, q, p)) continue;
         __syncthreads();  // the previous piece's readers are done with the LDS arrays
         int m;
-        if constexpr (!BUCKET) {
-            for (int i = tid; i < n; i += THREADS) s_match[i] = perm[pb + i];
-            m = n;
-        } else {
-            constexpr int IPT = PART / THREADS;  // consecutive entries per thread: keeps the compaction stable
-            const uint32_t low = (uint32_t)dst & 255u;
-            uint32_t pos[IPT];
-            uint32_t c = 0;
-#pragma unroll
-            for (int j = 0; j < IPT; ++j) {
-                const int i = tid * IPT + j;
-                pos[j] = 0xffffffffu;
-                if (i < n && (keys[pb + i] & 255u) == low) { pos[j] = vals[pb + i]; ++c; }
-            }
-            uint32_t tot;
-            uint32_t off = block_excl_scan_u32<THREADS / 64>(c, s_tmp, &tot);
-#pragma unroll
-            for (int j = 0; j < IPT; ++j)
-                if (pos[j] != 0xffffffffu) s_match[off++] = (int32_t)pos[j];
-            m = (int)tot;
-        }
+        if constexpr (BUCKET) HUB_STAGE_BUCKET_PIECE(p, keys, vals, s_match, s_tmp, m)
+        else m = stage_piece(p, perm, s_match);
         __syncthreads();
-        const int part = (m + groups - 1) / groups;
-        const int jb = gi * part, je = (jb + part < m) ? jb + part : m;
+        int jb, je;
+        slice(m, l, jb, je);
         for (int chunk = 0; chunk < kchunks; ++chunk) {
-            const int64_t col = ((int64_t)chunk * G + gl) * VEC;
+            const int64_t col = ((int64_t)chunk * l.G + l.gl) * VEC;
             float acc[VEC];
             int32_t arg[VEC];
 #pragma unroll
             for (int v = 0; v < VEC; ++v) { acc[v] = Red<R>::identity(); arg[v] = (int32_t)E; }
             if (col < K) {
                 const T* srcb = src + col;
-                for (int j = jb; j < je; j += U) {
-                    int32_t e[U];
-                    u32x4 rows[U];
+                for_rows(
+                    s_match, jb, je, [&](int32_t e) { return load16<true>(srcb + (int64_t)e * K); },
+                    [&](int32_t e, const u32x4& row) {
+                        float f[VEC];
+                        Elem<T>::unpack(row, f);
 #pragma unroll
-                    for (int u = 0; u < U; ++u) e[u] = (j + u < je) ? s_match[j + u] : -1;
-#pragma unroll
-                    for (int u = 0; u < U; ++u)
-                        if (e[u] >= 0) rows[u] = load16<true>(srcb + (int64_t)e[u] * K);
-#pragma unroll
-                    for (int u = 0; u < U; ++u) {
-                        if (e[u] >= 0) {
-                            float f[VEC];
-                            Elem<T>::unpack(rows[u], f);
-#pragma unroll
-                            for (int v = 0; v < VEC; ++v) {
-                                if constexpr (IS_ARG) {
-                                    if (Red<R>::better(f[v], acc[v])) { acc[v] = f[v]; arg[v] = e[u]; }
-                                } else {
-                                    acc[v] = Red<R>::apply(acc[v], f[v]);
-                                }
-                            }
-                        }
-                    }
-                }
+                        for (int v = 0; v < VEC; ++v)
+                            if (take(acc[v], f[v])) arg[v] = e;
+                    });
             }
-#pragma unroll
-            for (int v = 0; v < VEC; ++v) {
-                s_part[tid * VEC + v] = acc[v];
-                if constexpr (IS_ARG) s_parg[tid * VEC + v] = arg[v];
-            }
-            __syncthreads();
-            if (gi == 0 && col < K) {  // fold the groups' partials in group (= source) order
-#pragma unroll
-                for (int v = 0; v < VEC; ++v) {
-                    float a = s_part[gl * VEC + v];
-                    int32_t ar = IS_ARG ? s_parg[gl * VEC + v] : 0;
-                    for (int g = 1; g < groups; ++g) {
-                        const float f = s_part[(g * G + gl) * VEC + v];
-                        if constexpr (IS_ARG) {
-                            if (Red<R>::better(f, a)) { a = f; ar = s_parg[(g * G + gl) * VEC + v]; }
-                        } else {
-                            a = Red<R>::apply(a, f);
-                        }
-                    }
+            fold_groups<VEC, IS_ARG>(
+                l, col < K, acc, s_part, take,
+                [&](int v, float a, int32_t ar) {
                     w.partial[(int64_t)q * K + col + v] = a;
                     if constexpr (IS_ARG) {
                         if (w.parg) w.parg[(int64_t)q * K + col + v] = ar;
                     }
-                }
-            }
-            __syncthreads();
+                },
+                arg, s_parg);
         }
     }
 }
@@ -276,28 +360,23 @@ __global__ __launch_bounds__(THREADS) void hub_partial_spmm_kernel(const int32_t
     constexpr int VEC = Elem<T>::VEC;
     __shared__ int32_t s_match[PART];
     __shared__ float s_part[THREADS * VEC];
-    const int tid = threadIdx.x;
-    const int G = 1 << gshift, gl = tid & (G - 1), gi = tid >> gshift, groups = THREADS >> gshift;
-    int npieces = w.counters[1];
-    if (npieces > w.cap_p) npieces = w.cap_p;
-    for (int q = blockIdx.x; q < npieces; q += gridDim.x) {
-        const int h = w.pieces[2 * q];
-        if (h < 0) continue;
-        const int pno = w.pieces[2 * q + 1];
-        const int beg = w.hubs[4 * h + 1], end = w.hubs[4 * h + 2];
-        const int pb = beg + pno * PART;
-        const int n = (end - pb < PART) ? end - pb : PART;
+    const Lanes l(gshift);
+    const int np = npieces(w);
+    for (int q = blockIdx.x; q < np; q += gridDim.x) {
+        Piece p;
+        if (!piece_at(w, q, p)) continue;
         __syncthreads();
-        for (int i = tid; i < n; i += THREADS) s_match[i] = perm ? perm[pb + i] : pb + i;
+        const int n = stage_piece(p, perm, s_match);
         __syncthreads();
-        const int part = (n + groups - 1) / groups;
-        const int jb = gi * part, je = (jb + part < n) ? jb + part : n;
+        int jb, je;
+        slice(n, l, jb, je);
         for (int chunk = 0; chunk < kchunks; ++chunk) {
-            const int64_t c0 = ((int64_t)chunk * G + gl) * VEC;
+            const int64_t c0 = ((int64_t)chunk * l.G + l.gl) * VEC;
             float acc[VEC];
 #pragma unroll
             for (int v = 0; v < VEC; ++v) acc[v] = 0.f;
             if (c0 < D) {
+                // not for_rows: column and weight of a nonzero are read with the positions, ahead of the rows of mat that hang on them
                 for (int j = jb; j < je; j += U) {
                     int64_t c[U];
                     float wt[U];
@@ -325,18 +404,9 @@ __global__ __launch_bounds__(THREADS) void hub_partial_spmm_kernel(const int32_t
                     }
                 }
             }
-#pragma unroll
-            for (int v = 0; v < VEC; ++v) s_part[tid * VEC + v] = acc[v];
-            __syncthreads();
-            if (gi == 0 && c0 < D) {
-#pragma unroll
-                for (int v = 0; v < VEC; ++v) {
-                    float a = s_part[gl * VEC + v];
-                    for (int g = 1; g < groups; ++g) a = __fadd_rn(a, s_part[(g * G + gl) * VEC + v]);
-                    w.partial[(int64_t)q * D + c0 + v] = a;
-                }
-            }
-            __syncthreads();
+            fold_groups<VEC>(
+                l, c0 < D, acc, s_part, [](float& a, float f) { a = __fadd_rn(a, f); return false; },
+                [&](int v, float a, int32_t) { w.partial[(int64_t)q * D + c0 + v] = a; });
         }
     }
 }
@@ -344,9 +414,8 @@ __global__ __launch_bounds__(THREADS) void hub_partial_spmm_kernel(const int32_t
 template <typename T>
 inline void launch_spmm_pass(const int32_t* perm, const int64_t* col, const T* value, const T* mat, T* out, const Ws& w,
                              int64_t nnz, int64_t D, int gshift, int kchunks, hipStream_t stream) {
-    const int ga = w.cap_p < 2048 ? w.cap_p : 2048;
-    hipLaunchKernelGGL((hub_partial_spmm_kernel<T>), dim3(ga), dim3(THREADS), 0, stream, perm, col, value, mat, w, D, gshift,
-                       kchunks);
+    hipLaunchKernelGGL((hub_partial_spmm_kernel<T>), dim3(piece_grid(w)), dim3(THREADS), 0, stream, perm, col, value, mat, w, D,
+                       gshift, kchunks);
     const int64_t items = (int64_t)w.cap_h * kchunks;
     const int gb = gnnops_grid_cap(gnnops_cdiv(items, THREADS >> gshift), 1024);
     hipLaunchKernelGGL((hub_combine_kernel<T, GNNOPS_SUM>), dim3(gb), dim3(THREADS), 0, stream, out, (int64_t*)nullptr, w, nnz,
@@ -364,50 +433,25 @@ __global__ __launch_bounds__(THREADS) void hub_push_kernel(const char* __restric
                                                            int chunks) {
     __shared__ int32_t s_match[PART];
     __shared__ uint32_t s_tmp[THREADS / 64];
-    const int tid = threadIdx.x;
-    const int G = 1 << gshift, gl = tid & (G - 1), gi = tid >> gshift, groups = THREADS >> gshift;
-    int npieces = w.counters[1];
-    if (npieces > w.cap_p) npieces = w.cap_p;
-    for (int q = blockIdx.x; q < npieces; q += gridDim.x) {
-        const int h = w.pieces[2 * q];
-        if (h < 0) continue;
-        const int pno = w.pieces[2 * q + 1];
-        const int dst = w.hubs[4 * h], beg = w.hubs[4 * h + 1], end = w.hubs[4 * h + 2];
-        const int pb = beg + pno * PART;
-        const int n = (end - pb < PART) ? end - pb : PART;
+    const Lanes l(gshift);
+    const int np = npieces(w);
+    for (int q = blockIdx.x; q < np; q += gridDim.x) {
+        Piece p;
+        if (!piece_at(w, q, p)) continue;
         __syncthreads();
         int m;
-        if constexpr (!BUCKET) {
-            for (int i = tid; i < n; i += THREADS) s_match[i] = perm[pb + i];
-            m = n;
-        } else {
-            constexpr int IPT = PART / THREADS;
-            const uint32_t low = (uint32_t)dst & 255u;
-            uint32_t pos[IPT];
-            uint32_t c = 0;
-#pragma unroll
-            for (int j = 0; j < IPT; ++j) {
-                const int i = tid * IPT + j;
-                pos[j] = 0xffffffffu;
-                if (i < n && (keys[pb + i] & 255u) == low) { pos[j] = vals[pb + i]; ++c; }
-            }
-            uint32_t tot;
-            uint32_t off = block_excl_scan_u32<THREADS / 64>(c, s_tmp, &tot);
-#pragma unroll
-            for (int j = 0; j < IPT; ++j)
-                if (pos[j] != 0xffffffffu) s_match[off++] = (int32_t)pos[j];
-            m = (int)tot;
-        }
+        if constexpr (BUCKET) HUB_STAGE_BUCKET_PIECE(p, keys, vals, s_match, s_tmp, m)
+        else m = stage_piece(p, perm, s_match);
         __syncthreads();
         for (int c = 0; c < chunks; ++c) {
-            const int64_t colb = ((int64_t)c * G + gl) * 16;
+            const int64_t colb = ((int64_t)c * l.G + l.gl) * 16;
             if (colb >= rowbytes) continue;
-            const u32x4 v = load16<false>(in + (int64_t)dst * rowbytes + colb);
+            const u32x4 v = load16<false>(in + (int64_t)p.dst * rowbytes + colb);
             char* outb = out + colb;
-            for (int j0 = gi; j0 < m; j0 += groups * U) {   // groups interleave: neighbouring positions, neighbouring groups
+            for (int j0 = l.gi; j0 < m; j0 += l.groups * U) {   // groups interleave: neighbouring positions, neighbouring groups
 #pragma unroll
                 for (int u = 0; u < U; ++u) {
-                    const int j = j0 + u * groups;
+                    const int j = j0 + u * l.groups;
                     if (j < m) store16<true>(outb + (int64_t)s_match[j] * rowbytes, v);
                 }
             }
@@ -417,13 +461,12 @@ __global__ __launch_bounds__(THREADS) void hub_push_kernel(const char* __restric
 
 inline void launch_push_pass(bool bucket, const char* in, const int32_t* perm, const uint32_t* keys, const uint32_t* vals,
                              char* out, const Ws& w, int64_t rowbytes, int gshift, int chunks, hipStream_t stream) {
-    const int ga = w.cap_p < 2048 ? w.cap_p : 2048;
     if (bucket)
-        hipLaunchKernelGGL((hub_push_kernel<true>), dim3(ga), dim3(THREADS), 0, stream, in, perm, keys, vals, out, w, rowbytes,
-                           gshift, chunks);
+        hipLaunchKernelGGL((hub_push_kernel<true>), dim3(piece_grid(w)), dim3(THREADS), 0, stream, in, perm, keys, vals, out, w,
+                           rowbytes, gshift, chunks);
     else
-        hipLaunchKernelGGL((hub_push_kernel<false>), dim3(ga), dim3(THREADS), 0, stream, in, perm, keys, vals, out, w, rowbytes,
-                           gshift, chunks);
+        hipLaunchKernelGGL((hub_push_kernel<false>), dim3(piece_grid(w)), dim3(THREADS), 0, stream, in, perm, keys, vals, out, w,
+                           rowbytes, gshift, chunks);
 }
 
 // The two launches that follow a main kernel which set hubs aside (they exit at once when there are none).
@@ -431,13 +474,14 @@ template <typename T, int R, bool BUCKET>
 inline void launch_pass(const T* src, const int32_t* perm, const uint32_t* keys, const uint32_t* vals, T* out,
                         int64_t* arg_out, const Ws& w, int64_t E, int64_t K, int gshift, int kchunks, int init_from_out,
                         int is_mean, hipStream_t stream) {
-    const int ga = w.cap_p < 2048 ? w.cap_p : 2048;
-    hipLaunchKernelGGL((hub_partial_kernel<T, R, BUCKET>), dim3(ga), dim3(THREADS), 0, stream, src, perm, keys, vals, w, E, K,
-                       gshift, kchunks);
+    hipLaunchKernelGGL((hub_partial_kernel<T, R, BUCKET>), dim3(piece_grid(w)), dim3(THREADS), 0, stream, src, perm, keys, vals,
+                       w, E, K, gshift, kchunks);
     const int64_t items = (int64_t)w.cap_h * kchunks;
     const int gb = gnnops_grid_cap(gnnops_cdiv(items, THREADS >> gshift), 1024);
     hipLaunchKernelGGL((hub_combine_kernel<T, R>), dim3(gb), dim3(THREADS), 0, stream, out, arg_out, w, E, K, gshift, kchunks,
                        init_from_out, is_mean);
 }
+
+#undef HUB_STAGE_BUCKET_PIECE
 
 }  // namespace hub

@@ -325,18 +325,10 @@ int launch_seg(const void* src, const int32_t* rowptr, const int32_t* perm, void
         int grid = blk_map ? gnnops_grid_cap(gnnops_cdiv(items, SEG_BLOCK), 256 * 16)
                            : gnnops_grid_cap(gnnops_cdiv(items, 256 >> gshift), 256 * 64);
         // hubs (hub.h) are set aside when the caller brought the workspace for them: plan form, one matrix
-        constexpr bool IS_ARG_R = (R == GNNOPS_MIN || R == GNNOPS_MAX);
-        const bool want_arg = IS_ARG_R;
-        hub::Ws hw{};
-        int hub_on = 0;
-        if (hub_ws && perm && B == 1 && E > hub::T_HUB) {
-            const hub::Layout hl = hub::layout(E, K, want_arg);
-            if (hub_ws_bytes >= hl.total) {
-                hw = hub::make_ws(hub_ws, hl, E, want_arg);
-                if (gnnops_memset_async(hw.counters, 0, 8, stream) != hipSuccess) return gnnops_check_launch("hub memset");
-                hub_on = 1;
-            }
-        }
+        constexpr bool want_arg = (R == GNNOPS_MIN || R == GNNOPS_MAX);
+        hub::Ws hw;
+        const int hub_on = hub::open(perm && B == 1 ? hub_ws : nullptr, hub_ws_bytes, E, K, want_arg, stream, hw);
+        if (hub_on < 0) return gnnops_check_launch("hub memset");
         hipLaunchKernelGGL((seg_rows_kernel<T, R>), dim3(grid), dim3(256), 0, stream, (const T*)src, rowptr, perm,
                            (T*)out, arg_out, B, E, K, N, gshift, kchunks, init_from_out, is_mean, hw, hub_on, blk_map);
         if (hub_on)

@@ -295,16 +295,9 @@ int launch(const int32_t* rowptr, const int32_t* perm, const int64_t* col, const
         // a dense operand far beyond the 256 MiB Infinity Cache is streamed nontemporally (its rows would only evict
         // the CSR arrays); a smaller one keeps normal caching so repeated rows hit on-die
         const bool nt = (size_t)mat_rows * (size_t)D * sizeof(T) > ((size_t)2 << 30);
-        hub::Ws hw{};
-        int hub_on = 0;
-        if (hub_ws && nnz > hub::T_HUB) {
-            const hub::Layout hl = hub::layout(nnz, D, false);
-            if (hub_ws_bytes >= hl.total) {
-                hw = hub::make_ws(hub_ws, hl, nnz, false);
-                if (gnnops_memset_async(hw.counters, 0, 8, stream) != hipSuccess) return gnnops_check_launch("hub memset");
-                hub_on = 1;
-            }
-        }
+        hub::Ws hw;
+        const int hub_on = hub::open(hub_ws, hub_ws_bytes, nnz, D, false, stream, hw);
+        if (hub_on < 0) return gnnops_check_launch("hub memset");
         if (nt)
             hipLaunchKernelGGL((spmm_rows_kernel<T, true>), dim3(grid), dim3(256), 0, stream, rowptr, perm, col,
                                (const T*)value, (const T*)mat, (T*)out, M, D, gshift, kchunks, hw, hub_on);
